@@ -18,8 +18,20 @@ timed region rank 0 checks assembled frames against the oracle (u8 frames byte f
 
 Prints ONE JSON line on rank 0 (contract in the task description) including
   roofline      algorithmic bytes of the dominant kernel / its HIP-event launch time vs 8 TB/s
+
+A plain run (no --full) sets up, warms up, times --steps steps, writes --dump-outputs if asked and
+prints the line.  --full adds everything else, each in runs of its own after the timed steps:
+  per_frame, fast_colour, ref_layout   other call patterns / modes of the same frames (N = 1)
   cpu_baseline  the CPU oracle (a port of the reference's march; the reference has no CPU
                 renderer) timed on this host's cores on a bounded sample (rank 0, N = 1 only)
+  parity        GPU frames against the oracle (N = 1: the CPU baseline's poses; N > 1: the
+                frames assembled on rank 0)
+  footprints, live_call, cfg5, cfg3, cfg4_n1, cfg5_cfg3, fog   the secondary workloads (N = 1, cfg2)
+
+--dump-outputs DIR writes what the timed path computed in its last step (the frames) as float32
+.npy files, at most 64 MB in all: rgba_frame0.npy (the batch's first frame, when it is at most
+40 MB) and rgba_sample.npy (2^20 pixels of the whole batch at positions drawn with a fixed seed).
+The inputs are synthetic and seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -715,6 +727,22 @@ def extras_live_call(mnv, cases, orc, torch, dev, tree, cams, opt):
     return res
 
 
+DUMP_SAMPLE_PIXELS = 1 << 20         # 16 MB of float RGBA
+DUMP_FRAME_MAX_BYTES = 40 << 20      # a 1920x1080 float RGBA frame is 33 MB; with the sample at most 64 MB in all
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the frames of the timed path's last step (N x H x W x 4, float or RGBA8) as float32 .npy files under `out_dir`:
+    rgba_frame0.npy = frame 0 whole (if it takes at most DUMP_FRAME_MAX_BYTES as float32), rgba_sample.npy = DUMP_SAMPLE_PIXELS pixels of
+    the whole batch, at sorted flat positions drawn with seed 0 (the same positions in every run with the same arguments)."""
+    os.makedirs(out_dir, exist_ok=True)
+    if frames[0].numel() * 4 <= DUMP_FRAME_MAX_BYTES:
+        np.save(os.path.join(out_dir, "rgba_frame0.npy"), frames[0].float().cpu().numpy())
+    flat = frames.reshape(-1, frames.shape[-1])
+    idx = np.sort(np.random.default_rng(0).integers(0, flat.shape[0], size=min(DUMP_SAMPLE_PIXELS, flat.shape[0])))
+    np.save(os.path.join(out_dir, "rgba_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+
+
 def predicted_step(world, root_period, n_frames, workload):
     """ms per step that the one-GPU emulation of one rank of `world` measured for this partition (the latest profiles/rNN_root_emulation.jsonl, tools/root_emulation.py: rank 0's
     march beside a device copy of the incoming tiles and the un-permute; 64 frames of cfg2 per step), so that the line of a real N-GPU run
@@ -745,8 +773,13 @@ def main():
     ap.add_argument("--gather", choices=["f32", "u8"], default="u8",
                     help="pixel format rendered and gathered to rank 0 when N > 1: u8 = the reference's own output format "
                          "(RGBA8, renderer_kernel.cu:237; 8.3 MB per frame), f32 = the float RGBA the parity tests compare (33.2 MB per frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline (per_frame, fast_colour, ref_layout, "
+                         "cpu_baseline, parity, footprints and the secondary workloads); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step to DIR as float32 .npy files (frame 0 and a fixed, seeded sample; at most 64 MB)")
     ap.add_argument("--cpu-poses", type=int, default=16, help="poses rendered by the CPU baseline and compared bit for bit with the GPU frames (default: the whole 16-pose orbit, about 5 s on 128 host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline, no parity check and no secondary workloads")
     ap.add_argument("--kernel", choices=["accel", "ref_layout"], default="accel")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend for N > 1; gloo (host-staged gather, all ranks may share one GPU) is the single-GPU rehearsal of the multi-GPU path")
@@ -775,7 +808,7 @@ def main():
                     help="N > 1: abi = mnv_gather_tiles (libmnv's own RCCL gather, the product path); torch = torch.distributed's gather "
                          "(the launcher's second attempt if the first one fails or wedges)")
     ap.add_argument("--launch-timeout", type=float, default=600.0, help="--gpus N > 1 without a launcher: watchdog for the ranks this process starts (s)")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the secondary numbers for the other BASELINE configs (cfg3, cfg4_n1, cfg5)")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N = 1: skip the secondary numbers for the other BASELINE configs (cfg3, cfg4_n1, cfg5)")
     ap.add_argument("--test-fail-reserved", action="store_true", help=argparse.SUPPRESS)   # rehearsal of the launcher's ladder; reads no environment
     ap.add_argument("--laps", type=int, default=4, help="the step walks the 16-pose orbit this many times (16 x laps frames in one launch, <= 64)")
     args = ap.parse_args()
@@ -784,6 +817,8 @@ def main():
         W, H = 3840, 2160
     if not 1 <= args.laps <= 4:
         raise SystemExit("--laps must be 1 .. 4 (MNV_MAX_BATCH = 64 frames per launch)")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     N_FRAMES = N_POSES * args.laps
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -973,11 +1008,13 @@ def main():
 
     rays_per_step = N_FRAMES * W * H
     value = rays_per_step * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frames[(counter[0] - 1) % RING])
 
     # secondary number: the reference's call pattern -- ONE launch per frame -- with --frame-streams frames in flight
     # (what VolumeRenderer::render does); not the headline, reported beside it
     per_frame = None
-    if not multi and args.kernel == "accel" and not args.per_frame and args.frame_streams >= 1:
+    if args.full and not multi and args.kernel == "accel" and not args.per_frame and args.frame_streams >= 1:
         k = args.frame_streams
         sts = [torch.cuda.Stream(device=dev) for _ in range(k)]
         pf_out = torch.empty_like(frames[0])   # own buffer: the batched frames of the last timed step stay intact for the parity check
@@ -1002,7 +1039,7 @@ def main():
     # transmittance, step sequence and every branch stay on the exact path.  Within the north star's 1e-4 (measured here against the exact
     # frames of the last timed step, which the parity leg below compares bit for bit with the oracle); the headline stays the exact mode.
     fast_colour = None
-    if not multi and args.kernel == "accel" and not args.per_frame and not args.fast_colour and args.frame_streams >= 1:
+    if args.full and not multi and args.kernel == "accel" and not args.per_frame and not args.fast_colour and args.frame_streams >= 1:
         exact = frames[(counter[0] - 1) % RING]
         fc_out = pf_out
         mnv.accel_set_colour_math(tree.accel, 1)
@@ -1024,7 +1061,7 @@ def main():
     # third secondary number: mnv_render_voxels itself -- the literal drop-in on the reference's own arrays (no accel, nothing kept between
     # calls), one call per frame, on one stream and with two frames in flight; bit-identical to the frames above
     ref_layout = None
-    if not multi and args.kernel == "accel" and not args.per_frame and args.frame_streams >= 1:
+    if args.full and not multi and args.kernel == "accel" and not args.per_frame and args.frame_streams >= 1:
         dv_ref = tree.device_view()
         exact = frames[(counter[0] - 1) % RING]
         rl_out = pf_out
@@ -1063,7 +1100,7 @@ def main():
     counters_checked = 0
     cpu_baseline = None
     parity = None
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not multi and not args.no_cpu_baseline:
         import mnv_oracle as orc
         ot = orc.tree_from_view(tree.host_view())
         n_cpu = max(1, min(args.cpu_poses, N_POSES))
@@ -1118,7 +1155,7 @@ def main():
                 raise SystemExit(f"bench.py: tests/golden/{args.workload if args.workload in ('cfg2', 'fog') else 'cfg3'}_counters.json disagrees with the oracle's counters for poses {stale}: "
                                  f"e.g. committed {counters['poses'].get(stale[0])} vs fresh {fresh[stale[0]]}")
             counters_checked = len(fresh)
-    if rank == 0 and multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and multi and not args.no_cpu_baseline:
         # the assembled frames of the last step against the oracle (not timed): validates partition + gather + un-permute
         import mnv_oracle as orc
         ot = orc.tree_from_view(tree.host_view())
@@ -1138,7 +1175,7 @@ def main():
         parity = {"max_abs_drgba_vs_oracle": max_diff, "pixels_not_bit_identical": n_bad, "frames_checked": n_chk,
                   "frames": chk, "what": "frames assembled on rank 0 after the gather"}
     footprints = {}
-    extras_on = rank == 0 and not multi and args.kernel == "accel" and not args.per_frame and args.workload == "cfg2" and not args.no_extras and not args.no_cpu_baseline
+    extras_on = args.full and rank == 0 and not multi and args.kernel == "accel" and not args.per_frame and args.workload == "cfg2" and not args.no_extras and not args.no_cpu_baseline
     if extras_on and N_FRAMES == 64:
         # one pass of the diagnostics instantiation per workload in a child process on the test-hook build: the unique 128-byte lines a launch touches
         footprints = measured_footprints(["cfg2", "cfg3", "cfg4", "fog"])
@@ -1170,7 +1207,7 @@ def main():
                                    "device it left to its neighbour" if n_march_streams > 1 else ""))
 
     cfg345 = {}
-    if rank == 0 and not multi and args.kernel == "accel" and not args.per_frame and args.workload == "cfg2" and not args.no_extras and not args.no_cpu_baseline:
+    if extras_on:
         import mnv_oracle as orc
         try:
             cfg345["live_call"] = extras_live_call(mnv, cases, orc, torch, dev, tree, cams, opt)
@@ -1211,7 +1248,7 @@ def main():
                        "partition": "none" if not multi else f"interleaved {MACRO_W}x{MACRO_H} macro tiles, {args.gather} " + (
                            ("RCCL (mnv_gather_tiles)" if comm is not None else "RCCL (torch.distributed)") if args.backend == "nccl" else ("mnv_gather_tiles over a transport stand-in (MNV_RCCL_LIBRARY)" if comm is not None
                                                                   else "gloo (host-staged rehearsal)")) + " gather to rank 0",
-                       "reserved_cus": reserve, "march_streams": n_march_streams, "root_period": part.root_period if multi else 0},
+                       "reserved_cus": reserve, "march_streams": n_march_streams, "root_period": part.root_period if multi else 0, "full": args.full},
             "roofline": roofline,
             "per_frame": per_frame,
             "fast_colour": fast_colour,

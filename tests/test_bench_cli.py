@@ -34,6 +34,13 @@ def test_world_size_must_equal_gpus():
     assert r.returncode != 0 and "refusing" in r.stderr
 
 
+def test_steps_and_warmup_must_be_counts():
+    for steps, warmup in (("0", "1"), ("2", "-1")):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", steps, "--warmup", warmup], capture_output=True, text=True, timeout=300, env=_env())
+        assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+        assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
 def test_kernel_source_sha_is_stable_and_matches_the_binding():
     sys.path.insert(0, ROOT)
     import bench
@@ -123,3 +130,36 @@ def test_footprint_pass_counts_the_lines_a_launch_touches(torch_gpu):
     lines = sum(v for k, v in a.items() if k.endswith("_lines"))
     assert 0 < a["frame_lines_min"] <= a["frame_lines_max"] <= lines
     assert a["footprint_bytes"] <= a["footprint_frame_by_frame_bytes"] < 4 * a["footprint_bytes"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(torch_gpu, tmp_path):
+    """A plain run (no --full) carries the headline and ms_per_step of exactly --steps timed steps and none of the --full numbers;
+    --dump-outputs writes the last step's frames as float32 (frame 0 whole, the seeded sample at the documented positions), at most
+    64 MB, bit-identical from one run to the next with the same arguments."""
+    import json
+
+    import numpy as np
+
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--laps", "1"]
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run(cmd + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=_env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["roofline"]["launches"] == 3
+        assert line["value"] > 0 and line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert all(line[f] is None for f in ("per_frame", "fast_colour", "ref_layout", "cpu_baseline", "parity")) and "cfg3" not in line
+        assert sorted(p.name for p in d.iterdir()) == ["rgba_frame0.npy", "rgba_sample.npy"]
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        frame0, sample = np.load(d / "rgba_frame0.npy"), np.load(d / "rgba_sample.npy")
+        assert frame0.dtype == np.float32 and sample.dtype == np.float32
+        assert frame0.shape == (1080, 1920, 4) and sample.shape == (1 << 20, 4)
+        idx = np.sort(np.random.default_rng(0).integers(0, 16 * 1080 * 1920, size=1 << 20))
+        in0 = idx < 1080 * 1920
+        assert in0.sum() > 0 and np.array_equal(sample[in0].view(np.uint32), frame0.reshape(-1, 4)[idx[in0]].view(np.uint32))
+        assert np.isfinite(frame0).all() and frame0[..., 3].max() > 0
+        outs.append((frame0, sample))
+    for a, b in zip(outs[0], outs[1]):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))

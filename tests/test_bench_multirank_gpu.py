@@ -1,7 +1,7 @@
 """Rehearsal of bench.py's N > 1 path on ONE GPU: two (three) ranks share cuda:0, the gather goes through
 gloo with host staging instead of RCCL, everything else -- interleaved partition, one batched launch per
 step per rank, ring of in-flight gathers, un-permute on rank 0 -- is the production code path.  The JSON
-line's `parity` field compares frames assembled on rank 0 with the oracle."""
+line's `parity` field (bench.py --full) compares frames assembled on rank 0 with the oracle."""
 import json
 import os
 import socket
@@ -28,7 +28,7 @@ def _port():
 def test_bench_multirank_rehearsal(torch_gpu, world, gather):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--laps", "1",
-           "--backend", "gloo", "--gather", gather]
+           "--backend", "gloo", "--gather", gather, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -42,7 +42,7 @@ def test_bench_starts_its_own_ranks(torch_gpu):
     """`python bench.py --gpus 2` WITHOUT a launcher: bench.py starts the two ranks itself (fresh child processes, the parent never
     touches the GPU) and relays rank 0's line; a line that reports another rank count is an error, not a one-GPU number."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--laps", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--laps", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -58,7 +58,7 @@ def test_bench_launcher_repeats_a_failed_run_conservatively_and_kills_a_wedged_o
     that do not finish within --launch-timeout are killed -- their process group, nothing else -- and the exit code is not 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MNV_LIB_PATH"] = hooks.HOOKS_LIB
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--laps", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--laps", "1", "--full"]
     # (i) the two-step ladder over the stand-in
     e1 = dict(env, MNV_RCCL_LIBRARY=fake_rccl)
     r = subprocess.run(cmd + ["--test-fail-reserved"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=e1)
@@ -86,7 +86,7 @@ def test_bench_multirank_through_the_c_abi_gather(torch_gpu, fake_rccl, world):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MNV_RCCL_LIBRARY"] = fake_rccl
     env["MNV_LIB_PATH"] = hooks.HOOKS_LIB
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "3", "--warmup", "1", "--laps", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "3", "--warmup", "1", "--laps", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -115,7 +115,7 @@ def test_bench_rccl_path_single_rank(torch_gpu, gather, reserve):
     compared with the oracle inside bench.py."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "1", "--laps", "1", "--gather", gather,
-           "--reserve-cus", str(reserve)]
+           "--reserve-cus", str(reserve), "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

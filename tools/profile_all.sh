@@ -31,5 +31,7 @@ python3 tools/prof_summary.py gpurun_out/${R}_guided > gpurun_out/${R}_guided/su
 python3 tools/guided_pmc_summary.py gpurun_out/${R}_guided >> gpurun_out/${R}_guided/summary.txt 2>&1
 MNV_FUSED_DIAG=1 python3 tools/guided_bench.py 32 4 2> /dev/null | grep "^{" > gpurun_out/${R}_guided/phases.json; cat gpurun_out/${R}_guided/phases.json >> gpurun_out/${R}_guided/summary.txt
 cp gpurun_out/${R}_batch/traffic.json profiles/${R}_traffic.json   # on the GPU box's copy: the bench line below then carries this run's traffic
-python3 bench.py --steps 10 --warmup 2 > gpurun_out/${R}_bench_n1.json 2> /dev/null
+# the full bench line (--full: the secondary numbers and checks as well), written next to the batched profile above
+out=$(dirname "$(ls -d "$PWD"/*/"${R}_batch" | head -n 1)")
+python3 bench.py --full --steps 10 --warmup 2 > "$out/${R}_bench_n1.json" 2> /dev/null
 cat gpurun_out/${R}_batch/traffic.json; tail -n 3 gpurun_out/${R}_mem.txt; cat gpurun_out/${R}_bench_n1.json | cut -c1-1200
