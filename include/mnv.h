@@ -682,6 +682,57 @@ int mnv_render_guided_fused_track_part(const mnv_accel *accel, const mnv_camera 
 int mnv_stream_create_reserved(int32_t reserve_cus, void **stream_out, int32_t *enabled_cus);
 int mnv_stream_destroy(void *stream);
 
+/* ------------------------------------------------ the octree grid overlay (RenderOptions::show_grid, grid_max_depth)
+ * The reference draws the edges of N3Tree::gen_wireframe(grid_max_depth) (n3tree.cpp:249-329) with GL into the two attachments its march
+ * then reads with offscreen == false (cuda_renderer.cpp:68-90,111-142): an RGBA8 image cleared to background_brightness with the edges in
+ * black, and an R32F "Depth" image cleared to 1e9 holding the camera-space distance of the nearest edge.  Here the edge list lives on the
+ * device and a line rasteriser writes that pair (mnv_frame_inputs).
+ *
+ * mnv_wireframe: the cubes gen_wireframe would push, built from a DEVICE tree view by a level-synchronous walk (one kernel and one wait per
+ * tree level).  A voxel is a cube when child == 0 || depth >= max_depth (a negative max_depth acts like 0).  N != 2 answers
+ * MNV_E_UNSUPPORTED; a child link outside [1, capacity) MNV_E_INVALID.  _update regenerates in place (after the tree or the depth changed);
+ * both wait for hip_stream.  Calls that read a wireframe on other streams must have finished before it is updated or destroyed. */
+typedef struct mnv_wireframe mnv_wireframe;
+int mnv_wireframe_create(const mnv_tree_view *device_tree, int32_t max_depth, void *hip_stream, mnv_wireframe **out);
+int mnv_wireframe_update(mnv_wireframe *w, const mnv_tree_view *device_tree, int32_t max_depth, void *hip_stream);
+void mnv_wireframe_destroy(mnv_wireframe *w);
+int64_t mnv_wireframe_cube_count(const mnv_wireframe *w);
+/* The segments: device float [n][6] (world endpoints A xyz, B xyz), 12 per cube in _push_wireframe_bb's edge order, the corners in the
+ * reference's float arithmetic; the order of the cubes is unspecified.  *n_segments receives the count (segments_out NULL and
+ * cap_segments 0: the count only); a buffer of fewer than that many segments is MNV_E_INVALID. */
+int mnv_wireframe_segments(const mnv_wireframe *w, float *segments_out, int64_t cap_segments, int64_t *n_segments, void *hip_stream);
+/*
+ * The GL pass as a kernel: writes tile [tile.h][tile.w] of both images (clear values included; either output may be NULL), the
+ * mnv_frame_inputs pair of the frame.  rgba8_out must be 4-byte aligned (else MNV_E_INVALID).  Raster contract (float32, this order, no contraction):
+ *   1. camera coordinates: c2w columns r, u, b, C; d = P - C; X = (r0*d0 + r1*d1) + r2*d2, Y likewise with u,
+ *      z = -((b0*d0 + b1*d1) + b2*d2)
+ *   2. near clip: a segment with both z < 1e-3f is dropped; if one endpoint has z < 1e-3f it moves along the camera-space segment to
+ *      t = (1e-3f - z_in) / (z_out - z_in), X_in = X_in + t*(X_out - X_in) (Y alike), z_in = 1e-3f.  No far plane, no x/y clip.
+ *   3. pixels: px = cx + fx*(X/z), py = cy - fy*(Y/z) (pixel (x, y) is centred at (x+0.5, y+0.5): the inverse of screen2worlddir,
+ *      renderer_kernel.cu:30-38); dx = px_b - px_a, dy = py_b - py_a, dd = dx*dx + dy*dy; dd == 0 (or not finite): nothing
+ *   4. line rule: x-major when |dx| >= |dy|: one fragment in every column x whose centre xc = x + 0.5f lies in [min px, max px), in
+ *      row floor(py_a + ((xc - px_a) / dx) * dy); y-major alike with rows; fragments outside the tile are discarded
+ *   5. fragment value: t = clamp(((xc - px_a)*dx + (yc - py_a)*dy) / dd, 0, 1) at the pixel centre (xc, yc); qa = (1 - t)/z_a,
+ *      qb = t/z_b, s = qa + qb; X = (qa*X_a + qb*X_b)/s, Y alike, Z = (qa*z_a + qb*z_b)/s; dist = sqrt((X*X + Y*Y) + Z*Z);
+ *      key = bits(Z) << 32 | bits(dist), the smallest key of a pixel wins
+ *   6. outputs: a pixel with a fragment: tmax = dist, rgba8 = (0,0,0,255); else tmax = 1e9f, rgba8 = (c,c,c,255) with
+ *      c = floor(clamp(background_brightness, 0, 1)*255 + 0.5)
+ * Deliberate deviations from the GL pass: the principal point is the camera's cx, cy (the reference's K ignores them); depth ties are
+ * broken by the key (GL keeps the first-drawn fragment); the fragments are this rule's, not a particular GL driver's.
+ */
+int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mnv_render_options *opt, mnv_rect tile, float *tmax_px_out,
+                         uint8_t *rgba8_out, void *hip_stream);
+/* How mnv_render_wireframe resolves depth; the images are bit-identical either way (the smallest key wins whatever the order).
+ *   MNV_WIREFRAME_BINNED  (edge, 32x32 screen tile) pairs are counted, scanned and listed per tile (one wait for the pair total), then one
+ *                         workgroup per tile resolves its fragments with 64-bit atomicMin in LDS
+ *   MNV_WIREFRAME_GLOBAL  thread per edge, a 64-bit global atomicMin per fragment into a key image, then a resolve pass
+ *   MNV_WIREFRAME_AUTO    (default) the one measured faster for the edge count
+ * Scratch is kept per HIP stream; calls on one stream from several host threads are serialised by the object. */
+#define MNV_WIREFRAME_AUTO 0
+#define MNV_WIREFRAME_BINNED 1
+#define MNV_WIREFRAME_GLOBAL 2
+int mnv_wireframe_set_method(mnv_wireframe *w, int32_t method);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -702,6 +753,10 @@ int mnv_n3tree_move_to_device(mnv_n3tree *t, int64_t max_capacity, int need_pare
 int mnv_n3tree_device_view(const mnv_n3tree *t, mnv_tree_view *view);
 const mnv_accel *mnv_n3tree_accel(const mnv_n3tree *t);
 int mnv_n3tree_save_npz(const mnv_n3tree *t, const char *npz_path); /* svox layout, stored (no deflate) */
+/* N3Tree::gen_wireframe (n3tree.cpp:249-329) on the host arrays: 24 vertices of 9 floats (position, colour 0,0,0, normal 0,0,1) per cube,
+ * in the reference's order and float arithmetic.  *n_floats receives the length; out NULL with cap_floats 0 asks for it alone; a buffer
+ * shorter than that is MNV_E_INVALID (and *n_floats still says what it needs). */
+int mnv_n3tree_gen_wireframe(const mnv_n3tree *t, int32_t max_depth, float *out, int64_t cap_floats, int64_t *n_floats);
 /* DataFormat::parse / to_string (src/data_format.cpp:5-41) */
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim);
 int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size_t buflen);
@@ -774,6 +829,12 @@ int32_t mnv_renderer_last_slot(const mnv_renderer *r);
 int mnv_renderer_download_slot(mnv_renderer *r, int32_t slot, float *rgba_host, uint8_t *rgba8_host);
 /* copy the (refined) device tree back into the mnv_n3tree's host arrays */
 int mnv_renderer_sync_tree(mnv_renderer *r);
+/* options.show_grid: render() draws the grid of options.grid_max_depth with mnv_render_wireframe into per-slot images and passes them to
+ * the frame as its mnv_frame_inputs (refused together with caller-set frame inputs or several ranks).  The wireframe of the last grid
+ * frame (NULL before the first): regenerated when the depth or the tree changed.  Owned by the renderer. */
+const mnv_wireframe *mnv_renderer_wireframe(const mnv_renderer *r);
+/* the camera (pose matrix and intrinsics) the last mnv_renderer_render used */
+int mnv_renderer_camera(const mnv_renderer *r, mnv_camera *out);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

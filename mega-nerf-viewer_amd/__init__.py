@@ -325,6 +325,16 @@ _SIGNATURES = {
     "mnv_synth_random_tree": (C.c_int, [C.POINTER(SynthRandomParams), C.POINTER(C.c_void_p)]),
     "mnv_synth_shell_tree": (C.c_int, [C.POINTER(SynthShellParams), C.POINTER(C.c_void_p)]),
     "mnv_synth_terrain_tree": (C.c_int, [C.POINTER(SynthTerrainParams), C.POINTER(C.c_void_p)]),
+    "mnv_n3tree_gen_wireframe": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "mnv_wireframe_create": (C.c_int, [C.POINTER(TreeView), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mnv_wireframe_update": (C.c_int, [C.c_void_p, C.POINTER(TreeView), C.c_int32, C.c_void_p]),
+    "mnv_wireframe_destroy": (None, [C.c_void_p]),
+    "mnv_wireframe_cube_count": (C.c_int64, [C.c_void_p]),
+    "mnv_wireframe_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    "mnv_render_wireframe": (C.c_int, [C.c_void_p, C.POINTER(CameraStruct), C.POINTER(RenderOptions), Rect, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_renderer_wireframe": (C.c_void_p, [C.c_void_p]),
+    "mnv_renderer_camera": (C.c_int, [C.c_void_p, C.POINTER(CameraStruct)]),
+    "mnv_wireframe_set_method": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -579,6 +589,16 @@ class N3Tree:
 
     def save_npz(self, path: str) -> None:
         _check(lib().mnv_n3tree_save_npz(self._h, os.fsencode(path)))
+
+    def gen_wireframe(self, max_depth: int = 100000) -> np.ndarray:
+        """N3Tree::gen_wireframe (n3tree.cpp:249-329) on the host arrays: float32 [n_vertices, 9] (position, colour, normal), 24 vertices
+        (12 edges) per cube in the reference's order."""
+        n = C.c_int64(0)
+        _check(lib().mnv_n3tree_gen_wireframe(self._h, int(max_depth), None, 0, C.byref(n)))
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            _check(lib().mnv_n3tree_gen_wireframe(self._h, int(max_depth), out.ctypes.data, out.size, C.byref(n)))
+        return out.reshape(-1, 9)
 
 
 def _ptr(t) -> Optional[int]:
@@ -1142,11 +1162,95 @@ class Renderer:
     def last_slot(self) -> int:
         return int(lib().mnv_renderer_last_slot(self._h))
 
+    def last_camera(self) -> CameraStruct:
+        """The camera (matrix and intrinsics) the last render() used."""
+        c = CameraStruct()
+        _check(lib().mnv_renderer_camera(self._h, C.byref(c)))
+        return c
+
+    def wireframe(self) -> int:
+        """Raw mnv_wireframe handle of the last show_grid frame (0 before the first); owned by the renderer."""
+        return lib().mnv_renderer_wireframe(self._h) or 0
+
     def download_slot(self, slot: int, want_rgba8=False):
         rgba = np.empty((self.height, self.width, 4), np.float32)
         rgba8 = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
         _check(lib().mnv_renderer_download_slot(self._h, int(slot), rgba.ctypes.data, rgba8.ctypes.data if want_rgba8 else None))
         return (rgba, rgba8) if want_rgba8 else rgba
+
+
+WIREFRAME_AUTO, WIREFRAME_BINNED, WIREFRAME_GLOBAL = 0, 1, 2
+
+
+class Wireframe:
+    """mnv_wireframe: the grid overlay's edge list on the device, built from a device tree view (N3Tree::gen_wireframe's cubes)."""
+
+    def __init__(self, tree_view: TreeView, max_depth: int, stream: int = 0):
+        h = C.c_void_p()
+        _check(lib().mnv_wireframe_create(C.byref(tree_view), int(max_depth), C.c_void_p(stream), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                lib().mnv_wireframe_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @property
+    def handle(self) -> int:
+        return self._h.value
+
+    def update(self, tree_view: TreeView, max_depth: int, stream: int = 0) -> None:
+        _check(lib().mnv_wireframe_update(self._h, C.byref(tree_view), int(max_depth), C.c_void_p(stream)))
+
+    def set_method(self, method: int) -> None:
+        """WIREFRAME_AUTO / WIREFRAME_BINNED / WIREFRAME_GLOBAL: how mnv_render_wireframe resolves depth (same images either way)."""
+        _check(lib().mnv_wireframe_set_method(self._h, int(method)))
+
+    @property
+    def cube_count(self) -> int:
+        return int(lib().mnv_wireframe_cube_count(self._h))
+
+    def segments(self, stream: int = 0):
+        """float32 device tensor [n, 6]: the world endpoints (A, B) of every edge, 12 per cube in _push_wireframe_bb's order."""
+        return wireframe_segments(self._h.value, stream)
+
+    def render(self, cam: Camera, opt: RenderOptions, tile=None, tmax_px=None, rgba8=None, stream: int = 0):
+        return render_wireframe(self._h.value, cam, opt, tile, tmax_px, rgba8, stream)
+
+
+def wireframe_segments(wire: int, stream: int = 0):
+    """mnv_wireframe_segments of a raw mnv_wireframe handle (e.g. Renderer.wireframe()) into a new float32 device tensor [n, 6]."""
+    import torch
+
+    n = C.c_int64(0)
+    _check(lib().mnv_wireframe_segments(C.c_void_p(wire), None, 0, C.byref(n), C.c_void_p(stream)))
+    out = torch.empty((n.value, 6), dtype=torch.float32, device="cuda")
+    if n.value:
+        _check(lib().mnv_wireframe_segments(C.c_void_p(wire), out.data_ptr(), n.value, C.byref(n), C.c_void_p(stream)))
+    return out
+
+
+def render_wireframe(wire: int, cam: Camera, opt: RenderOptions, tile=None, tmax_px=None, rgba8=None, stream: int = 0):
+    """mnv_render_wireframe: the grid pass into (tmax_px float32 [h, w], rgba8 uint8 [h, w, 4]) device tensors (allocated when None);
+    returns both."""
+    import torch
+
+    if tile is None:
+        tile = (0, 0, cam.width, cam.height)
+    w, h = tile[2], tile[3]
+    if tmax_px is None:
+        tmax_px = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    if rgba8 is None:
+        rgba8 = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
+    if not tmax_px.is_cuda or not tmax_px.is_contiguous() or tmax_px.dtype != torch.float32 or tmax_px.numel() < w * h:
+        raise MnvError(MNV_E_INVALID, f"tmax_px must be a contiguous float32 device tensor with at least {w * h} elements")
+    _check_out("rgba8", rgba8, w * h, "u8")
+    _check(lib().mnv_render_wireframe(C.c_void_p(wire), C.byref(cam.c), C.byref(opt), Rect(*tile), tmax_px.data_ptr(), rgba8.data_ptr(),
+                                      C.c_void_p(stream)))
+    return tmax_px, rgba8
 
 
 MAX_BATCH = 64

@@ -1,6 +1,7 @@
 // host_capi.cpp -- extern "C" wrappers of include/mnv.h over the C++ host data model.
 #include <cstring>
 #include <exception>
+#include <stdexcept>
 #include <string>
 
 #include "../../include/mnv.h"
@@ -29,6 +30,8 @@ template <typename F>
 int guarded(F f) {
     try {
         return f();
+    } catch (const viewer::StatusError &e) {  // e.g. show_grid with frame inputs (MNV_E_INVALID), a grid of an N != 2 tree (MNV_E_UNSUPPORTED)
+        return mnv::set_error(e.code, e.what());
     } catch (const std::exception &e) {
         return mnv::set_error(MNV_E_IO, e.what());
     } catch (...) {
@@ -156,6 +159,20 @@ int mnv_n3tree_save_npz(const mnv_n3tree *t, const char *npz_path) {
     return guarded([&] {
         t->tree.save_npz(npz_path);
         return MNV_OK;
+    });
+}
+
+int mnv_n3tree_gen_wireframe(const mnv_n3tree *t, int32_t max_depth, float *out, int64_t cap_floats, int64_t *n_floats) {
+    if (n_floats) *n_floats = 0;
+    if (!t) return mnv::set_error(MNV_E_INVALID, "null tree");
+    if (cap_floats < 0 || (cap_floats > 0 && !out)) return mnv::set_error(MNV_E_INVALID, "invalid output buffer");
+    return guarded([&] {
+        const int64_t n = t->tree.gen_wireframe_floats(max_depth);  // counts, builds nothing
+        if (n_floats) *n_floats = n;
+        if (!out && cap_floats == 0) return (int)MNV_OK;
+        if (cap_floats < n) return mnv::set_error(MNV_E_INVALID, "buffer too small (n_floats holds the length)");
+        t->tree.gen_wireframe_into(max_depth, out);
+        return (int)MNV_OK;
     });
 }
 
@@ -391,6 +408,14 @@ int mnv_renderer_sync_tree(mnv_renderer *r) {
         r->rend.sync_tree();
         return MNV_OK;
     });
+}
+
+const mnv_wireframe *mnv_renderer_wireframe(const mnv_renderer *r) { return r ? r->rend.wireframe() : nullptr; }
+
+int mnv_renderer_camera(const mnv_renderer *r, mnv_camera *out) {
+    if (!r || !out) return mnv::set_error(MNV_E_INVALID, "null argument");
+    *out = r->rend.last_camera();
+    return MNV_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // mnv_render -- offline batch renderer: the reference's `nerf-viewer` command line without the window.
 //
 // Flag names and defaults follow the reference (src/opts.cpp:17-32 common flags, main.cpp:491-505
-// viewer flags); --grid (wireframe overlay) is accepted and ignored.  --model_path names a model container
+// viewer flags).  --grid D draws the octree grid down to depth D over the volume, as the reference's --grid (src/opts.cpp:53-55):
+// the edges of N3Tree::gen_wireframe(D) in black on background_brightness, the march stopping at them (VolumeRenderer, options.show_grid);
+// --bounds_only --grid 0 shows the scene bounds as the root cube cut in eight.  --model_path names a model container
 // (an .npz, see VolumeRenderer::load_model) and enables the refinement flags, which the reference exposes as
 // window check boxes (main.cpp:270-300) rather than flags:
 //   --use_splitting          grow / resample / prune the tree from the per-ray trackers while rendering
@@ -106,7 +108,7 @@ Args parse(int argc, char **argv) {
 void usage() {
     std::puts("usage: mnv_render npz_file [--bg 0.0] [-s step_size] [-e stop_thresh] [-a sigma_thresh] [-c max_tree_capacity]\n"
               "                  [-w width] [-h height] [--fx 1111] [--fy -1] [--cx -1] [--cy -1] [--center x,y,z] [--back x,y,z]\n"
-              "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
+              "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--grid D] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
               "                  [--in_flight K] [--guided_in_flight] [--gpus N [--reserve_cus R] [--root_period M]]\n"
               "                  [--model_path MODEL.npz [--use_splitting] [--use_guided_sampling] [-x split_batch_size] [-v samples_per_voxel]\n"
               "                   [-y appearance_embedding] [-z max_guided_samples] [--max_depth D] [--max_sample_count C] [--seed S]\n"
@@ -146,6 +148,10 @@ void configure(const Args &args, viewer::VolumeRenderer &rend, int width, int he
     rend.options.samples_per_corner = (int)args.l("samples_per_voxel", 8);
     rend.options.appearance_embedding = (int)args.l("appearance_embedding", -1);
     rend.options.max_guided_samples = (int)args.l("max_guided_samples", 128);
+    if (args.has("grid")) {  // src/opts.cpp:53-55
+        rend.options.show_grid = true;
+        rend.options.grid_max_depth = (int)args.l("grid", rend.options.grid_max_depth);
+    }
     rend.camera = viewer::Camera(width, height, args.f("fx", 1111.f), args.f("fy", -1.f), args.f("cx", -1.f), args.f("cy", -1.f));
     const std::vector<float> center = args.vec("center", {-3.5f, 0.f, 3.5f}), back = args.vec("back", {-0.7071068f, 0.f, 0.7071068f}),
                              origin = args.vec("origin", {0.f, 0.f, 0.f}), up = args.vec("world_up", {0.f, 0.f, 1.f});
@@ -512,6 +518,7 @@ int main(int argc, char **argv) {
             usage();
             return args.has("help") ? 0 : 2;
         }
+        if (args.has("gpus") && args.has("grid")) throw std::runtime_error("--grid draws on one GPU: it cannot be combined with --gpus");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 

@@ -316,6 +316,81 @@ void N3Tree::save_npz(const std::string &path) const {
     w.close();
 }
 
+namespace {
+// n3tree.cpp:249-273: the 12 edges of box bb = {x0, y0, z0, x1, y1, z1} as 24 vertices (position, colour 0, normal 0,0,1) at out[0 .. 216)
+void push_wireframe_bb(const float bb[6], float *out) {
+    auto vert = [&](int i, int j, int k) {
+        const float v[9] = {bb[i * 3], bb[j * 3 + 1], bb[k * 3 + 2], 0.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+        for (int c = 0; c < 9; ++c) *out++ = v[c];
+    };
+    for (int i = 0; i < 2; ++i) {
+        for (int j = 0; j < 2; ++j) {
+            vert(0, i, j);
+            vert(1, i, j);
+            vert(i, 0, j);
+            vert(i, 1, j);
+            vert(i, j, 0);
+            vert(i, j, 1);
+        }
+    }
+}
+constexpr int64_t kFloatsPerCube = 24 * 9;
+
+// n3tree.cpp:275-320 on the host arrays (the reference reads every word with .item() from device tensors); cube(bb) per cube pushed
+template <typename Cube>
+void gen_wireframe_impl(const N3Tree &tree, int32_t nodeid, size_t xi, size_t yi, size_t zi, int depth, size_t gridsz, int max_depth, Cube &cube) {
+    const size_t n = (size_t)tree.N;
+    const int n3 = tree.N * tree.N * tree.N;
+    int cnt = 0;
+    for (size_t i = xi * n; i < (xi + 1) * n; ++i) {
+        for (size_t j = yi * n; j < (yi + 1) * n; ++j) {
+            for (size_t k = zi * n; k < (zi + 1) * n; ++k) {
+                const int32_t child = tree.child[(size_t)nodeid * n3 + cnt];
+                if (child == 0 || depth >= max_depth) {
+                    const float bb[6] = {((float)i / gridsz - tree.offset[0]) / tree.scale[0],
+                                         ((float)j / gridsz - tree.offset[1]) / tree.scale[1],
+                                         ((float)k / gridsz - tree.offset[2]) / tree.scale[2],
+                                         ((float)(i + 1) / gridsz - tree.offset[0]) / tree.scale[0],
+                                         ((float)(j + 1) / gridsz - tree.offset[1]) / tree.scale[1],
+                                         ((float)(k + 1) / gridsz - tree.offset[2]) / tree.scale[2]};
+                    cube(bb);
+                } else {
+                    const int64_t next = (int64_t)nodeid + child;
+                    if (next <= 0 || next >= tree.capacity || depth >= 62) throw StatusError(MNV_E_INVALID, "gen_wireframe: a child link leaves the tree");
+                    gen_wireframe_impl(tree, (int32_t)next, i, j, k, depth + 1, gridsz * n, max_depth, cube);
+                }
+                ++cnt;
+            }
+        }
+    }
+}
+}  // namespace
+
+int64_t N3Tree::gen_wireframe_floats(int max_depth) const {
+    int64_t n = 0;
+    auto count = [&](const float *) { n += kFloatsPerCube; };
+    if (N > 0 && capacity > 0) gen_wireframe_impl(*this, 0, 0, 0, 0, /*depth*/ 0, (size_t)N, max_depth, count);
+    return n;
+}
+
+void N3Tree::gen_wireframe_into(int max_depth, float *out) const {
+    auto write = [&](const float *bb) {
+        push_wireframe_bb(bb, out);
+        out += kFloatsPerCube;
+    };
+    if (N > 0 && capacity > 0) gen_wireframe_impl(*this, 0, 0, 0, 0, /*depth*/ 0, (size_t)N, max_depth, write);
+}
+
+std::vector<float> N3Tree::gen_wireframe(int max_depth) const {
+    std::vector<float> verts;
+    auto push = [&](const float *bb) {
+        verts.resize(verts.size() + kFloatsPerCube);
+        push_wireframe_bb(bb, verts.data() + verts.size() - kFloatsPerCube);
+    };
+    if (N > 0 && capacity > 0) gen_wireframe_impl(*this, 0, 0, 0, 0, /*depth*/ 0, (size_t)N, max_depth, push);
+    return verts;
+}
+
 int64_t N3Tree::pack_index(int nd, int i, int j, int k) {
     assert(i < N && j < N && k < N && i >= 0 && j >= 0 && k >= 0);
     return (int64_t)nd * N3_ + i * N2_ + j * N + k;

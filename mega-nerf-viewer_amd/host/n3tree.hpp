@@ -4,12 +4,14 @@
 // Same public surface (open, move_to_device, N, data_dim, data_format, scale, offset,
 // data, child, parent, sample_counts, capacity, pack_index, unpack_index); the
 // torch::Tensor members of the reference become plain host vectors plus raw HIP
-// device buffers -- there is no libtorch in the product.  gen_wireframe (GL overlay
-// only) is not carried.
+// device buffers -- there is no libtorch in the product.  gen_wireframe (the grid overlay's
+// vertex list) is carried on the host arrays; the renderer draws the grid from a device
+// edge list instead (mnv_wireframe, include/mnv.h).
 #pragma once
 
 #include <array>
 #include <cstdint>
+#include <stdexcept>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -18,6 +20,12 @@
 #include "data_format.hpp"
 
 namespace viewer {
+
+// An error that carries its C-ABI status code: the extern "C" wrappers return `code` for it (other exceptions become MNV_E_IO).
+struct StatusError : std::runtime_error {
+    int code;
+    StatusError(int c, const std::string &msg) : std::runtime_error(msg), code(c) {}
+};
 
 struct N3Tree {
     N3Tree();
@@ -77,6 +85,15 @@ struct N3Tree {
     mnv_tree_view host_view() const;
     mnv_tree_view device_view() const;  // pointers are null before move_to_device
     bool on_device() const { return device.data != nullptr; }
+
+    // Vertices of the grid overlay (n3tree.cpp:249-329): every voxel with child == 0 || depth >= max_depth as a cube of
+    // 12 edges = 24 vertices of 9 floats (position, colour 0,0,0, normal 0,0,1), in the reference's order and float arithmetic.
+    // Reads the host arrays (after refinement on the device: copy_from_device first).  A child link outside the tree throws
+    // StatusError(MNV_E_INVALID).  gen_wireframe_floats: the length alone (no vertex is built); gen_wireframe_into: the same vertices
+    // written to out[0 .. gen_wireframe_floats(max_depth)).
+    std::vector<float> gen_wireframe(int max_depth = 100000) const;
+    int64_t gen_wireframe_floats(int max_depth = 100000) const;
+    void gen_wireframe_into(int max_depth, float *out) const;
 
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;

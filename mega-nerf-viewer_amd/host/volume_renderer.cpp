@@ -58,6 +58,8 @@ struct VolumeRenderer::Impl {
         uint8_t *rgba8 = nullptr;
         unsigned long long *count_dev = nullptr, *count_host = nullptr;  // guided frames in flight: this slot's sample counter and its pinned copy
         bool counted = false;                                             // ... which a frame on this slot has written (or is about to)
+        float *grid_tmax = nullptr;                                       // show_grid: this slot's depth image and image under the volume
+        uint8_t *grid_rgba8 = nullptr;
     };
     std::vector<Slot> slots;
     int cur = 0;            // slot of the most recent render()
@@ -89,6 +91,20 @@ struct VolumeRenderer::Impl {
     int quiet_frames = 0;
     long reuse_total = 0;
     uint64_t frame = 0;
+    // show_grid: the device edge list, the depth and the tree structure it was made for (tree_version counts set / splits / prunes)
+    mnv_wireframe *wire = nullptr;
+    mnv_camera last_camera{};  // the camera of the last render()
+    int wire_depth = 0;
+    uint64_t tree_version = 0, wire_version = 0;
+    // the grid pass of this frame into slot S's images on `st`, returned as the frame's inputs (the edge list is current)
+    mnv_frame_inputs grid_inputs(Slot &S, hipStream_t st, const mnv_camera &cv, const RenderOptions &o) {
+        if (!S.grid_tmax) {
+            hip_check(hipMalloc((void **)&S.grid_tmax, (size_t)width * height * sizeof(float)), "hipMalloc(grid depth image)");
+            hip_check(hipMalloc((void **)&S.grid_rgba8, (size_t)width * height * 4), "hipMalloc(grid image)");
+        }
+        mnv_check(mnv_render_wireframe(wire, &cv, o.c_abi(), {0, 0, width, height}, S.grid_tmax, S.grid_rgba8, st), "mnv_render_wireframe");
+        return {S.grid_tmax, S.grid_rgba8};
+    }
     // the fused guided kernel's sample count: copied to pinned memory behind the kernel and read at the frame's LAST wait (the vote's,
     // the tree edit's) instead of at a wait of its own right behind the march -- 20-40 us of a refinement frame
     unsigned long long *count_host = nullptr;
@@ -112,6 +128,7 @@ struct VolumeRenderer::Impl {
     }
     ~Impl() {
         free_frame();
+        if (wire) mnv_wireframe_destroy(wire);
         if (count_host) (void)hipHostFree(count_host);
         if (mlp) mnv_mlp_destroy(mlp);
         for (Slot &s : slots) {
@@ -129,8 +146,12 @@ struct VolumeRenderer::Impl {
             if (s.stream) (void)hipStreamSynchronize(s.stream);
             if (s.rgba) (void)hipFree(s.rgba);
             if (s.rgba8) (void)hipFree(s.rgba8);
+            if (s.grid_tmax) (void)hipFree(s.grid_tmax);
+            if (s.grid_rgba8) (void)hipFree(s.grid_rgba8);
             s.rgba = nullptr;
             s.rgba8 = nullptr;
+            s.grid_tmax = nullptr;
+            s.grid_rgba8 = nullptr;
         }
         rgba = nullptr;
         rgba8 = nullptr;
@@ -240,6 +261,7 @@ void VolumeRenderer::Impl::expand_voxels(RenderOptions &o, FrameStats &st, uint6
               "mnv_apply_split_results");
     const int old_capacity = tree->capacity;
     tree->capacity += n;
+    ++tree_version;
     st.added = n;
     can_reuse_results = false;
     if (!accel_stale) tree->refresh_accel(old_capacity, nullptr, 0, stream);  // the packed layout follows the split
@@ -283,6 +305,7 @@ void VolumeRenderer::Impl::prune_tree(FrameStats &st) {
     st.pruned = n_del > 0 ? n_del : -1;
     if (n_del > 0) {
         tree->capacity = new_cap;
+        ++tree_version;
         tree_changed();
         if (follow) {
             accel_stale = false;
@@ -330,6 +353,7 @@ void VolumeRenderer::set(N3Tree &tree, long max_tree_capacity) {
     tree.move_to_device(max_tree_capacity, true, true, impl_->stream);
     impl_->tree = &tree;
     impl_->max_tree_capacity = max_tree_capacity;
+    ++impl_->tree_version;
     // visit_tracker = zeros, [0] = 1 (cuda_renderer.cpp:504-506)
     int32_t *visited = impl_->visit_tracker.get<int32_t>((size_t)max_tree_capacity);
     hip_check(hipMemsetAsync(visited, 0, (size_t)max_tree_capacity * 4, impl_->stream), "clear visit marks");
@@ -404,7 +428,13 @@ void VolumeRenderer::load_model(const std::string &npz_path) {
     set_model(desc, p.data<uint16_t>(), p.num_vals(), grid);
 }
 
-void VolumeRenderer::clear() { impl_->tree = nullptr; }
+void VolumeRenderer::clear() {
+    impl_->tree = nullptr;
+    ++impl_->tree_version;
+}
+
+const mnv_wireframe *VolumeRenderer::wireframe() const { return impl_->wire; }
+const mnv_camera &VolumeRenderer::last_camera() const { return impl_->last_camera; }
 
 const mnv_mlp *VolumeRenderer::model() const { return impl_->mlp; }
 const mnv_cluster_grid &VolumeRenderer::cluster_grid() const { return impl_->grid; }
@@ -458,8 +488,26 @@ void VolumeRenderer::render() {
     if (!I.slots[0].rgba) resize(camera.width, camera.height);
     camera._update();
     const mnv_camera cv = camera.c_abi();
+    I.last_camera = cv;
     const mnv_rect full = {0, 0, I.width, I.height};
     stats = FrameStats();
+    // show_grid: the grid pass produces this frame's inputs (cuda_renderer.cpp:68-90 draws it before the march)
+    const bool grid = options.show_grid && I.tree != nullptr && I.tree->N > 0;
+    if (grid) {
+        if (I.inputs.tmax_px || I.inputs.rgba8_init)
+            throw StatusError(MNV_E_INVALID, "show_grid draws the frame inputs itself: it cannot be combined with set_frame_inputs");
+        if (I.comm) throw StatusError(MNV_E_INVALID, "show_grid is for one rank: it cannot be combined with set_ranks");
+        if (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version) {
+            I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
+            const mnv_tree_view dv = I.tree->device_view();
+            const int rc = I.wire ? mnv_wireframe_update(I.wire, &dv, options.grid_max_depth, I.stream)
+                                  : mnv_wireframe_create(&dv, options.grid_max_depth, I.stream, &I.wire);
+            if (rc != MNV_OK) throw StatusError(rc, std::string("show_grid: ") + mnv_last_error());  // keeps the code (N != 2: unsupported)
+            I.wire_depth = options.grid_max_depth;
+            I.wire_version = I.tree_version;
+            I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
+        }
+    }
     {
         // a plain frame of a tree with a current accel takes the next slot; everything else runs alone on slot 0
         if (overlaps_next()) {
@@ -474,13 +522,14 @@ void VolumeRenderer::render() {
             I.use_slot((I.cur + 1) % frames_in_flight);
             I.overlapped = true;
             Impl::Slot &S = I.slots[I.cur];
+            const mnv_frame_inputs in = grid ? I.grid_inputs(S, S.stream, cv, options) : I.inputs;
             if (I.mlp != nullptr && options.use_guided_sampling) {  // (overlaps_next: a guided-sampling frame that changes nothing, guided_in_flight)
                 if (!S.count_dev) {
                     hip_check(hipMalloc((void **)&S.count_dev, sizeof(unsigned long long)), "hipMalloc(sample counter)");
                     hip_check(hipHostMalloc((void **)&S.count_host, sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc(sample count)");
                 }
                 hip_check(hipMemsetAsync(S.count_dev, 0, sizeof(unsigned long long), S.stream), "clear sample counter");
-                mnv_check(mnv_render_guided_fused_track_ex(I.tree->device.accel, &cv, options.c_abi(), full, &I.inputs, I.mlp, &I.grid, I.rgba, I.rgba8, nullptr,
+                mnv_check(mnv_render_guided_fused_track_ex(I.tree->device.accel, &cv, options.c_abi(), full, &in, I.mlp, &I.grid, I.rgba, I.rgba8, nullptr,
                                                            nullptr, nullptr, nullptr, nullptr, S.count_dev, S.stream),
                           "mnv_render_guided_fused_track_ex");
                 hip_check(hipMemcpyAsync(S.count_host, S.count_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream), "read sample counter");
@@ -490,7 +539,7 @@ void VolumeRenderer::render() {
                 ++I.quiet_frames;           // (what refine_after_frame does for a frame without splitting)
             } else {
                 S.counted = false;
-                mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cv, options.c_abi(), full, &I.inputs, I.rgba, I.rgba8, S.stream),
+                mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, S.stream),
                           "mnv_render_voxels_accel_ex");
             }
             stats.used_accel = true;
@@ -514,6 +563,7 @@ void VolumeRenderer::render() {
         return;
     }
     N3Tree &tree = *I.tree;
+    const mnv_frame_inputs in = grid ? I.grid_inputs(I.slots[0], I.stream, cv, options) : I.inputs;
     const int64_t n_px = (int64_t)I.width * I.height;
     const bool refine = I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling);
     if (refine && I.mlp_desc.out_dim != tree.data_dim + 1)
@@ -557,7 +607,7 @@ void VolumeRenderer::render() {
         unsigned long long *counter = I.fused_counter.get<unsigned long long>(1);
         hip_check(hipMemsetAsync(counter, 0, sizeof(unsigned long long), I.stream), "clear sample counter");
         // with refinement on as well (configs[4]) the same kernel also writes the trackers and the visit marks
-        mnv_check(mnv_render_guided_fused_track_ex(tree.device.accel, &cv, options.c_abi(), full, &I.inputs, I.mlp, &I.grid, I.rgba, I.rgba8, split, sample,
+        mnv_check(mnv_render_guided_fused_track_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.mlp, &I.grid, I.rgba, I.rgba8, split, sample,
                                                    split ? tree.device.sample_counts : nullptr, track_visit ? visited : nullptr, tree.device.parent,
                                                    counter, I.stream),
                   "mnv_render_guided_fused_track_ex");
@@ -577,12 +627,12 @@ void VolumeRenderer::render() {
             if (tree.device.accel && !I.accel_stale && (!track_visit || tree.device.parent)) {
                 // visit marks on the packed layout: the march marks leaf chunks, a closure pass adds their ancestors
                 stats.used_accel = true;
-                mnv_check(mnv_get_samples_from_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &I.inputs, split, sample,
+                mnv_check(mnv_get_samples_from_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, split, sample,
                                                                      tree.device.sample_counts, track_visit ? visited : nullptr, tree.device.parent, num, guided,
                                                                      samples_dim, clusters, &I.grid, I.stream),
                           "mnv_get_samples_from_voxels_accel_visit_ex");
             } else {
-                mnv_check(mnv_get_samples_from_voxels_ex(&dv, &cv, options.c_abi(), full, &I.inputs, split, sample, visited, track_visit, num, guided,
+                mnv_check(mnv_get_samples_from_voxels_ex(&dv, &cv, options.c_abi(), full, &in, split, sample, visited, track_visit, num, guided,
                                                          samples_dim, clusters, &I.grid, I.stream),
                           "mnv_get_samples_from_voxels_ex");
             }
@@ -613,11 +663,11 @@ void VolumeRenderer::render() {
                   "mnv_render_nerf_results");
     } else if (tree.device.accel && !I.accel_stale && (!track_visit || tree.device.parent)) {
         stats.used_accel = true;
-        mnv_check(mnv_render_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &I.inputs, I.rgba, I.rgba8, split, sample,
+        mnv_check(mnv_render_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, split, sample,
                                                    tree.device.sample_counts, track_visit ? visited : nullptr, tree.device.parent, I.stream),
                   "mnv_render_voxels_accel_visit_ex");
     } else {
-        mnv_check(mnv_render_voxels_ex(&dv, &cv, options.c_abi(), full, &I.inputs, I.rgba, I.rgba8, split, sample, visited, track_visit, I.stream),
+        mnv_check(mnv_render_voxels_ex(&dv, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, split, sample, visited, track_visit, I.stream),
                   "mnv_render_voxels_ex");
     }
 

@@ -96,6 +96,14 @@ struct VolumeRenderer {
     // ([height][width] float, [height][width][4] uint8; either may be null) that stay valid while frames are rendered; both null (the default) is
     // the offline renderer.  One rank only.
     void set_frame_inputs(const float *tmax_px_device, const uint8_t *rgba8_init_device);
+    // options.show_grid: every frame first draws the octree grid of options.grid_max_depth (the edges of N3Tree::gen_wireframe) with
+    // mnv_render_wireframe into images of its own frame slot, on the slot's stream, and the march then runs with them as its frame inputs
+    // (offscreen == false), whatever the frame kind -- what the reference's window shows with "Show Grid" on.  The edge list is
+    // regenerated when the depth or the tree's structure changed (set, splits, prunes).  Refused (StatusError, MNV_E_INVALID) together with
+    // set_frame_inputs or set_ranks.  wireframe(): the edge list of the last grid frame, null before the first.
+    const mnv_wireframe *wireframe() const;
+    // The camera the last render() used (Camera::_update renormalises v_back on every call: the matrix may move by an ulp between frames).
+    const mnv_camera &last_camera() const;
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
