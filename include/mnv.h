@@ -733,6 +733,63 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
 #define MNV_WIREFRAME_GLOBAL 2
 int mnv_wireframe_set_method(mnv_wireframe *w, int32_t method);
 
+/* ------------------------------------------------ anti-aliased frames: jittered sub-frames in one launch, filtered resolve
+ * Every march kernel sends one ray through each pixel centre.  A supersampled frame is K frames of the SAME camera whose principal point is
+ * shifted by a sub-pixel offset (mnv_camera carries cx, cy per camera, and mnv_render_voxels_accel_batch marches up to MNV_MAX_BATCH cameras
+ * in one launch), filtered into one frame by mnv_resolve_samples.  The reference has no counterpart: it shows point-sampled frames in a window.
+ *
+ * The recipe for callers that drive accel handles themselves (VolumeRenderer / mnv_renderer_set_antialiasing do the same per frame):
+ *     mnv_aa_pattern(K, off);                                                  // 1. pattern
+ *     for (k = 0; k < K; ++k) { cams[k] = cam; cams[k].cx = cam.cx - off[2*k]; cams[k].cy = cam.cy - off[2*k + 1]; }   // 2. shifted cameras
+ *     mnv_render_voxels_accel_batch(accel, cams, K, opt, full, whole, sub, NULL, stream);   // 3. K float sub-frames, one launch
+ *     mnv_aa_weights(MNV_AA_TENT, K, off, &r, w_host, cap, &n); (copy w_host to the device: w_dev)                    // 4. weights
+ *     mnv_resolve_samples(sub, K, width, height, w_dev, r, rgba, rgba8, stream);            // 5. resolve
+ * (sample k looks at the point (x + 0.5 + dx_k, y + 0.5 + dy_k) of pixel (x, y): px = cx + fx * X/z, so moving the principal point by
+ * -d moves the image by -d under the pixel grid.)
+ *
+ * mnv_aa_pattern (host; no GPU needed): n_samples offsets (dx, dy), each in [-0.5, 0.5).  1 <= n_samples <= MNV_MAX_BATCH, else MNV_E_INVALID.
+ * n_samples == 1 gives (0, 0).  Otherwise sample k is (H2(k + 1) - 0.5, H3(k + 1) - 0.5), Hb the radical inverse in base b (a Halton
+ * sequence), computed in double exactly as
+ *     f = 1; r = 0; i = k + 1; while (i > 0) { f = f / b; r = r + f * (i % b); i = i / b; }
+ * then r - 0.5 rounded to float.
+ */
+int mnv_aa_pattern(int32_t n_samples, float *offsets_xy /* host [n_samples][2] */);
+/*
+ * mnv_aa_weights (host; no GPU needed): the reconstruction filter as a table weights[k][j + r][i + r] -- the weight with which sample k
+ * of the pixel at window offset (i, j), i along x, both in -r .. r, enters a pixel.  Not normalised: the resolve divides by the sum it
+ * accumulates.
+ *   MNV_AA_BOX   r = 0, every weight 1.0f: the plain mean of a pixel's own samples
+ *   MNV_AA_TENT  r = 1, max(0, 1 - |i + dx_k|) * max(0, 1 - |j + dy_k|), in double from the float offsets, rounded to float
+ *                (a tent of one pixel radius centred on the pixel centre, evaluated at the sample's position)
+ * Size-query convention of mnv_n3tree_gen_wireframe: *radius_out and *n_floats (= n_samples * (2r + 1)^2) are always set (either may be
+ * NULL); weights NULL with cap_floats 0 asks for them alone; a buffer shorter than n_floats is MNV_E_INVALID.  Unknown filter, n_samples
+ * outside 1 .. MNV_MAX_BATCH or a null offsets array: MNV_E_INVALID.
+ */
+#define MNV_AA_BOX 0
+#define MNV_AA_TENT 1
+int mnv_aa_weights(int32_t filter, int32_t n_samples, const float *offsets_xy, int32_t *radius_out, float *weights /* host */,
+                   int64_t cap_floats, int64_t *n_floats);
+/*
+ * The resolve (a HIP kernel, asynchronous on hip_stream): n_samples sub-frames -> one frame, through a weight table of radius 0 .. 2 (the
+ * tables above, or a caller's own).  sub_rgba and rgba_out are 16-byte aligned device arrays, `weights` is a DEVICE array.
+ * Resolve contract (float32, this order, products and sums rounded separately -- no contraction -- and a correctly rounded division):
+ *   for each pixel (x, y):  acc[0..3] = 0, wsum = 0
+ *     for k = 0 .. n_samples-1, then j = -r .. r, then i = -r .. r:
+ *       skip the term if (x + i, y + j) is outside the frame
+ *       w = weights[k][j + r][i + r]; skip the term if w == 0
+ *       acc[c] = acc[c] + w * sub[k][y + j][x + i][c]   (c = 0 .. 3)      wsum = wsum + w
+ *     out[c] = wsum > 0 ? acc[c] / wsum : 0
+ *   rgba_out[y][x][c] = out[c]; rgba8_out[y][x][c] = the truncating pack of the march's composite (renderer_kernel.cu:237):
+ *   s = out[c] * 255; 0 unless s > 0, 255 if s >= 255, else (uint8)s.  The alpha channel is filtered and packed like the others.
+ * Dividing by the accumulated wsum is what handles the frame's border (the window's terms outside the frame are missing from both sums: the
+ * filter is renormalised over what exists) and tables that are not normalised.
+ * MNV_E_INVALID: null sub_rgba or weights, both outputs null, n_samples outside 1 .. MNV_MAX_BATCH, radius outside 0 .. 2, non-positive
+ * sizes, rgba8_out not 4-byte aligned, sub_rgba / rgba_out not 16-byte aligned.
+ */
+int mnv_resolve_samples(const float *sub_rgba /* device [n_samples][height][width][4] */, int32_t n_samples, int32_t width, int32_t height,
+                        const float *weights /* DEVICE [n_samples][2r+1][2r+1] */, int32_t radius /* 0..2 */,
+                        float *rgba_out /* device [height][width][4] or NULL */, uint8_t *rgba8_out /* or NULL */, void *hip_stream);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -835,6 +892,15 @@ int mnv_renderer_sync_tree(mnv_renderer *r);
 const mnv_wireframe *mnv_renderer_wireframe(const mnv_renderer *r);
 /* the camera (pose matrix and intrinsics) the last mnv_renderer_render used */
 int mnv_renderer_camera(const mnv_renderer *r, mnv_camera *out);
+/* VolumeRenderer::aa_samples / aa_filter (default 1, MNV_AA_TENT).  samples == 1: every frame is what it is without this call, byte for byte.
+ * samples = K > 1: a plain frame (no refinement, packed accel) takes its frame slot as before and, on the slot's stream, marches the K
+ * cameras of mnv_aa_pattern (cx - dx_k, cy - dy_k) with one mnv_render_voxels_accel_batch launch into a per-slot float sub-frame buffer
+ * (K * width * height * 16 bytes, allocated at the first such frame, freed by a resize or another K) and resolves it into the slot's
+ * frame with mnv_resolve_samples; frames in flight keep working.  With options.show_grid the K sub-frames are issued one by one (grid pass
+ * + march per camera: the batch call takes no per-pixel inputs).  An unknown filter is refused here; mnv_renderer_render answers
+ * MNV_E_INVALID while samples > 1 meets caller-set frame inputs, several ranks, a model with use_splitting / use_guided_sampling, a tree
+ * without a packed accel, or samples outside 1 .. MNV_MAX_BATCH (samples = 1 renders again). */
+int mnv_renderer_set_antialiasing(mnv_renderer *r, int32_t samples, int32_t filter);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

@@ -335,6 +335,10 @@ _SIGNATURES = {
     "mnv_renderer_wireframe": (C.c_void_p, [C.c_void_p]),
     "mnv_renderer_camera": (C.c_int, [C.c_void_p, C.POINTER(CameraStruct)]),
     "mnv_wireframe_set_method": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mnv_aa_pattern": (C.c_int, [C.c_int32, C.c_void_p]),
+    "mnv_aa_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "mnv_resolve_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_renderer_set_antialiasing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1168,6 +1172,12 @@ class Renderer:
         _check(lib().mnv_renderer_camera(self._h, C.byref(c)))
         return c
 
+    def set_antialiasing(self, samples: int, filter: int = 1) -> None:
+        """VolumeRenderer::aa_samples / aa_filter (AA_BOX / AA_TENT): samples > 1 renders that many jittered sub-frames per frame in one
+        launch and resolves them on the device; 1 (the default) is the point-sampled frame, unchanged.  What render() refuses with
+        samples > 1 (frame inputs, ranks, refinement, no packed accel, samples > MAX_BATCH) raises there, with MNV_E_INVALID."""
+        _check(lib().mnv_renderer_set_antialiasing(self._h, int(samples), int(filter)))
+
     def wireframe(self) -> int:
         """Raw mnv_wireframe handle of the last show_grid frame (0 before the first); owned by the renderer."""
         return lib().mnv_renderer_wireframe(self._h) or 0
@@ -1254,6 +1264,45 @@ def render_wireframe(wire: int, cam: Camera, opt: RenderOptions, tile=None, tmax
 
 
 MAX_BATCH = 64
+AA_BOX, AA_TENT = 0, 1
+
+
+def aa_pattern(n: int) -> np.ndarray:
+    """mnv_aa_pattern: float32 [n, 2] sub-pixel offsets (dx, dy) in [-0.5, 0.5); n == 1 is (0, 0), else the Halton (2, 3) points k + 1."""
+    out = np.zeros((max(int(n), 0), 2), np.float32)
+    _check(lib().mnv_aa_pattern(int(n), out.ctypes.data))
+    return out
+
+
+def aa_weights(filter: int, offsets) -> np.ndarray:
+    """mnv_aa_weights: the filter table float32 [n, 2r + 1, 2r + 1] (weights[k, j + r, i + r], i along x) of AA_BOX (r = 0) or AA_TENT
+    (r = 1) for the offsets of aa_pattern; the radius is weights.shape[1] // 2."""
+    off = np.ascontiguousarray(offsets, np.float32).reshape(-1, 2)
+    r, n = C.c_int32(0), C.c_int64(0)
+    _check(lib().mnv_aa_weights(int(filter), off.shape[0], off.ctypes.data, C.byref(r), None, 0, C.byref(n)))
+    out = np.empty(n.value, np.float32)
+    _check(lib().mnv_aa_weights(int(filter), off.shape[0], off.ctypes.data, C.byref(r), out.ctypes.data, out.size, C.byref(n)))
+    d = 2 * r.value + 1
+    return out.reshape(off.shape[0], d, d)
+
+
+def resolve_samples(sub, weights, radius: int, rgba=None, rgba8=None, stream: int = 0) -> None:
+    """mnv_resolve_samples (asynchronous on `stream`): sub float32 device tensor [n, h, w, 4], weights float32 device tensor
+    [n, 2r + 1, 2r + 1] (a numpy table is copied to the device first), rgba float32 [h, w, 4] / rgba8 uint8 [h, w, 4] device tensors."""
+    import torch
+
+    if not sub.is_cuda or not sub.is_contiguous() or sub.dtype != torch.float32 or sub.dim() != 4 or sub.shape[3] != 4:
+        raise MnvError(MNV_E_INVALID, "sub must be a contiguous float32 device tensor [n, height, width, 4]")
+    n, h, w = int(sub.shape[0]), int(sub.shape[1]), int(sub.shape[2])
+    if isinstance(weights, np.ndarray):
+        weights = torch.from_numpy(np.ascontiguousarray(weights, np.float32)).to(sub.device)
+    d = 2 * int(radius) + 1
+    if not weights.is_cuda or not weights.is_contiguous() or weights.dtype != torch.float32 or weights.numel() < n * d * d:
+        raise MnvError(MNV_E_INVALID, f"weights must be a contiguous float32 device tensor with at least {n * d * d} elements")
+    _check_out("rgba", rgba, w * h, "f32")
+    _check_out("rgba8", rgba8, w * h, "u8")
+    with _timed(stream):
+        _check(lib().mnv_resolve_samples(sub.data_ptr(), n, w, h, weights.data_ptr(), int(radius), _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
 
 
 def render_voxels_accel_batch(accel: int, cams, opt: RenderOptions, tile=None, part=None, rgba=None, rgba8=None,

@@ -193,6 +193,33 @@ int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size
     return MNV_OK;
 }
 
+/* ---- anti-aliasing: the sample pattern and the filter tables (the recipes are stated in include/mnv.h; the tests restate them) */
+
+int mnv_aa_pattern(int32_t n_samples, float *offsets_xy) {
+    if (n_samples < 1 || n_samples > MNV_MAX_BATCH) return mnv::set_error(MNV_E_INVALID, "mnv_aa_pattern: need 1 .. MNV_MAX_BATCH samples");
+    if (!offsets_xy) return mnv::set_error(MNV_E_INVALID, "mnv_aa_pattern: null output");
+    viewer::aa_pattern(n_samples, offsets_xy);
+    return MNV_OK;
+}
+
+int mnv_aa_weights(int32_t filter, int32_t n_samples, const float *offsets_xy, int32_t *radius_out, float *weights, int64_t cap_floats,
+                   int64_t *n_floats) {
+    if (n_floats) *n_floats = 0;
+    if (radius_out) *radius_out = 0;
+    if (filter != MNV_AA_BOX && filter != MNV_AA_TENT) return mnv::set_error(MNV_E_INVALID, "mnv_aa_weights: unknown filter");
+    if (n_samples < 1 || n_samples > MNV_MAX_BATCH) return mnv::set_error(MNV_E_INVALID, "mnv_aa_weights: need 1 .. MNV_MAX_BATCH samples");
+    if (!offsets_xy) return mnv::set_error(MNV_E_INVALID, "mnv_aa_weights: null offsets");
+    if (cap_floats < 0 || (cap_floats > 0 && !weights)) return mnv::set_error(MNV_E_INVALID, "invalid output buffer");
+    const int r = viewer::aa_filter_radius(filter);
+    const int64_t n = (int64_t)n_samples * (2 * r + 1) * (2 * r + 1);
+    if (radius_out) *radius_out = r;
+    if (n_floats) *n_floats = n;
+    if (!weights && cap_floats == 0) return MNV_OK;
+    if (cap_floats < n) return mnv::set_error(MNV_E_INVALID, "buffer too small (n_floats holds the length)");
+    viewer::aa_weights(filter, n_samples, offsets_xy, weights);
+    return MNV_OK;
+}
+
 int mnv_synth_random_tree(const mnv_synth_random_params *p, mnv_n3tree **out) {
     if (!p || !out) return mnv::set_error(MNV_E_INVALID, "null argument");
     return guarded([&] {
@@ -415,6 +442,14 @@ const mnv_wireframe *mnv_renderer_wireframe(const mnv_renderer *r) { return r ? 
 int mnv_renderer_camera(const mnv_renderer *r, mnv_camera *out) {
     if (!r || !out) return mnv::set_error(MNV_E_INVALID, "null argument");
     *out = r->rend.last_camera();
+    return MNV_OK;
+}
+
+int mnv_renderer_set_antialiasing(mnv_renderer *r, int32_t samples, int32_t filter) {
+    if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
+    if (filter != MNV_AA_BOX && filter != MNV_AA_TENT) return mnv::set_error(MNV_E_INVALID, "anti-aliasing: unknown filter");
+    r->rend.aa_samples = samples;  // (a count render() cannot use is refused there, like the other combinations it refuses)
+    r->rend.aa_filter = filter;
     return MNV_OK;
 }
 

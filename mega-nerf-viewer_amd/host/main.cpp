@@ -29,6 +29,11 @@
 //                    after frames k+1 .. k+K-1 have been issued
 //   --guided_in_flight   guided-sampling frames without splitting rotate over the slots as well (VolumeRenderer::guided_in_flight); their
 //                    sample counts are printed when the frame is written
+//   --aa K           anti-aliased frames (default 1: off): K jittered sub-frames per frame in one launch, resolved on the device
+//                    (VolumeRenderer::aa_samples; 1 .. 64).  --aa_filter box|tent (default tent) names the reconstruction filter: the mean
+//                    of a pixel's own samples, or a tent of one pixel radius over the samples of the 3x3 pixels around it.
+//                    Refused with --gpus: that path gathers RGBA8 tiles, and resolving across ranks would need the float sub-frames
+//                    of every rank on the wire -- out of scope.  Refused (by the renderer) while refining or sampling through a model.
 #include <hip/hip_runtime_api.h>
 
 #include <sys/mman.h>
@@ -109,7 +114,7 @@ void usage() {
     std::puts("usage: mnv_render npz_file [--bg 0.0] [-s step_size] [-e stop_thresh] [-a sigma_thresh] [-c max_tree_capacity]\n"
               "                  [-w width] [-h height] [--fx 1111] [--fy -1] [--cx -1] [--cy -1] [--center x,y,z] [--back x,y,z]\n"
               "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--grid D] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
-              "                  [--in_flight K] [--guided_in_flight] [--gpus N [--reserve_cus R] [--root_period M]]\n"
+              "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--gpus N [--reserve_cus R] [--root_period M]]\n"
               "                  [--model_path MODEL.npz [--use_splitting] [--use_guided_sampling] [-x split_batch_size] [-v samples_per_voxel]\n"
               "                   [-y appearance_embedding] [-z max_guided_samples] [--max_depth D] [--max_sample_count C] [--seed S]\n"
               "                   [--save_tree FILE.npz]]");
@@ -519,6 +524,10 @@ int main(int argc, char **argv) {
             return args.has("help") ? 0 : 2;
         }
         if (args.has("gpus") && args.has("grid")) throw std::runtime_error("--grid draws on one GPU: it cannot be combined with --gpus");
+        const std::string aa_filter = args.get("aa_filter", "tent");
+        if (aa_filter != "box" && aa_filter != "tent") throw std::runtime_error("--aa_filter is box or tent");
+        if (args.has("gpus") && args.l("aa", 1) != 1)
+            throw std::runtime_error("--aa resolves its sub-frames on one GPU: it cannot be combined with --gpus");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 
@@ -554,6 +563,8 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> rgba8;
         rend.frames_in_flight = (int)std::max<long>(1, args.l("in_flight", rend.frames_in_flight));
         rend.guided_in_flight = args.has("guided_in_flight");
+        rend.aa_samples = (int)args.l("aa", 1);
+        rend.aa_filter = aa_filter == "box" ? MNV_AA_BOX : MNV_AA_TENT;
         std::deque<std::pair<long, int>> pending;  // (frame, slot) rendered but not yet written
         auto write_oldest = [&]() {
             const long f = pending.front().first;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -19,7 +20,43 @@ void hip_check(hipError_t e, const char *what) {
 void mnv_check(int rc, const char *what) {
     if (rc != MNV_OK) throw std::runtime_error(std::string(what) + ": " + mnv_last_error());
 }
+double radical_inverse(int i, int b) {  // include/mnv.h, mnv_aa_pattern
+    double f = 1, r = 0;
+    while (i > 0) {
+        f = f / b;
+        r = r + f * (i % b);
+        i = i / b;
+    }
+    return r;
+}
 }  // namespace
+
+void aa_pattern(int n_samples, float *offsets_xy) {
+    if (n_samples == 1) {
+        offsets_xy[0] = offsets_xy[1] = 0.f;
+        return;
+    }
+    for (int k = 0; k < n_samples; ++k) {
+        offsets_xy[2 * k] = (float)(radical_inverse(k + 1, 2) - 0.5);
+        offsets_xy[2 * k + 1] = (float)(radical_inverse(k + 1, 3) - 0.5);
+    }
+}
+
+int aa_filter_radius(int filter) { return filter == MNV_AA_TENT ? 1 : 0; }
+
+void aa_weights(int filter, int n_samples, const float *offsets_xy, float *weights) {
+    if (filter != MNV_AA_TENT) {  // box
+        for (int k = 0; k < n_samples; ++k) weights[k] = 1.f;
+        return;
+    }
+    for (int k = 0; k < n_samples; ++k)
+        for (int j = -1; j <= 1; ++j)
+            for (int i = -1; i <= 1; ++i) {
+                const double wx = std::max(0.0, 1.0 - std::fabs((double)i + (double)offsets_xy[2 * k]));
+                const double wy = std::max(0.0, 1.0 - std::fabs((double)j + (double)offsets_xy[2 * k + 1]));
+                weights[(k * 3 + (j + 1)) * 3 + (i + 1)] = (float)(wx * wy);
+            }
+}
 
 // grow-only device buffer
 struct DeviceBuffer {
@@ -60,6 +97,7 @@ struct VolumeRenderer::Impl {
         bool counted = false;                                             // ... which a frame on this slot has written (or is about to)
         float *grid_tmax = nullptr;                                       // show_grid: this slot's depth image and image under the volume
         uint8_t *grid_rgba8 = nullptr;
+        float *aa_sub = nullptr;  // aa_samples > 1: this slot's K float sub-frames
     };
     std::vector<Slot> slots;
     int cur = 0;            // slot of the most recent render()
@@ -96,6 +134,20 @@ struct VolumeRenderer::Impl {
     mnv_camera last_camera{};  // the camera of the last render()
     int wire_depth = 0;
     uint64_t tree_version = 0, wire_version = 0;
+    // anti-aliasing: what the device weight table (shared by the slots) and the slots' sub-frame buffers were made for
+    int aa_k = 1, aa_filter = -1, aa_radius = 0;
+    float *aa_weights_dev = nullptr;
+    std::vector<float> aa_offsets;
+    void free_aa() {  // (the streams are idle)
+        for (Slot &s : slots) {
+            if (s.aa_sub) (void)hipFree(s.aa_sub);
+            s.aa_sub = nullptr;
+        }
+        if (aa_weights_dev) (void)hipFree(aa_weights_dev);
+        aa_weights_dev = nullptr;
+        aa_k = 1;
+        aa_filter = -1;
+    }
     // the grid pass of this frame into slot S's images on `st`, returned as the frame's inputs (the edge list is current)
     mnv_frame_inputs grid_inputs(Slot &S, hipStream_t st, const mnv_camera &cv, const RenderOptions &o) {
         if (!S.grid_tmax) {
@@ -128,6 +180,7 @@ struct VolumeRenderer::Impl {
     }
     ~Impl() {
         free_frame();
+        if (aa_weights_dev) (void)hipFree(aa_weights_dev);
         if (wire) mnv_wireframe_destroy(wire);
         if (count_host) (void)hipHostFree(count_host);
         if (mlp) mnv_mlp_destroy(mlp);
@@ -148,6 +201,8 @@ struct VolumeRenderer::Impl {
             if (s.rgba8) (void)hipFree(s.rgba8);
             if (s.grid_tmax) (void)hipFree(s.grid_tmax);
             if (s.grid_rgba8) (void)hipFree(s.grid_rgba8);
+            if (s.aa_sub) (void)hipFree(s.aa_sub);
+            s.aa_sub = nullptr;
             s.rgba = nullptr;
             s.rgba8 = nullptr;
             s.grid_tmax = nullptr;
@@ -491,6 +546,20 @@ void VolumeRenderer::render() {
     I.last_camera = cv;
     const mnv_rect full = {0, 0, I.width, I.height};
     stats = FrameStats();
+    if (aa_samples != 1) {  // refused before anything is touched: aa_samples = 1 renders again
+        if (aa_samples < 1 || aa_samples > MNV_MAX_BATCH) throw StatusError(MNV_E_INVALID, "anti-aliasing: aa_samples must be 1 .. MNV_MAX_BATCH");
+        if (aa_filter != MNV_AA_BOX && aa_filter != MNV_AA_TENT) throw StatusError(MNV_E_INVALID, "anti-aliasing: unknown aa_filter");
+        if (I.inputs.tmax_px || I.inputs.rgba8_init)
+            throw StatusError(MNV_E_INVALID, "anti-aliasing jitters the camera: it cannot be combined with set_frame_inputs (images of one fixed camera)");
+        if (I.comm) throw StatusError(MNV_E_INVALID, "anti-aliasing is for one rank: it cannot be combined with set_ranks");
+        if (I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling))
+            throw StatusError(MNV_E_INVALID, "anti-aliasing cannot be combined with use_splitting / use_guided_sampling (refinement votes per ray of one camera)");
+        if (I.tree == nullptr || I.tree->N <= 0 || !I.tree->device.accel)
+            throw StatusError(MNV_E_INVALID, "anti-aliasing needs a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)");
+    } else if (I.aa_k != 1) {  // the buffers of earlier anti-aliased frames go; from here on render() is what it is without the feature
+        I.sync_all();
+        I.free_aa();
+    }
     // show_grid: the grid pass produces this frame's inputs (cuda_renderer.cpp:68-90 draws it before the march)
     const bool grid = options.show_grid && I.tree != nullptr && I.tree->N > 0;
     if (grid) {
@@ -507,6 +576,10 @@ void VolumeRenderer::render() {
             I.wire_version = I.tree_version;
             I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
         }
+    }
+    if (aa_samples != 1) {
+        render_aa(cv, grid);
+        return;
     }
     {
         // a plain frame of a tree with a current accel takes the next slot; everything else runs alone on slot 0
@@ -675,6 +748,75 @@ void VolumeRenderer::render() {
     I.finish_count(stats);
     ++I.frame;
     stats.capacity = tree.capacity;
+}
+
+// render() with aa_samples > 1 (the combinations it cannot serve were refused by render()): K jittered sub-frames on the frame's slot
+// and stream, then the resolve into the slot's frame
+void VolumeRenderer::render_aa(const mnv_camera &cv, bool grid) {
+    Impl &I = *impl_;
+    N3Tree &tree = *I.tree;
+    const int K = aa_samples;
+    if (I.accel_stale) {  // (left behind by refinement frames that were switched off since): every sub-frame runs on the packed layout
+        if (I.overlapped) I.sync_all();
+        tree.rebuild_accel(I.stream);
+        I.accel_stale = false;
+        I.tree_stream_dirty = true;
+    }
+    if (K != I.aa_k || aa_filter != I.aa_filter) {
+        I.sync_all();  // frames in flight read the old table and write the old sub-frame buffers
+        const bool resized = K != I.aa_k;
+        if (resized || !I.aa_weights_dev) {
+            I.free_aa();
+            hip_check(hipMalloc((void **)&I.aa_weights_dev, (size_t)K * 25 * sizeof(float)), "hipMalloc(filter weights)");
+        }
+        I.aa_offsets.resize((size_t)K * 2);
+        aa_pattern(K, I.aa_offsets.data());
+        I.aa_radius = aa_filter_radius(aa_filter);
+        std::vector<float> w((size_t)K * (2 * I.aa_radius + 1) * (2 * I.aa_radius + 1));
+        aa_weights(aa_filter, K, I.aa_offsets.data(), w.data());
+        hip_check(hipMemcpy(I.aa_weights_dev, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice), "upload filter weights");
+        I.aa_k = K;
+        I.aa_filter = aa_filter;
+    }
+    // the slot, as for a plain frame
+    if (overlaps_next()) {
+        if (I.tree_stream_dirty) {
+            hip_check(hipStreamSynchronize(I.stream), "hipStreamSynchronize");
+            I.tree_stream_dirty = false;
+        }
+        I.ensure_slots(frames_in_flight);
+        I.use_slot((I.cur + 1) % frames_in_flight);
+        I.overlapped = true;
+    } else {
+        if (I.overlapped) I.sync_all();
+        I.use_slot(0);
+    }
+    Impl::Slot &S = I.slots[I.cur];
+    S.counted = false;
+    const size_t frame_floats = (size_t)I.width * I.height * 4;
+    if (!S.aa_sub) hip_check(hipMalloc((void **)&S.aa_sub, (size_t)K * frame_floats * sizeof(float)), "hipMalloc(sub-frames)");
+    const mnv_rect full = {0, 0, I.width, I.height};
+    mnv_camera cams[MNV_MAX_BATCH];
+    for (int k = 0; k < K; ++k) {
+        cams[k] = cv;
+        cams[k].cx = cv.cx - I.aa_offsets[2 * k];
+        cams[k].cy = cv.cy - I.aa_offsets[2 * k + 1];
+    }
+    if (grid) {  // the batch call has no per-pixel inputs: grid pass + march per camera, in stream order (the slot's two grid images are reused)
+        for (int k = 0; k < K; ++k) {
+            const mnv_frame_inputs in = I.grid_inputs(S, S.stream, cams[k], options);
+            mnv_check(mnv_render_voxels_accel_ex(tree.device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub + (size_t)k * frame_floats, nullptr, S.stream),
+                      "mnv_render_voxels_accel_ex");
+        }
+    } else {
+        const mnv_partition whole = {0, 1, 0, 0, 0};
+        mnv_check(mnv_render_voxels_accel_batch(tree.device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub, nullptr, S.stream),
+                  "mnv_render_voxels_accel_batch");
+    }
+    mnv_check(mnv_resolve_samples(S.aa_sub, K, I.width, I.height, I.aa_weights_dev, I.aa_radius, I.rgba, I.rgba8, S.stream), "mnv_resolve_samples");
+    stats.used_accel = true;
+    stats.capacity = tree.capacity;
+    ++I.frame;
 }
 
 // render() of one rank of several (set_ranks)

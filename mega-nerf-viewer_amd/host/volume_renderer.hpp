@@ -26,6 +26,12 @@
 
 namespace viewer {
 
+// The sample pattern and the filter tables of anti-aliased frames (host arithmetic; the recipes are stated in include/mnv.h at
+// mnv_aa_pattern / mnv_aa_weights, which check their arguments and call these).
+void aa_pattern(int n_samples, float *offsets_xy);  // [n_samples][2]
+int aa_filter_radius(int filter);
+void aa_weights(int filter, int n_samples, const float *offsets_xy, float *weights);  // [n_samples][2r+1][2r+1]
+
 struct VolumeRenderer {
     explicit VolumeRenderer();
     ~VolumeRenderer();
@@ -105,6 +111,19 @@ struct VolumeRenderer {
     // The camera the last render() used (Camera::_update renormalises v_back on every call: the matrix may move by an ulp between frames).
     const mnv_camera &last_camera() const;
 
+    // Anti-aliased frames (the reference has none: it point-samples into a window).  aa_samples == 1: render() is what it is without these
+    // fields.  aa_samples = K > 1: a plain frame takes its slot as usual (overlaps_next(); slot 0 otherwise) and, on the slot's stream,
+    // marches K cameras equal to the frame's but for cx - dx_k, cy - dy_k (aa_pattern) with ONE mnv_render_voxels_accel_batch launch into a
+    // per-slot sub-frame buffer (float RGBA, K * W * H * 16 bytes: allocated at the first such frame, freed by resize() and when K changes)
+    // and resolves them into the slot's rgba / rgba8 with mnv_resolve_samples through the device weight table of aa_filter (rebuilt when K
+    // or the filter changes).  With options.show_grid the K sub-frames are issued one by one -- mnv_render_wireframe with camera k, then
+    // mnv_render_voxels_accel_ex -- because the batch call takes no per-pixel inputs: slower, and the lines are what gains most.
+    // Refused (StatusError, MNV_E_INVALID) with aa_samples > 1: set_frame_inputs (a depth image of the caller's fixed camera cannot follow
+    // the jitter), set_ranks, a model with use_splitting / use_guided_sampling (refinement votes per ray of ONE camera), a tree without
+    // a packed accel, aa_samples outside 1 .. MNV_MAX_BATCH, an unknown aa_filter.
+    int aa_samples = 1;
+    int aa_filter = MNV_AA_TENT;
+
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
         bool track_visit = false, used_accel = false, full = false;
@@ -130,6 +149,7 @@ struct VolumeRenderer {
 
 private:
     void render_ranks();
+    void render_aa(const mnv_camera &cv, bool grid);
     struct Impl;
     std::unique_ptr<Impl> impl_;
 };
