@@ -733,6 +733,98 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
 #define MNV_WIREFRAME_GLOBAL 2
 int mnv_wireframe_set_method(mnv_wireframe *w, int32_t method);
 
+/* ------------------------------------------------ meshes under the volume (viewer::Mesh, include/mesh.hpp, src/mesh.cpp)
+ * The reference composites its volume with meshes: Mesh::draw writes an RGBA8 image and an R32F image holding length(FragPos), and the march
+ * then reads both with offscreen == false.  mnv_render_meshes is that pass for any list of meshes, without GL: it writes the
+ * mnv_frame_inputs pair of a frame, alone or over the grid pass.
+ *
+ * mnv_mesh: the arrays Mesh::update uploads, copied to the device by mnv_mesh_create (which waits for the copies).
+ *   vert       host float [n_verts][9]: position, colour, normal
+ *   faces      host uint32 [n_indices], face_size per primitive, or NULL with n_indices 0 for non-indexed drawing (glDrawArrays over n_verts)
+ *   face_size  1 points, 2 lines, 3 triangles
+ *   unlit      the fragment shader's switch: the vertex colour alone
+ * MNV_E_INVALID: another face_size, an index >= n_verts, an index count (or, non-indexed, a vertex count) that is no multiple of
+ * face_size, null or empty vertices, indices without a count or a count without indices.  A new mesh is visible and has the identity as
+ * its model matrix.  mnv_mesh_model_matrix takes a row-major 3 x 4 float matrix (mnv_model_matrix makes the reference's);
+ * mnv_mesh_show is Mesh::visible.  Calls that draw a mesh must have finished before it is destroyed.
+ */
+typedef struct mnv_mesh mnv_mesh;
+int mnv_mesh_create(const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit, mnv_mesh **out);
+/* new arrays for an existing handle (same checks; on an error the mesh keeps what it had); the model matrix and visibility stay */
+int mnv_mesh_update(mnv_mesh *m, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit);
+void mnv_mesh_destroy(mnv_mesh *m);
+int mnv_mesh_model_matrix(mnv_mesh *m, const float *matrix3x4);
+int mnv_mesh_show(mnv_mesh *m, int visible);
+int mnv_mesh_visible(const mnv_mesh *m);
+int64_t mnv_mesh_vertex_count(const mnv_mesh *m);
+int64_t mnv_mesh_face_count(const mnv_mesh *m); /* primitives: n_indices / face_size, or n_verts / face_size when non-indexed */
+int32_t mnv_mesh_face_size(const mnv_mesh *m);
+/* The model matrix of Mesh::draw (src/mesh.cpp:137-150) from (rotation axis-angle, translation, scale), on the host (no GPU needed):
+ * identity rotation when |rotation| < 1e-3, else glm::angleAxis(|rotation|, rotation / |rotation|) as a matrix; times scale; the
+ * translation in the fourth column.  Computed in double, rounded to float once.  out: row-major 3 x 4. */
+int mnv_model_matrix(const float rotation[3], const float translation[3], float scale, float *matrix3x4_out);
+/* viewer::Mesh::load_obj (host/mesh.hpp states what is read and how vertices are formed), on the host: the arrays mnv_mesh_create takes.
+ * default_color NULL = white.  Size-query convention of mnv_n3tree_gen_wireframe: *n_floats (9 per vertex), *n_indices (0: non-indexed)
+ * and *face_size are always set; vert / faces NULL with capacity 0 ask for them alone; a buffer that is too short is MNV_E_INVALID.  A
+ * file that cannot be read or is malformed: MNV_E_IO, mnv_last_error names the line ("line N"). */
+int mnv_obj_read(const char *path, const float *default_color, float *vert, int64_t cap_floats, int64_t *n_floats, uint32_t *faces,
+                 int64_t cap_indices, int64_t *n_indices, int32_t *face_size);
+/*
+ * The mesh pass as kernels: writes tile [tile.h][tile.w] of both images (either output may be NULL; rgba8 images 4-byte aligned, else
+ * MNV_E_INVALID).  Invisible meshes are skipped.  under == NULL: the images start cleared (tmax = 1e9f, rgba8 = the background of the
+ * wireframe's step 6).  under != NULL: the pass draws over an earlier pass's images (a NULL member of `under` stands for its clear
+ * value); `under` may name the outputs themselves.  Asynchronous on hip_stream but for one wait (the size of the tile lists); scratch
+ * is kept per HIP stream, calls from several host threads are serialised.
+ *
+ * Raster contract (float32, this order, no contraction, correctly rounded division and square root).  The steps named "wireframe n" are
+ * the steps of mnv_render_wireframe above, word for word.
+ *   A. vertices: world position w_c = ((M[c][0]*x + M[c][1]*y) + M[c][2]*z) + M[c][3] (c = 0..2, M the model matrix; no sin / cos on the
+ *      device); camera coordinates (X, Y, Z) of w by wireframe 1 (Z is its z).  Vertex normal n = t / sqrt((t0*t0 + t1*t1) + t2*t2) with
+ *      t_c = (M[c][0]*a0 + M[c][1]*a1) + M[c][2]*a2 of the normal attribute a (the vertex shader's normalize(mat3(M) * aNormal)).
+ *      Primitive k of a mesh takes vertices faces[k*face_size + i], or k*face_size + i when non-indexed.
+ *   B. lines (face_size 2): wireframe 2-5 on the two camera-space endpoints.  Fragment weights wa = qa/s, wb = qb/s.
+ *   C. points (face_size 1): dropped if Z < 1e-3f; px, py by wireframe 3; one fragment in pixel (floor(px), floor(py)) if that lies in the
+ *      tile (not finite: nothing); its (X, Y, Z) are the vertex's, weight w0 = 1.
+ *   D. triangles (face_size 3), no polygon clipping, no face culling (Mesh::draw enables none): dropped if all three Z < 1e-3f.
+ *      Edge normals: for the vertex pairs (V1,V2), (V2,V0), (V0,V1) in this order, n = A x B = (Ay*Bz - Az*By, Az*Bx - Ax*Bz, Ax*By - Ay*Bx)
+ *      of the camera-space vectors, computed with the pair in canonical order -- the vertex with the smaller X first, then the smaller Y,
+ *      then the smaller Z -- and negated when the triangle names the pair the other way round: two triangles sharing an edge see exactly
+ *      opposite normals.
+ *      Pixels evaluated: if any Z < 1e-3f or any px, py (wireframe 3 per vertex) is not finite, every pixel of the tile; else columns
+ *      floor(min px) - 1 .. floor(max px) + 1 and rows floor(min py) - 1 .. floor(max py) + 1, cut by the tile.
+ *      At pixel (x, y): xc = x + 0.5f, yc = y + 0.5f; u = (xc - cx)/fx, v = (cy - yc)/fy (the ray through the centre is (u, v, 1));
+ *      e_i = (n_i.x*u + n_i.y*v) + n_i.z for the three edges; s = (e0 + e1) + e2.  Covered iff (e0 >= 0, e1 >= 0, e2 >= 0, s > 0) or
+ *      (e0 <= 0, e1 <= 0, e2 <= 0, s < 0): a centre exactly on an edge belongs to both triangles.  Perspective-correct barycentrics
+ *      w_i = e_i / s; X = (w0*X0 + w1*X1) + w2*X2, Y and Z alike; the fragment is discarded unless Z >= 1e-3f (a vertex behind the camera
+ *      needs nothing else: the part of the plane behind the eye gets Z < 0).
+ *   E. depth: dist = sqrt((X*X + Y*Y) + Z*Z) (the shader's Depth = length(FragPos.xyz)); key = bits(Z) << 32 | bits(dist) (wireframe 5);
+ *      the smallest key of a pixel wins; among fragments with that key the lowest draw ordinal (visible meshes in list order, then
+ *      primitives in order) supplies the colour -- GL_LESS keeps the first-drawn fragment.
+ *   F. colour of the winning fragment: attribute = w0*a0, + w1*a1, + w2*a2 in vertex order (as many terms as the primitive has vertices),
+ *      for the colour and, lit, for the normal n of step A (not renormalised, as the shader).  Unlit: rgb = colour.  Lit, the fragment
+ *      shader of src/mesh.cpp:50-72 term for term:
+ *        L1 = (0.4402254521846771f, 0.17609018087387085f, 0.8804509043693542f)       (normalize(0.5, 0.2, 1))
+ *        L2 = (-0.40824830532073975f, -0.8164966106414795f, -0.40824830532073975f)   (normalize(-0.5, -1, -0.5))
+ *        dot(a, b) = (a0*b0 + a1*b1) + a2*b2;  max0(t) = t > 0 ? t : 0
+ *        diffuse = 0.7f * max0(dot(L1, n)); diffuse2 = 0.2f * max0(dot(L2, n))
+ *        view = (C0 - X, C1 - Y, C2 + Z) with C the camera centre in WORLD space and (X, Y, -Z) the shader's FragPos in CAMERA space: the
+ *        reference subtracts the two as they are, and so does this; len = sqrt((view0*view0 + view1*view1) + view2*view2), vd_c = view_c / len
+ *        I = -L1; dn = dot(n, I); r_c = I_c - (2*dn)*n_c                               (reflect(-L1, n))
+ *        sp = max0(dot(vd, r)), squared five times (pow(., 32)); specular = 0.6f * sp
+ *        k = ((0.3f + diffuse) + diffuse2) + specular; rgb = k * colour
+ *      rgba8 = (floor(clamp(c, 0, 1)*255 + 0.5) per channel, 255) (wireframe 6's rule); tmax = dist.
+ *   G. outputs: under == NULL: a pixel without a fragment gets tmax = 1e9f and the background of wireframe 6.  under != NULL: the winning
+ *      fragment replaces the pixel iff dist < under's tmax there; otherwise both values of `under` are copied through.  So tmax is the
+ *      minimum of the two passes, which is what the march needs.
+ * Deliberate deviations from the GL pass: the principal point is the camera's cx, cy (the reference's K ignores them); a triangle is
+ * sampled by the ray through the pixel centre in camera space (2-D homogeneous rasterisation) and lines and points by the rules above, not
+ * by a particular GL driver's; depth is tested on (Z, dist) with first-drawn-wins ties instead of window z with GL_LESS; between passes
+ * the test is on dist.  No pixel parity with a GL driver is claimed.
+ * MNV_E_UNSUPPORTED: 2^32 - 1 or more primitives in one call.
+ */
+int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv_camera *cam, const mnv_render_options *opt, mnv_rect tile,
+                      const mnv_frame_inputs *under, float *tmax_px_out, uint8_t *rgba8_out, void *hip_stream);
+
 /* ------------------------------------------------ anti-aliased frames: jittered sub-frames in one launch, filtered resolve
  * Every march kernel sends one ray through each pixel centre.  A supersampled frame is K frames of the SAME camera whose principal point is
  * shifted by a sub-pixel offset (mnv_camera carries cx, cy per camera, and mnv_render_voxels_accel_batch marches up to MNV_MAX_BATCH cameras
@@ -890,6 +982,15 @@ int mnv_renderer_sync_tree(mnv_renderer *r);
  * the frame as its mnv_frame_inputs (refused together with caller-set frame inputs or several ranks).  The wireframe of the last grid
  * frame (NULL before the first): regenerated when the depth or the tree changed.  Owned by the renderer. */
 const mnv_wireframe *mnv_renderer_wireframe(const mnv_renderer *r);
+/* VolumeRenderer::meshes: while any mesh of the list is visible, render() draws the grid first if options.show_grid is set, then the
+ * list with mnv_render_meshes over it, into the frame slot's depth image and image on the slot's stream, and hands those to the frame as
+ * its mnv_frame_inputs -- for every frame kind the grid works for (tracker and guided frames, frames in flight; with antialiasing the
+ * sub-frames are issued one by one).  Refused by mnv_renderer_render (MNV_E_INVALID), like the grid, together with caller-set frame
+ * inputs or several ranks.  With no visible mesh every frame is what it is without these calls, byte for byte.  The renderer does not
+ * own the handles: a mesh stays the caller's and must outlive its frames (mnv_renderer_clear_meshes waits for the frames in flight). */
+int mnv_renderer_add_mesh(mnv_renderer *r, const mnv_mesh *mesh);
+int mnv_renderer_clear_meshes(mnv_renderer *r);
+int32_t mnv_renderer_mesh_count(const mnv_renderer *r);
 /* the camera (pose matrix and intrinsics) the last mnv_renderer_render used */
 int mnv_renderer_camera(const mnv_renderer *r, mnv_camera *out);
 /* VolumeRenderer::aa_samples / aa_filter (default 1, MNV_AA_TENT).  samples == 1: every frame is what it is without this call, byte for byte.

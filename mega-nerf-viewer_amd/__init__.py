@@ -339,6 +339,23 @@ _SIGNATURES = {
     "mnv_aa_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "mnv_resolve_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mnv_renderer_set_antialiasing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mnv_mesh_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
+    "mnv_mesh_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int]),
+    "mnv_mesh_destroy": (None, [C.c_void_p]),
+    "mnv_mesh_model_matrix": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mnv_mesh_show": (C.c_int, [C.c_void_p, C.c_int]),
+    "mnv_mesh_visible": (C.c_int, [C.c_void_p]),
+    "mnv_mesh_vertex_count": (C.c_int64, [C.c_void_p]),
+    "mnv_mesh_face_count": (C.c_int64, [C.c_void_p]),
+    "mnv_mesh_face_size": (C.c_int32, [C.c_void_p]),
+    "mnv_model_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "mnv_obj_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int32)]),
+    "mnv_render_meshes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(CameraStruct), C.POINTER(RenderOptions), Rect, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "mnv_renderer_add_mesh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mnv_renderer_clear_meshes": (C.c_int, [C.c_void_p]),
+    "mnv_renderer_mesh_count": (C.c_int32, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1178,6 +1195,22 @@ class Renderer:
         samples > 1 (frame inputs, ranks, refinement, no packed accel, samples > MAX_BATCH) raises there, with MNV_E_INVALID."""
         _check(lib().mnv_renderer_set_antialiasing(self._h, int(samples), int(filter)))
 
+    def add_mesh(self, mesh: "Mesh") -> None:
+        """VolumeRenderer::meshes: while a listed mesh is visible every frame draws the list (over the grid, if show_grid is set) with
+        mnv_render_meshes and marches with the two images as its frame inputs.  The Mesh stays the caller's; this object keeps it alive."""
+        _check(lib().mnv_renderer_add_mesh(self._h, mesh._h))
+        if not hasattr(self, "_meshes"):
+            self._meshes = []
+        self._meshes.append(mesh)
+
+    def clear_meshes(self) -> None:
+        _check(lib().mnv_renderer_clear_meshes(self._h))
+        self._meshes = []
+
+    @property
+    def mesh_count(self) -> int:
+        return int(lib().mnv_renderer_mesh_count(self._h))
+
     def wireframe(self) -> int:
         """Raw mnv_wireframe handle of the last show_grid frame (0 before the first); owned by the renderer."""
         return lib().mnv_renderer_wireframe(self._h) or 0
@@ -1260,6 +1293,115 @@ def render_wireframe(wire: int, cam: Camera, opt: RenderOptions, tile=None, tmax
     _check_out("rgba8", rgba8, w * h, "u8")
     _check(lib().mnv_render_wireframe(C.c_void_p(wire), C.byref(cam.c), C.byref(opt), Rect(*tile), tmax_px.data_ptr(), rgba8.data_ptr(),
                                       C.c_void_p(stream)))
+    return tmax_px, rgba8
+
+
+def model_matrix(rotation=(0.0, 0.0, 0.0), translation=(0.0, 0.0, 0.0), scale: float = 1.0) -> np.ndarray:
+    """mnv_model_matrix: the model matrix of the reference's Mesh::draw as float32 [3, 4] (axis-angle rotation, then scale, translation in
+    the last column); host arithmetic, no GPU."""
+    out = np.empty((3, 4), np.float32)
+    _check(lib().mnv_model_matrix(_f3(rotation), _f3(translation), float(scale), out.ctypes.data))
+    return out
+
+
+def obj_read(path: str, color=None):
+    """mnv_obj_read: (vert float32 [n, 9], faces uint32 [m, face_size] or None when non-indexed, face_size) of a Wavefront OBJ file, as
+    viewer::Mesh::load_obj forms them; a malformed file raises MnvError (MNV_E_IO) naming the line."""
+    nf, ni, fs = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    col = _f3(color) if color is not None else None
+    _check(lib().mnv_obj_read(os.fsencode(path), col, None, 0, C.byref(nf), None, 0, C.byref(ni), C.byref(fs)))
+    vert = np.empty(nf.value, np.float32)
+    faces = np.empty(ni.value, np.uint32)
+    _check(lib().mnv_obj_read(os.fsencode(path), col, vert.ctypes.data, vert.size, C.byref(nf), faces.ctypes.data, faces.size, C.byref(ni), C.byref(fs)))
+    return vert.reshape(-1, 9), (faces.reshape(-1, fs.value) if ni.value else None), int(fs.value)
+
+
+class Mesh:
+    """mnv_mesh / viewer::Mesh: vertices float32 [n, 9] (position, colour, normal), optional indices [m, face_size], face_size 1 / 2 / 3
+    (points, lines, triangles), lit or unlit, a model transform (axis-angle rotation, translation, scale) and a visibility flag."""
+
+    def __init__(self, vert, faces=None, face_size: int = 3, unlit: bool = False):
+        v = np.ascontiguousarray(vert, np.float32)
+        if v.ndim != 2 or v.shape[1] != 9:
+            raise MnvError(MNV_E_INVALID, "vert must be [n_verts, 9] (position, colour, normal)")
+        f = None if faces is None else np.ascontiguousarray(faces, np.uint32).reshape(-1)
+        h = C.c_void_p()
+        _check(lib().mnv_mesh_create(v.ctypes.data if v.size else None, v.shape[0], f.ctypes.data if f is not None and f.size else None,
+                                     0 if f is None else f.size, int(face_size), int(bool(unlit)), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_obj(cls, path: str, color=None, unlit: bool = False) -> "Mesh":
+        vert, faces, face_size = obj_read(path, color)
+        return cls(vert, faces, face_size, unlit)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                lib().mnv_mesh_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @property
+    def handle(self) -> int:
+        return self._h.value
+
+    def set_matrix(self, matrix) -> None:
+        """The model matrix itself, float32 [3, 4] row-major (mnv_mesh_model_matrix)."""
+        m = np.ascontiguousarray(matrix, np.float32)
+        if m.shape != (3, 4):
+            raise MnvError(MNV_E_INVALID, "the model matrix is [3, 4]")
+        _check(lib().mnv_mesh_model_matrix(self._h, m.ctypes.data))
+
+    def set_transform(self, rotation=(0.0, 0.0, 0.0), translation=(0.0, 0.0, 0.0), scale: float = 1.0) -> None:
+        """The reference's Mesh::rotation (axis-angle) / translation / scale."""
+        self.set_matrix(model_matrix(rotation, translation, scale))
+
+    @property
+    def visible(self) -> bool:
+        return bool(lib().mnv_mesh_visible(self._h))
+
+    @visible.setter
+    def visible(self, on: bool) -> None:
+        _check(lib().mnv_mesh_show(self._h, int(bool(on))))
+
+    @property
+    def vertex_count(self) -> int:
+        return int(lib().mnv_mesh_vertex_count(self._h))
+
+    @property
+    def face_count(self) -> int:
+        return int(lib().mnv_mesh_face_count(self._h))
+
+    @property
+    def face_size(self) -> int:
+        return int(lib().mnv_mesh_face_size(self._h))
+
+
+def render_meshes(meshes, cam: Camera, opt: RenderOptions, tile=None, under=None, tmax_px=None, rgba8=None, stream: int = 0):
+    """mnv_render_meshes: the mesh pass into (tmax_px float32 [h, w], rgba8 uint8 [h, w, 4]) device tensors (allocated when None); returns
+    both.  under: None (the images start cleared) or a (tmax_px, rgba8) pair of an earlier pass to draw over -- it may be the outputs."""
+    import torch
+
+    if tile is None:
+        tile = (0, 0, cam.width, cam.height)
+    w, h = tile[2], tile[3]
+    if tmax_px is None:
+        tmax_px = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    if rgba8 is None:
+        rgba8 = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
+    if not tmax_px.is_cuda or not tmax_px.is_contiguous() or tmax_px.dtype != torch.float32 or tmax_px.numel() < w * h:
+        raise MnvError(MNV_E_INVALID, f"tmax_px must be a contiguous float32 device tensor with at least {w * h} elements")
+    _check_out("rgba8", rgba8, w * h, "u8")
+    inputs = None
+    if under is not None:
+        inputs = _frame_inputs(under[0], under[1], w * h)
+        if inputs is None:
+            inputs = FrameInputs()
+    handles = (C.c_void_p * max(len(meshes), 1))(*[m._h.value for m in meshes])
+    _check(lib().mnv_render_meshes(handles, len(meshes), C.byref(cam.c), C.byref(opt), Rect(*tile), C.byref(inputs) if inputs is not None else None,
+                                   tmax_px.data_ptr(), rgba8.data_ptr(), C.c_void_p(stream)))
     return tmax_px, rgba8
 
 

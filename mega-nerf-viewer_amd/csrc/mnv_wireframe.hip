@@ -22,15 +22,15 @@
 #include <vector>
 
 #include "mnv_internal.h"
+#include "mnv_raster.h"
 
 using mnv::check_hip;
 using mnv::set_error;
+using namespace mnv_raster;
 
 namespace {
 
 constexpr int kMaxLevel = 30;        // lattice corners are uint32: gridsz = 2^(level+1) <= 2^31
-constexpr float kNear = 1e-3f;       // camera.cpp:104 CLIP_NEAR
-constexpr unsigned long long kEmpty = ~0ull;
 
 // ---------------------------------------------------------------------------------------------------- generation
 
@@ -149,88 +149,18 @@ __global__ void __launch_bounds__(256) wire_segments_kernel(const uint4 *__restr
 
 struct RasterParams {
     WireTransform T;
-    float c2w[12];
-    float fx, fy, cx, cy;
-    int32_t x0, y0, w, h;
+    View V;
 };
 
-// raster contract step 1
-__device__ __forceinline__ void to_camera(const RasterParams &P, const float p[3], float &X, float &Y, float &z) {
-    const float *m = P.c2w;
-    const float d0 = p[0] - m[9], d1 = p[1] - m[10], d2 = p[2] - m[11];
-    X = (m[0] * d0 + m[1] * d1) + m[2] * d2;
-    Y = (m[3] * d0 + m[4] * d1) + m[5] * d2;
-    z = -((m[6] * d0 + m[7] * d1) + m[8] * d2);
-}
-
-// An edge after steps 1-3 of the contract with its fragment range (step 4): columns (x-major) or rows [s0, s1) of the tile whose centres lie in
-// [min, max) of the segment; the other coordinate must fall in [b0, b1).  Both raster methods walk fragments through this one form.
-struct Seg {
-    float pxa, pya, dx, dy, dd, Xa, Ya, za, Xb, Yb, zb;
-    float ua, va, du, dv;  // along the major axis / the other one
-    int s0, s1, b0, b1;
-    bool xm;
-};
-
+// steps 1-4 of the raster contract for edge e (csrc/mnv_raster.h has the steps themselves, shared with the mesh pass)
 __device__ __forceinline__ bool project_edge(const uint4 *__restrict__ cubes, int64_t e, const RasterParams &P, Seg &S) {
     float bb[6], A[3], B[3];
     cube_box(cubes[e / 12], P.T, bb);
     cube_edge(bb, (int)(e % 12), A, B);
     float Xa, Ya, za, Xb, Yb, zb;
-    to_camera(P, A, Xa, Ya, za);
-    to_camera(P, B, Xb, Yb, zb);
-    // step 2: near clip
-    if (za < kNear && zb < kNear) return false;
-    if (za < kNear) {
-        const float t = (kNear - za) / (zb - za);
-        Xa = Xa + t * (Xb - Xa);
-        Ya = Ya + t * (Yb - Ya);
-        za = kNear;
-    } else if (zb < kNear) {
-        const float t = (kNear - zb) / (za - zb);
-        Xb = Xb + t * (Xa - Xb);
-        Yb = Yb + t * (Ya - Yb);
-        zb = kNear;
-    }
-    // step 3: pixel coordinates
-    const float pxa = P.cx + P.fx * (Xa / za), pya = P.cy - P.fy * (Ya / za);
-    const float pxb = P.cx + P.fx * (Xb / zb), pyb = P.cy - P.fy * (Yb / zb);
-    const float dx = pxb - pxa, dy = pyb - pya;
-    const float dd = dx * dx + dy * dy;
-    if (!(dd > 0.f) || !isfinite(dd)) return false;  // zero-length (or unrepresentable) projection: nothing
-    // step 4: one fragment per column (x-major) / row (y-major) whose centre lies in [min, max) of the segment
-    const bool xm = fabsf(dx) >= fabsf(dy);
-    const float ua = xm ? pxa : pya, ub = xm ? pxb : pyb;
-    const int a0 = xm ? P.x0 : P.y0, a1 = a0 + (xm ? P.w : P.h);
-    const float lo = fminf(fmaxf(fminf(ua, ub), (float)(a0 - 1)), (float)(a1 + 1)), hi = fminf(fmaxf(fmaxf(ua, ub), (float)(a0 - 1)), (float)(a1 + 1));
-    S.s0 = max((int)ceilf(lo - 0.5f), a0);
-    S.s1 = min((int)ceilf(hi - 0.5f), a1);
-    if (S.s0 >= S.s1) return false;
-    S.b0 = xm ? P.y0 : P.x0;
-    S.b1 = S.b0 + (xm ? P.h : P.w);
-    S.pxa = pxa, S.pya = pya, S.dx = dx, S.dy = dy, S.dd = dd;
-    S.Xa = Xa, S.Ya = Ya, S.za = za, S.Xb = Xb, S.Yb = Yb, S.zb = zb;
-    S.ua = ua, S.va = xm ? pya : pxa, S.du = xm ? dx : dy, S.dv = xm ? dy : dx;
-    S.xm = xm;
-    return true;
-}
-
-// the floored other coordinate of fragment u (monotone in u: so is every float operation on the way)
-__device__ __forceinline__ float minor_floor(const Seg &S, int u) {
-    const float uc = (float)u + 0.5f;
-    return floorf(S.va + ((uc - S.ua) / S.du) * S.dv);
-}
-
-// step 5: window-space parameter of the pixel centre's orthogonal projection, clamped; perspective-correct camera-space point; the key
-__device__ __forceinline__ unsigned long long fragment_key(const Seg &S, int u, float vf) {
-    const float uc = (float)u + 0.5f, vc = vf + 0.5f;
-    const float xc = S.xm ? uc : vc, yc = S.xm ? vc : uc;
-    float t = ((xc - S.pxa) * S.dx + (yc - S.pya) * S.dy) / S.dd;
-    t = fminf(fmaxf(t, 0.f), 1.f);
-    const float qa = (1.f - t) / S.za, qb = t / S.zb, s = qa + qb;
-    const float X = (qa * S.Xa + qb * S.Xb) / s, Y = (qa * S.Ya + qb * S.Yb) / s, Z = (qa * S.za + qb * S.zb) / s;
-    const float dist = sqrtf((X * X + Y * Y) + Z * Z);
-    return ((unsigned long long)__float_as_uint(Z) << 32) | (unsigned long long)__float_as_uint(dist);
+    to_camera(P.V, A, Xa, Ya, za);
+    to_camera(P.V, B, Xb, Yb, zb);
+    return project_segment(Xa, Ya, za, Xb, Yb, zb, P.V, S);
 }
 
 // ---- MNV_WIREFRAME_GLOBAL: thread per edge, every fragment a 64-bit atomicMin into a key image, then a resolve pass
@@ -246,7 +176,7 @@ __global__ void __launch_bounds__(256) wire_raster_kernel(const uint4 *__restric
         if (!(vf >= (float)S.b0 && vf < (float)S.b1)) continue;
         const int v = (int)vf;
         const int x = S.xm ? u : v, y = S.xm ? v : u;
-        atomicMin(&keys[(int64_t)(y - P.y0) * P.w + (x - P.x0)], fragment_key(S, u, vf));
+        atomicMin(&keys[(int64_t)(y - P.V.y0) * P.V.w + (x - P.V.x0)], fragment_key(S, u, vf));
     }
 }
 
@@ -267,32 +197,10 @@ __global__ void __launch_bounds__(256) wire_resolve_kernel(unsigned long long *_
 // coordinate lies in the tile's span; the tiles of the other axis it reaches come from the floored other coordinate at the span's first and
 // last fragment (monotone along the span, so no fragment is missed).
 
-constexpr int kTile = 32;  // kTile x kTile pixels: 8 KiB of keys in LDS
 // MNV_WIREFRAME_AUTO takes the binned method up to this many edges and the global one beyond.  Measured on cfg2 at 1080p:
 // 63 k edges binned 0.14 ms / global 0.29 ms, 126 M edges binned 97.6 ms / global 4.4 ms (the binned count and fill passes are bound by
 // their 32-bit atomics on a few thousand tile counters); the crossover between the two, interpolated linearly, lies near 200 k edges.
 constexpr int64_t kBinnedMaxEdges = int64_t(1) << 18;
-
-struct TileGrid {
-    int ntx, nty;
-};
-
-// f(tile) for every tile the fragments of S may land in
-template <typename F>
-__device__ __forceinline__ void for_each_tile(const Seg &S, const RasterParams &P, const TileGrid &G, F f) {
-    const int a0 = S.xm ? P.x0 : P.y0;
-    for (int u = S.s0; u < S.s1;) {
-        const int k = (u - a0) / kTile;
-        const int ue = min(S.s1, a0 + (k + 1) * kTile);
-        const float v0 = minor_floor(S, u), v1 = minor_floor(S, ue - 1);
-        const float lo = fminf(v0, v1), hi = fmaxf(v0, v1);
-        if (hi >= (float)S.b0 && lo < (float)S.b1) {
-            const int ilo = lo < (float)S.b0 ? S.b0 : (int)lo, ihi = hi >= (float)S.b1 ? S.b1 - 1 : (int)hi;
-            for (int m = (ilo - S.b0) / kTile; m <= (ihi - S.b0) / kTile; ++m) f(S.xm ? m * G.ntx + k : k * G.ntx + m);
-        }
-        u = ue;
-    }
-}
 
 __global__ void __launch_bounds__(256) wire_bin_count_kernel(const uint4 *__restrict__ cubes, int64_t n_edges, RasterParams P, TileGrid G,
                                                               unsigned *__restrict__ count) {
@@ -300,31 +208,7 @@ __global__ void __launch_bounds__(256) wire_bin_count_kernel(const uint4 *__rest
     if (e >= n_edges) return;
     Seg S;
     if (!project_edge(cubes, e, P, S)) return;
-    for_each_tile(S, P, G, [&](int t) { atomicAdd(&count[t], 1u); });
-}
-
-// exclusive scan of the per-tile counts (one workgroup of 1024 threads); the total -> *total, the fill cursors cleared
-__global__ void __launch_bounds__(1024) wire_bin_scan_kernel(const unsigned *__restrict__ count, int n, unsigned long long *__restrict__ offset,
-                                                             unsigned *__restrict__ cursor, unsigned long long *__restrict__ total) {
-    __shared__ unsigned long long part[1024];
-    const int tid = threadIdx.x, per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    unsigned long long s = 0;
-    for (int i = lo; i < hi; ++i) s += count[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long v = tid >= d ? part[tid - d] : 0ull;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[tid] - s;
-    for (int i = lo; i < hi; ++i) {
-        offset[i] = run;
-        run += count[i];
-        cursor[i] = 0;
-    }
-    if (tid == 1023) *total = part[1023];
+    for_each_tile(S, P.V, G, [&](int t) { atomicAdd(&count[t], 1u); });
 }
 
 __global__ void __launch_bounds__(256) wire_bin_fill_kernel(const uint4 *__restrict__ cubes, int64_t n_edges, RasterParams P, TileGrid G,
@@ -334,7 +218,7 @@ __global__ void __launch_bounds__(256) wire_bin_fill_kernel(const uint4 *__restr
     if (e >= n_edges) return;
     Seg S;
     if (!project_edge(cubes, e, P, S)) return;
-    for_each_tile(S, P, G, [&](int t) { list[offset[t] + atomicAdd(&cursor[t], 1u)] = (uint32_t)e; });
+    for_each_tile(S, P.V, G, [&](int t) { list[offset[t] + atomicAdd(&cursor[t], 1u)] = (uint32_t)e; });
 }
 
 __global__ void __launch_bounds__(256) wire_tile_kernel(const uint4 *__restrict__ cubes, RasterParams P, TileGrid G, unsigned *__restrict__ count,
@@ -342,7 +226,7 @@ __global__ void __launch_bounds__(256) wire_tile_kernel(const uint4 *__restrict_
                                                         uint32_t background_word, float *__restrict__ tmax_out, uint32_t *__restrict__ rgba8_out) {
     __shared__ unsigned long long keys[kTile * kTile];
     const int t = blockIdx.x, tx = t % G.ntx, ty = t / G.ntx;
-    const int gx0 = P.x0 + tx * kTile, gy0 = P.y0 + ty * kTile;  // the tile: pixels [gx0, gx0 + kTile) x [gy0, gy0 + kTile), cut by the frame
+    const int gx0 = P.V.x0 + tx * kTile, gy0 = P.V.y0 + ty * kTile;  // the tile: pixels [gx0, gx0 + kTile) x [gy0, gy0 + kTile), cut by the frame
     for (int i = threadIdx.x; i < kTile * kTile; i += blockDim.x) keys[i] = kEmpty;
     const unsigned n = count[t];
     const unsigned long long base = offset[t];
@@ -363,13 +247,13 @@ __global__ void __launch_bounds__(256) wire_tile_kernel(const uint4 *__restrict_
         }
     }
     __syncthreads();
-    const int wx = min(kTile, P.x0 + P.w - gx0), wy = min(kTile, P.y0 + P.h - gy0);
+    const int wx = min(kTile, P.V.x0 + P.V.w - gx0), wy = min(kTile, P.V.y0 + P.V.h - gy0);
     for (int i = threadIdx.x; i < kTile * kTile; i += blockDim.x) {
         const int lx = i % kTile, ly = i / kTile;
         if (lx >= wx || ly >= wy) continue;
         const unsigned long long k = keys[i];
         const bool hit = k != kEmpty;
-        const int64_t o = (int64_t)(gy0 - P.y0 + ly) * P.w + (gx0 - P.x0 + lx);
+        const int64_t o = (int64_t)(gy0 - P.V.y0 + ly) * P.V.w + (gx0 - P.V.x0 + lx);
         if (tmax_out) tmax_out[o] = hit ? __uint_as_float((uint32_t)k) : 1e9f;
         if (rgba8_out) rgba8_out[o] = hit ? 0xff000000u : background_word;
     }
@@ -554,9 +438,9 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
     }
     RasterParams P{};
     P.T = w->T;
-    std::memcpy(P.c2w, cam->c2w, sizeof(P.c2w));
-    P.fx = cam->fx, P.fy = cam->fy, P.cx = cam->cx, P.cy = cam->cy;
-    P.x0 = tile.x0, P.y0 = tile.y0, P.w = tile.w, P.h = tile.h;
+    std::memcpy(P.V.c2w, cam->c2w, sizeof(P.V.c2w));
+    P.V.fx = cam->fx, P.V.fy = cam->fy, P.V.cx = cam->cx, P.V.cy = cam->cy;
+    P.V.x0 = tile.x0, P.V.y0 = tile.y0, P.V.w = tile.w, P.V.h = tile.h;
     const int64_t n_edges = w->n_cubes * 12;
     // background: floor(clamp(background_brightness, 0, 1) * 255 + 0.5), alpha 255
     const float bb = std::fmin(std::fmax(opt->background_brightness, 0.f), 1.f);
@@ -606,7 +490,7 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
     }
     if (n_edges > 0) {
         hipLaunchKernelGGL(wire_bin_count_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes, n_edges, P, G, S->count);
-        hipLaunchKernelGGL(wire_bin_scan_kernel, dim3(1), dim3(1024), 0, stream, S->count, (int)n_tiles, S->offset, S->cursor, S->total);
+        hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, S->count, (int)n_tiles, S->offset, S->cursor, S->total);
         if ((rc = check_hip(hipGetLastError(), "wire_bin_count / scan")) ||
             (rc = check_hip(hipMemcpyAsync(S->total_host, S->total, 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
             (rc = check_hip(hipStreamSynchronize(stream), "wire_bin_count / scan")))

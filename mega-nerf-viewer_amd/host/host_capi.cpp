@@ -7,6 +7,7 @@
 #include "../../include/mnv.h"
 #include "../csrc/mnv_error.h"
 #include "camera.hpp"
+#include "mesh.hpp"
 #include "n3tree.hpp"
 #include "render_options.hpp"
 #include "volume_renderer.hpp"
@@ -452,5 +453,45 @@ int mnv_renderer_set_antialiasing(mnv_renderer *r, int32_t samples, int32_t filt
     r->rend.aa_filter = filter;
     return MNV_OK;
 }
+
+int mnv_model_matrix(const float rotation[3], const float translation[3], float scale, float *matrix3x4_out) {
+    if (!rotation || !translation || !matrix3x4_out) return mnv::set_error(MNV_E_INVALID, "mnv_model_matrix: null argument");
+    viewer::model_matrix(rotation, translation, scale, matrix3x4_out);
+    return MNV_OK;
+}
+
+int mnv_obj_read(const char *path, const float *default_color, float *vert, int64_t cap_floats, int64_t *n_floats, uint32_t *faces,
+                 int64_t cap_indices, int64_t *n_indices, int32_t *face_size) {
+    if (!path) return mnv::set_error(MNV_E_INVALID, "mnv_obj_read: null path");
+    return guarded([&] {
+        const viewer::Mesh m = viewer::Mesh::load_obj(path, default_color);
+        if (n_floats) *n_floats = (int64_t)m.vert.size();
+        if (n_indices) *n_indices = (int64_t)m.faces.size();
+        if (face_size) *face_size = m.face_size;
+        if (!vert && !faces) return cap_floats == 0 && cap_indices == 0 ? MNV_OK : mnv::set_error(MNV_E_INVALID, "mnv_obj_read: null buffers");
+        if ((!vert && !m.vert.empty()) || cap_floats < (int64_t)m.vert.size() || (!faces && !m.faces.empty()) || cap_indices < (int64_t)m.faces.size())
+            return mnv::set_error(MNV_E_INVALID, "mnv_obj_read: buffer too small (n_floats / n_indices hold the sizes)");
+        if (!m.vert.empty()) std::memcpy(vert, m.vert.data(), m.vert.size() * sizeof(float));
+        if (!m.faces.empty()) std::memcpy(faces, m.faces.data(), m.faces.size() * sizeof(uint32_t));
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_add_mesh(mnv_renderer *r, const mnv_mesh *mesh) {
+    if (!r || !mesh) return mnv::set_error(MNV_E_INVALID, "null argument");
+    r->rend.meshes.push_back(mesh);
+    return MNV_OK;
+}
+
+int mnv_renderer_clear_meshes(mnv_renderer *r) {
+    if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
+    return guarded([&] {
+        r->rend.sync_tree_streams();  // frames in flight draw the listed meshes
+        r->rend.meshes.clear();
+        return MNV_OK;
+    });
+}
+
+int32_t mnv_renderer_mesh_count(const mnv_renderer *r) { return r ? (int32_t)r->rend.meshes.size() : 0; }
 
 }  // extern "C"

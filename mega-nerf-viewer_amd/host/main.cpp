@@ -34,12 +34,16 @@
 //                    of a pixel's own samples, or a tent of one pixel radius over the samples of the 3x3 pixels around it.
 //                    Refused with --gpus: that path gathers RGBA8 tiles, and resolving across ranks would need the float sub-frames
 //                    of every rank on the wire -- out of scope.  Refused (by the renderer) while refining or sampling through a model.
+//   --mesh PATH[,unlit]   draw a Wavefront OBJ file under the volume (viewer::Mesh::load_obj, VolumeRenderer::meshes); repeatable.
+//                    --mesh_color r,g,b (vertices without a colour; default white), --mesh_translate x,y,z, --mesh_rotate x,y,z
+//                    (axis-angle) and --mesh_scale s apply to the mesh named before them.  Refused with --gpus, as --grid is.
 #include <hip/hip_runtime_api.h>
 
 #include <sys/mman.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <csignal>
@@ -54,6 +58,7 @@
 #include <string>
 #include <vector>
 
+#include "mesh.hpp"
 #include "volume_renderer.hpp"
 
 namespace {
@@ -61,6 +66,7 @@ namespace {
 struct Args {
     std::map<std::string, std::string> kv;
     std::string file;
+    std::vector<std::pair<std::string, std::string>> mesh_flags;  // --mesh and the --mesh_* flags after it, in command-line order
     bool has(const std::string &k) const { return kv.count(k) != 0; }
     std::string get(const std::string &k, const std::string &d) const { return has(k) ? kv.at(k) : d; }
     float f(const std::string &k, float d) const { return has(k) ? std::strtof(kv.at(k).c_str(), nullptr) : d; }
@@ -102,6 +108,7 @@ Args parse(int argc, char **argv) {
                 val = argv[++i];
             }
             a.kv[name] = is_flag && !has_val ? "1" : val;
+            if (name.rfind("mesh", 0) == 0) a.mesh_flags.emplace_back(name, val);
         } else {
             a.file = t;
         }
@@ -115,6 +122,7 @@ void usage() {
               "                  [-w width] [-h height] [--fx 1111] [--fy -1] [--cx -1] [--cy -1] [--center x,y,z] [--back x,y,z]\n"
               "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--grid D] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
               "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--gpus N [--reserve_cus R] [--root_period M]]\n"
+              "                  [--mesh FILE.obj[,unlit] [--mesh_color r,g,b] [--mesh_translate x,y,z] [--mesh_rotate x,y,z] [--mesh_scale s]]...\n"
               "                  [--model_path MODEL.npz [--use_splitting] [--use_guided_sampling] [-x split_batch_size] [-v samples_per_voxel]\n"
               "                   [-y appearance_embedding] [-z max_guided_samples] [--max_depth D] [--max_sample_count C] [--seed S]\n"
               "                   [--save_tree FILE.npz]]");
@@ -165,6 +173,64 @@ void configure(const Args &args, viewer::VolumeRenderer &rend, int width, int he
     rend.camera.v_back = {back[0], back[1], back[2]};
     rend.camera.origin = {origin[0], origin[1], origin[2]};
     rend.camera.v_world_up = {up[0], up[1], up[2]};
+}
+
+std::vector<float> floats_of(const std::string &name, const std::string &s, size_t want) {
+    std::vector<float> out;
+    for (size_t i = 0; i <= s.size();) {
+        size_t j = s.find(',', i);
+        if (j == std::string::npos) j = s.size();
+        char *end = nullptr;
+        const std::string t = s.substr(i, j - i);
+        out.push_back(std::strtof(t.c_str(), &end));
+        if (t.empty() || end != t.c_str() + t.size()) throw std::runtime_error("--" + name + ": malformed number '" + t + "'");
+        i = j + 1;
+    }
+    if (out.size() != want) throw std::runtime_error("--" + name + " takes " + std::to_string(want) + " number(s)");
+    return out;
+}
+
+// --mesh PATH[,unlit] and the --mesh_* flags that follow each: loaded, uploaded and listed in `rend`
+void load_meshes(const Args &args, std::vector<viewer::Mesh> &meshes, viewer::VolumeRenderer &rend) {
+    struct Spec {
+        std::string path;
+        bool unlit = false;
+        float color[3] = {1.f, 1.f, 1.f}, translate[3] = {0.f, 0.f, 0.f}, rotate[3] = {0.f, 0.f, 0.f}, scale = 1.f;
+    };
+    std::vector<Spec> specs;
+    for (const auto &kv : args.mesh_flags) {
+        if (kv.first == "mesh") {
+            Spec sp;
+            sp.path = kv.second;
+            const std::string suffix = ",unlit";
+            if (sp.path.size() > suffix.size() && sp.path.compare(sp.path.size() - suffix.size(), suffix.size(), suffix) == 0) {
+                sp.unlit = true;
+                sp.path.resize(sp.path.size() - suffix.size());
+            }
+            specs.push_back(sp);
+            continue;
+        }
+        if (specs.empty()) throw std::runtime_error("--" + kv.first + " applies to the --mesh named before it");
+        Spec &sp = specs.back();
+        if (kv.first == "mesh_scale") {
+            sp.scale = floats_of(kv.first, kv.second, 1)[0];
+        } else {
+            float *dst = kv.first == "mesh_color" ? sp.color : kv.first == "mesh_translate" ? sp.translate : kv.first == "mesh_rotate" ? sp.rotate : nullptr;
+            if (!dst) throw std::runtime_error("unknown flag --" + kv.first);
+            const std::vector<float> v = floats_of(kv.first, kv.second, 3);
+            std::copy(v.begin(), v.end(), dst);
+        }
+    }
+    meshes.reserve(specs.size());
+    for (const Spec &sp : specs) {
+        meshes.push_back(viewer::Mesh::load_obj(sp.path, sp.color, sp.unlit));
+        viewer::Mesh &m = meshes.back();
+        std::copy(sp.translate, sp.translate + 3, m.translation);
+        std::copy(sp.rotate, sp.rotate + 3, m.rotation);
+        m.scale = sp.scale;
+        m.update();
+        rend.meshes.push_back(m.handle());
+    }
 }
 
 // --orbit: rotate the camera about `origin` around world_up by `ang`
@@ -524,6 +590,7 @@ int main(int argc, char **argv) {
             return args.has("help") ? 0 : 2;
         }
         if (args.has("gpus") && args.has("grid")) throw std::runtime_error("--grid draws on one GPU: it cannot be combined with --gpus");
+        if (args.has("gpus") && !args.mesh_flags.empty()) throw std::runtime_error("--mesh draws on one GPU: it cannot be combined with --gpus");
         const std::string aa_filter = args.get("aa_filter", "tent");
         if (aa_filter != "box" && aa_filter != "tent") throw std::runtime_error("--aa_filter is box or tent");
         if (args.has("gpus") && args.l("aa", 1) != 1)
@@ -547,6 +614,8 @@ int main(int argc, char **argv) {
         const long max_capacity = refine ? std::max<long>(tree.capacity, args.l("max_tree_capacity", 20000000)) : tree.capacity;
         if (tree.N > 0) rend.set(tree, max_capacity);
         rend.resize(width, height);
+        std::vector<viewer::Mesh> meshes;
+        load_meshes(args, meshes, rend);
         if (args.has("model_path")) {  // main.cpp:585-589
             rend.load_model(args.get("model_path", ""));
             rend.options.use_splitting = args.has("use_splitting");

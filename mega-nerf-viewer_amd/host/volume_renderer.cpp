@@ -148,14 +148,23 @@ struct VolumeRenderer::Impl {
         aa_k = 1;
         aa_filter = -1;
     }
-    // the grid pass of this frame into slot S's images on `st`, returned as the frame's inputs (the edge list is current)
+    // what draws this frame's inputs (set by render()): the grid, the visible meshes of VolumeRenderer::meshes, or both
+    bool pass_grid = false;
+    std::vector<const mnv_mesh *> pass_meshes;
+    // the grid pass and / or the mesh pass of this frame into slot S's images on `st`, returned as the frame's inputs (the edge list is
+    // current); the meshes are drawn over the grid, in place
     mnv_frame_inputs grid_inputs(Slot &S, hipStream_t st, const mnv_camera &cv, const RenderOptions &o) {
         if (!S.grid_tmax) {
             hip_check(hipMalloc((void **)&S.grid_tmax, (size_t)width * height * sizeof(float)), "hipMalloc(grid depth image)");
             hip_check(hipMalloc((void **)&S.grid_rgba8, (size_t)width * height * 4), "hipMalloc(grid image)");
         }
-        mnv_check(mnv_render_wireframe(wire, &cv, o.c_abi(), {0, 0, width, height}, S.grid_tmax, S.grid_rgba8, st), "mnv_render_wireframe");
-        return {S.grid_tmax, S.grid_rgba8};
+        const mnv_frame_inputs in = {S.grid_tmax, S.grid_rgba8};
+        if (pass_grid) mnv_check(mnv_render_wireframe(wire, &cv, o.c_abi(), {0, 0, width, height}, S.grid_tmax, S.grid_rgba8, st), "mnv_render_wireframe");
+        if (!pass_meshes.empty())
+            mnv_check(mnv_render_meshes(pass_meshes.data(), (int32_t)pass_meshes.size(), &cv, o.c_abi(), {0, 0, width, height}, pass_grid ? &in : nullptr,
+                                        S.grid_tmax, S.grid_rgba8, st),
+                      "mnv_render_meshes");
+        return in;
     }
     // the fused guided kernel's sample count: copied to pinned memory behind the kernel and read at the frame's LAST wait (the vote's,
     // the tree edit's) instead of at a wait of its own right behind the march -- 20-40 us of a refinement frame
@@ -560,12 +569,21 @@ void VolumeRenderer::render() {
         I.sync_all();
         I.free_aa();
     }
-    // show_grid: the grid pass produces this frame's inputs (cuda_renderer.cpp:68-90 draws it before the march)
-    const bool grid = options.show_grid && I.tree != nullptr && I.tree->N > 0;
+    // show_grid / meshes: the grid pass and the mesh pass produce this frame's inputs (cuda_renderer.cpp:68-90 draws them before the march)
+    const bool show_grid = options.show_grid && I.tree != nullptr && I.tree->N > 0;
+    I.pass_meshes.clear();
+    for (const mnv_mesh *m : meshes)
+        if (m && mnv_mesh_visible(m)) I.pass_meshes.push_back(m);
+    const bool grid = show_grid || !I.pass_meshes.empty();  // (from here on: "this frame draws its inputs itself")
+    I.pass_grid = show_grid;
     if (grid) {
+        const char *who = show_grid ? "show_grid" : "a mesh list";
         if (I.inputs.tmax_px || I.inputs.rgba8_init)
-            throw StatusError(MNV_E_INVALID, "show_grid draws the frame inputs itself: it cannot be combined with set_frame_inputs");
-        if (I.comm) throw StatusError(MNV_E_INVALID, "show_grid is for one rank: it cannot be combined with set_ranks");
+            throw StatusError(MNV_E_INVALID, std::string(who) + " draws the frame inputs itself: it cannot be combined with set_frame_inputs");
+        if (I.comm) throw StatusError(MNV_E_INVALID, std::string(who) + " is for one rank: it cannot be combined with set_ranks");
+        if (!I.pass_meshes.empty()) I.can_reuse_results = false;  // (a mesh may have moved: the samples of the last guided frame were limited by it)
+    }
+    if (show_grid) {
         if (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version) {
             I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
             const mnv_tree_view dv = I.tree->device_view();
@@ -631,7 +649,8 @@ void VolumeRenderer::render() {
     }
     if (I.tree == nullptr || I.tree->N <= 0) {
         mnv_tree_view empty = {};  // N == 0: background only (renderer_kernel.cu:266)
-        mnv_check(mnv_render_voxels_ex(&empty, &cv, options.c_abi(), full, &I.inputs, I.rgba, I.rgba8, nullptr, nullptr, nullptr, 0, I.stream),
+        const mnv_frame_inputs in0 = grid ? I.grid_inputs(I.slots[0], I.stream, cv, options) : I.inputs;
+        mnv_check(mnv_render_voxels_ex(&empty, &cv, options.c_abi(), full, &in0, I.rgba, I.rgba8, nullptr, nullptr, nullptr, 0, I.stream),
                   "mnv_render_voxels_ex");
         return;
     }

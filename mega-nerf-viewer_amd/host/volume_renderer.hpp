@@ -108,6 +108,13 @@ struct VolumeRenderer {
     // regenerated when the depth or the tree's structure changed (set, splits, prunes).  Refused (StatusError, MNV_E_INVALID) together with
     // set_frame_inputs or set_ranks.  wireframe(): the edge list of the last grid frame, null before the first.
     const mnv_wireframe *wireframe() const;
+    // Meshes under the volume (the reference's Mesh::draw before the march): device handles of viewer::Mesh::update() / mnv_mesh_create,
+    // not owned.  While any of them is visible, every frame draws the grid first (if options.show_grid), then the visible meshes over it
+    // with mnv_render_meshes, into the frame slot's two images on the slot's stream, and marches with them as its frame inputs -- for every
+    // frame kind the grid works for; with aa_samples > 1 the sub-frames are issued one by one, as with the grid.  Refused like the grid
+    // together with set_frame_inputs or set_ranks.  With no visible mesh render() is what it is without this field.  Wait for the frames
+    // in flight (sync_tree_streams) before a listed mesh is destroyed.
+    std::vector<const mnv_mesh *> meshes;
     // The camera the last render() used (Camera::_update renormalises v_back on every call: the matrix may move by an ulp between frames).
     const mnv_camera &last_camera() const;
 
