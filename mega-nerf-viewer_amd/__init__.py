@@ -383,14 +383,48 @@ def lib() -> C.CDLL:
     return _lib
 
 
+class ProbeCamBlock(C.Structure):
+    """csrc/mnv_device.h CamBlock, field for field (80 bytes)."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("c2w", C.c_float * 12), ("cen", C.c_float * 3),
+                ("pad", C.c_float)]
+
+
+class ProbeFrame(C.Structure):
+    """csrc/mnv_device.h FrameParams, field for field (240 bytes, 16-byte aligned): the by-value argument block of the march kernels, as
+    mnv_hook_probe_setup_ray takes it.  The four pointers at the end are ignored by the probes."""
+    _fields_ = [("cam", ProbeCamBlock), ("x0", C.c_int32), ("y0", C.c_int32), ("tw", C.c_int32), ("th", C.c_int32),
+                ("offset", C.c_float * 3), ("scale", C.c_float * 3),
+                ("step_size", C.c_float), ("sigma_thresh", C.c_float), ("stop_thresh", C.c_float), ("background_brightness", C.c_float),
+                ("render_bbox", C.c_float * 6), ("basis_min", C.c_int32), ("basis_max", C.c_int32), ("render_depth", C.c_int32),
+                ("rot_enabled", C.c_int32), ("rot_k", C.c_float * 3), ("rot_cos", C.c_float), ("rot_sin", C.c_float),
+                ("rgba", C.c_void_p), ("rgba8", C.c_void_p), ("tmax_px", C.c_void_p), ("rgba8_init", C.c_void_p), ("tail_pad", C.c_uint64)]
+
+
+# The element-wise probes of mnv_device.h's device functions (csrc/mnv_probe.hip, test-hook build only): device pointers in, device
+# pointers out, hip_stream last, an MNV_E_* code back.  tests/test_primitives_gpu.py is their caller.
+_PROBE_SIGNATURES = {
+    "mnv_hook_probe_frame_size": (C.c_int, []),
+    "mnv_hook_probe_cam_size": (C.c_int, []),
+    "mnv_hook_probe_expf": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_expf_digest": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_expf_variants_differ": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_half": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_sh": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_setup_ray": (C.c_int, [C.POINTER(ProbeFrame), C.POINTER(ProbeCamBlock), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _hooks_lib: Optional[C.CDLL] = None
 HOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "testhooks", "libmnv.so")
 
 
 def hooks_lib() -> C.CDLL:
     """The test-hook build of the library (testhooks/libmnv.so: the same object code but for the knobs / transport units) as a SECOND binding in
-    this process -- for the one switch the shipped library does not have: mnv_hook_set_ref_table_min_rays, with which the tests run
-    mnv_render_voxels' per-launch lookup table at any frame size.  (When MNV_LIB_PATH already selects the hooks build it is that library.)"""
+    this process -- for what the shipped library does not have: mnv_hook_set_ref_table_min_rays, with which the tests run
+    mnv_render_voxels' per-launch lookup table at any frame size, and the mnv_hook_probe_* entry points (_PROBE_SIGNATURES).  (When
+    MNV_LIB_PATH already selects the hooks build it is that library.)"""
     global _hooks_lib
     if _hooks_lib is None:
         lib()   # torch's HIP runtime first (see lib())
@@ -406,6 +440,12 @@ def hooks_lib() -> C.CDLL:
                 fn.argtypes = args
         h.mnv_hook_set_ref_table_min_rays.restype = None
         h.mnv_hook_set_ref_table_min_rays.argtypes = [C.c_longlong]
+        for name, (res, args) in _PROBE_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
+        if h.mnv_hook_probe_frame_size() != C.sizeof(ProbeFrame) or h.mnv_hook_probe_cam_size() != C.sizeof(ProbeCamBlock):
+            raise RuntimeError("ProbeFrame / ProbeCamBlock no longer mirror csrc/mnv_device.h's FrameParams / CamBlock")
         _hooks_lib = h
     return _hooks_lib
 

@@ -712,11 +712,18 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                             return half_bits_to_float((uint16_t)((k & 1) ? (wd >> 16) : (wd & 0xffffu)));
                         };
                         const float tmp = sh_channel<BASIS>(b, coef, 0);
+                        // (both expressions are copied in mnv_probe.hip: colour_sigmoid_hw / colour_sigmoid_exact; change them together)
                         if constexpr (MODE == 4) {
                             // colour-only arithmetic: it feeds no branch (opacity, transmittance and the step sequence stay exact),
-                            // so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else
-                            const float e = __builtin_amdgcn_exp2f(tmp * -1.44269504088896341f);
-                            v = w * __builtin_amdgcn_rcpf(1.f + e);
+                            // so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else.  Scaled so that
+                            // neither instruction leaves its range: v_rcp_f32 returns 0 for a subnormal result and exp2 overflows
+                            // from 2^128, which lost every term below 2^-126 (t < -87.3).  The reciprocal is taken of (1 + e) * 2^-32,
+                            // beyond x = 96 of (2^-64 + exp2(x - 64)) * 2^-32 (x - 64 is exact there), and the product scaled back
+                            const float x = tmp * -1.44269504088896341f;
+                            const bool big = x > 96.f;
+                            const float e = __builtin_amdgcn_exp2f(big ? x - 64.f : x);
+                            const float den = __builtin_ldexpf((big ? 0x1p-64f : 1.f) + e, -32);
+                            v = __builtin_ldexpf(w * __builtin_amdgcn_rcpf(den), big ? -96 : -32);
                         } else {
                             v = w / (1.f + exact_expf(-tmp, s_exp));
                         }
@@ -780,11 +787,18 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                     auto chan = [&](int c) -> float {
                         auto coef = [&](int k) -> float { return half_bits_to_float((uint16_t)half_at(k)); };
                         const float tmp = sh_channel<BASIS>(b, coef, c * BASIS);
+                        // (both expressions are copied in mnv_probe.hip: colour_sigmoid_hw / colour_sigmoid_exact; change them together)
                         if constexpr (MODE == 4) {
                             // colour-only arithmetic: it feeds no branch (opacity, transmittance and the step sequence stay exact),
-                            // so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else
-                            const float e = __builtin_amdgcn_exp2f(tmp * -1.44269504088896341f);
-                            return weight * __builtin_amdgcn_rcpf(1.f + e);
+                            // so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else.  Scaled so that
+                            // neither instruction leaves its range: v_rcp_f32 returns 0 for a subnormal result and exp2 overflows
+                            // from 2^128, which lost every term below 2^-126 (t < -87.3).  The reciprocal is taken of (1 + e) * 2^-32,
+                            // beyond x = 96 of (2^-64 + exp2(x - 64)) * 2^-32 (x - 64 is exact there), and the product scaled back
+                            const float x = tmp * -1.44269504088896341f;
+                            const bool big = x > 96.f;
+                            const float e = __builtin_amdgcn_exp2f(big ? x - 64.f : x);
+                            const float den = __builtin_ldexpf((big ? 0x1p-64f : 1.f) + e, -32);
+                            return __builtin_ldexpf(weight * __builtin_amdgcn_rcpf(den), big ? -96 : -32);
                         } else {
                             return weight / (1.f + exact_expf(-tmp, s_exp));
                         }
