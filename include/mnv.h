@@ -882,6 +882,57 @@ int mnv_resolve_samples(const float *sub_rgba /* device [n_samples][height][widt
                         const float *weights /* DEVICE [n_samples][2r+1][2r+1] */, int32_t radius /* 0..2 */,
                         float *rgba_out /* device [height][width][4] or NULL */, uint8_t *rgba8_out /* or NULL */, void *hip_stream);
 
+/* ------------------------------------------------ ray lists; orthographic and equirectangular frames
+ * Every march entry point above builds its rays from a pinhole mnv_camera.  mnv_render_rays_accel marches rays the CALLER has -- the lens
+ * model and pixel subset of a data set, an orthographic top-down view of a terrain (with render_depth: a height map), a 360-degree
+ * panorama -- and mnv_generate_rays makes the rays of three projections.  The reference has no counterpart (svox's volume renderer takes
+ * rays; the viewer does not).
+ *
+ * mnv_render_rays_accel: origins / dirs are DEVICE float [height][width][3] in world space; a flat list is height == 1.  Image positions
+ * map to wavefronts through the ray tiles of the camera frames (8 x 8; 64 x 1 for height == 1), so neighbouring rays march together.
+ * Outputs, `inputs` (tmax_px / rgba8_init, NULL or either member NULL as for mnv_render_voxels_accel_ex) are indexed like the rays.
+ * Arithmetic contract, per ray, float32 in this order, no contraction (o, d: the ray's origin and direction; d need not have unit length):
+ *     invnorm = 1.f / sqrtf(d0*d0 + d1*d1 + d2*d2);  dir = d * invnorm;  vdir = dir, rotated by options.rot_dirs as in every frame;
+ *     cen[k] = offset[k] + scale[k] * o[k]   (the tree's offset / scale: what the frame kernels' host code computes for a camera centre);
+ *     from there the set-up, march, composite and pack of mnv_render_voxels_accel_ex (with options.render_depth: of its depth image),
+ *     t_max = tmax_px[ray] or 1e9f.
+ * So the rays mnv_generate_rays(MNV_PROJ_PINHOLE) makes give the frame of mnv_render_voxels_accel_ex bit for bit, and a ray equals the
+ * one-pixel camera (width = height = 1, cx = cy = 0.5, fx = fy = 1, c2w = [1,0,0 | 0,1,0 | -d | o]) of the oracle.
+ * A DEGENERATE ray -- d0*d0 + d1*d1 + d2*d2 zero (or underflowed to zero) or not finite, or a non-finite origin component -- is a miss: its
+ * pixel is what a ray that misses the bounding box gets (the background or the pixel of rgba8_init, alpha 0).
+ * Every row format of the frame kernels (RGBA, SH1/4/9/16/25; anything else: MNV_E_UNSUPPORTED), on inline cell words / brick records where
+ * a camera frame would be.  The ray march ALWAYS uses the exact colour math (mnv_accel_set_colour_math does not reach it), and ray lists are
+ * not offered for trackers, visit marks, sample emission, partitions or batches.
+ * MNV_E_INVALID, before any device call: null origins / dirs / opt / accel, both outputs null, width or height < 1, width * height > 2^28.
+ */
+int mnv_render_rays_accel(const mnv_accel *accel, const float *origins, const float *dirs /* device [height][width][3] */, int32_t width,
+                          int32_t height, const mnv_render_options *opt,
+                          const mnv_frame_inputs *inputs /* NULL, or tmax_px / rgba8_init indexed like the rays */, float *rgba_out,
+                          uint8_t *rgba8_out, void *hip_stream);
+/*
+ * mnv_generate_rays (a HIP kernel, asynchronous on hip_stream): the rays of the rectangle `tile` (inside cam's image) into
+ * origins_out / dirs_out, DEVICE float [tile.h][tile.w][3] (4-byte aligned; 16-byte aligned outputs are written with 16-byte stores).
+ * With m = cam->c2w, pixel (ix, iy), u = (ix + 0.5f - cx) / fx, v = -(iy + 0.5f - cy) / fy; float32, every sum left to right, no contraction:
+ *   MNV_PROJ_PINHOLE   origin = m[9..11];  dir[k] = m[k]*u + m[3+k]*v + m[6+k]*(-1.f), not normalised -- the vector the frame kernels
+ *                      normalise (renderer_kernel.cu:30-38)
+ *   MNV_PROJ_ORTHO     fx, fy are pixels per world unit;  origin[k] = (m[9+k] + m[k]*u) + m[3+k]*v;  dir[k] = m[6+k]*(-1.f).  Rays start ON
+ *                      the camera plane: put it outside the volume
+ *   MNV_PROJ_EQUIRECT  longitude [-pi, pi) left to right, latitude pi/2 .. -pi/2 top to bottom; fx, fy, cx, cy are ignored.  No sine or
+ *                      cosine runs on the device: with (sl, cl) the table's entry of row iy and (so, co) of column ix,
+ *                      dx = cl*so, dy = sl, dz = -(cl*co);  dir[k] = m[k]*dx + m[3+k]*dy + m[6+k]*dz;  origin = m[9..11]
+ * equirect_tables: DEVICE copy of what mnv_equirect_tables(cam->width, cam->height, .) wrote (8-byte aligned); NULL unless EQUIRECT.
+ * mnv_equirect_tables (host; no GPU needed): out[(width + height)][2] = (float)sin, (float)cos -- computed in double -- of
+ * lon = ((x + 0.5) / width - 0.5) * 2 pi for column x = 0 .. width-1, then of lat = (0.5 - (y + 0.5) / height) * pi for row y.
+ * MNV_E_INVALID, before any device call: an unknown projection, null camera / outputs / table (EQUIRECT), a rectangle with w or h < 1,
+ * outside the image or of more than 2^28 pixels, misaligned arrays; mnv_equirect_tables: width or height < 1, null table.
+ */
+#define MNV_PROJ_PINHOLE 0
+#define MNV_PROJ_ORTHO 1
+#define MNV_PROJ_EQUIRECT 2
+int mnv_generate_rays(int32_t projection, const mnv_camera *cam, mnv_rect tile, const float *equirect_tables /* device; NULL unless EQUIRECT */,
+                      float *origins_out, float *dirs_out, void *hip_stream);
+int mnv_equirect_tables(int32_t width, int32_t height, float *out /* host [(width + height)][2] */);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -1002,6 +1053,14 @@ int mnv_renderer_camera(const mnv_renderer *r, mnv_camera *out);
  * MNV_E_INVALID while samples > 1 meets caller-set frame inputs, several ranks, a model with use_splitting / use_guided_sampling, a tree
  * without a packed accel, or samples outside 1 .. MNV_MAX_BATCH (samples = 1 renders again). */
 int mnv_renderer_set_antialiasing(mnv_renderer *r, int32_t samples, int32_t filter);
+/* VolumeRenderer::projection (default MNV_PROJ_PINHOLE: every frame is what it is without this call, byte for byte).  MNV_PROJ_ORTHO /
+ * MNV_PROJ_EQUIRECT: a frame takes its frame slot as a plain frame does (frames in flight keep working) and, on the slot's stream,
+ * generates its rays with mnv_generate_rays from the renderer's camera into per-slot buffers (width * height * 24 bytes, allocated at the
+ * first such frame, freed by a resize) and marches them with mnv_render_rays_accel into the slot's frame; the equirectangular table is
+ * rebuilt when the size changes.  An unknown projection is refused here; mnv_renderer_render answers MNV_E_INVALID while another projection
+ * than the pinhole meets caller-set frame inputs, several ranks, options.show_grid, a visible mesh, antialiasing with more than one sample,
+ * a model with use_splitting / use_guided_sampling, or a tree without a packed accel (MNV_PROJ_PINHOLE renders again). */
+int mnv_renderer_set_projection(mnv_renderer *r, int32_t projection);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

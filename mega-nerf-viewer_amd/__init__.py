@@ -356,6 +356,11 @@ _SIGNATURES = {
     "mnv_renderer_add_mesh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mnv_renderer_clear_meshes": (C.c_int, [C.c_void_p]),
     "mnv_renderer_mesh_count": (C.c_int32, [C.c_void_p]),
+    "mnv_render_rays_accel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RenderOptions), C.POINTER(FrameInputs),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_generate_rays": (C.c_int, [C.c_int32, C.POINTER(CameraStruct), Rect, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_equirect_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "mnv_renderer_set_projection": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1235,6 +1240,13 @@ class Renderer:
         samples > 1 (frame inputs, ranks, refinement, no packed accel, samples > MAX_BATCH) raises there, with MNV_E_INVALID."""
         _check(lib().mnv_renderer_set_antialiasing(self._h, int(samples), int(filter)))
 
+    def set_projection(self, projection: int) -> None:
+        """VolumeRenderer::projection (PROJ_PINHOLE / PROJ_ORTHO / PROJ_EQUIRECT): with another projection than the pinhole a frame generates
+        its rays on the device and marches them as a ray list; PROJ_PINHOLE (the default) is the camera frame, unchanged.  What render()
+        refuses with another projection (frame inputs, ranks, show_grid, a visible mesh, anti-aliasing, refinement, no packed accel)
+        raises there, with MNV_E_INVALID."""
+        _check(lib().mnv_renderer_set_projection(self._h, int(projection)))
+
     def add_mesh(self, mesh: "Mesh") -> None:
         """VolumeRenderer::meshes: while a listed mesh is visible every frame draws the list (over the grid, if show_grid is set) with
         mnv_render_meshes and marches with the two images as its frame inputs.  The Mesh stays the caller's; this object keeps it alive."""
@@ -1485,6 +1497,71 @@ def resolve_samples(sub, weights, radius: int, rgba=None, rgba8=None, stream: in
     _check_out("rgba8", rgba8, w * h, "u8")
     with _timed(stream):
         _check(lib().mnv_resolve_samples(sub.data_ptr(), n, w, h, weights.data_ptr(), int(radius), _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
+
+
+PROJ_PINHOLE, PROJ_ORTHO, PROJ_EQUIRECT = 0, 1, 2
+_equirect_dev = {}   # (width, height, device) -> the device copy of equirect_tables, kept alive for the launches that read it
+
+
+def equirect_tables(width: int, height: int) -> np.ndarray:
+    """mnv_equirect_tables: float32 [width + height, 2] = (sin, cos) of every column's longitude, then of every row's latitude."""
+    out = np.zeros((max(int(width), 0) + max(int(height), 0), 2), np.float32)
+    _check(lib().mnv_equirect_tables(int(width), int(height), out.ctypes.data))
+    return out
+
+
+def _check_rays(name: str, t, shape=None):
+    import torch
+
+    if t is None or not hasattr(t, "is_cuda") or not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or t.dim() not in (2, 3) \
+            or t.shape[-1] != 3 or t.numel() == 0 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = f"{tuple(shape)}" if shape is not None else "[height, width, 3] or [n, 3]"
+        raise MnvError(MNV_E_INVALID, f"{name} must be a contiguous float32 device tensor {want}"
+                                      f" (got {None if t is None else (tuple(t.shape), t.dtype, t.device)})")
+
+
+def generate_rays(projection: int, cam: Camera, tile=None, origins=None, dirs=None, stream: int = 0):
+    """mnv_generate_rays (asynchronous on `stream`): world-space origins and directions, float32 device tensors [tile h, tile w, 3], of the
+    rectangle `tile` of cam's image under PROJ_PINHOLE / PROJ_ORTHO / PROJ_EQUIRECT; origins / dirs are allocated when not given.
+    -> (origins, dirs)"""
+    import torch
+
+    if tile is None:
+        tile = (0, 0, cam.width, cam.height)
+    shape = (tile[3], tile[2], 3)
+    if tile[2] < 1 or tile[3] < 1:
+        raise MnvError(MNV_E_INVALID, "the rectangle needs w >= 1 and h >= 1")
+    if origins is None:
+        origins = torch.empty(shape, dtype=torch.float32, device="cuda")
+    if dirs is None:
+        dirs = torch.empty(shape, dtype=torch.float32, device="cuda")
+    _check_rays("origins", origins, shape)
+    _check_rays("dirs", dirs, shape)
+    tables = None
+    if projection == PROJ_EQUIRECT:
+        key = (cam.width, cam.height, str(origins.device))
+        if key not in _equirect_dev:
+            _equirect_dev[key] = torch.from_numpy(equirect_tables(cam.width, cam.height)).to(origins.device)
+        tables = _equirect_dev[key]
+    with _timed(stream):
+        _check(lib().mnv_generate_rays(int(projection), C.byref(cam.c), Rect(*tile), _ptr(tables), origins.data_ptr(), dirs.data_ptr(),
+                                       C.c_void_p(stream)))
+    return origins, dirs
+
+
+def render_rays_accel(accel: int, origins, dirs, opt: RenderOptions, rgba=None, rgba8=None, tmax=None, rgba8_init=None, stream: int = 0) -> None:
+    """mnv_render_rays_accel (asynchronous on `stream`): the tuned march on the caller's rays.  origins / dirs: float32 device tensors
+    [height, width, 3] (an image of rays) or [n, 3] (a flat list), world space, directions of any length; outputs, tmax (float32, a ray's
+    t_max) and rgba8_init (uint8 RGBA, the pixel under the volume) are indexed like the rays."""
+    _check_rays("origins", origins)
+    _check_rays("dirs", dirs, tuple(origins.shape))
+    height, width = (1, int(origins.shape[0])) if origins.dim() == 2 else (int(origins.shape[0]), int(origins.shape[1]))
+    _check_out("rgba", rgba, width * height, "f32")
+    _check_out("rgba8", rgba8, width * height, "u8")
+    inputs = _frame_inputs(tmax, rgba8_init, width * height)
+    with _timed(stream):
+        _check(lib().mnv_render_rays_accel(C.c_void_p(accel), origins.data_ptr(), dirs.data_ptr(), width, height, C.byref(opt),
+                                           C.byref(inputs) if inputs is not None else None, _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
 
 
 def render_voxels_accel_batch(accel: int, cams, opt: RenderOptions, tile=None, part=None, rgba=None, rgba8=None,

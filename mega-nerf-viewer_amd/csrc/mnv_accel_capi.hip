@@ -68,9 +68,12 @@ int32_t partition_local_tiles(mnv_rect tile, mnv_partition part) {
     return (int32_t)part_local_count(mx * my, part.rank, part.world, root_period_of(part));
 }
 
+// ray_origins / ray_dirs (both or neither; one frame, no partition, no trackers): the rays of the P.tw x P.th image are the caller's
+// (mnv_render_rays_accel) and `cams` only fills the launch slot.
 int launch_accel(const mnv_accel *accel, const FrameParams &P, const CamBlock *cams, int n_frames, mnv_partition part,
-                 const AccelTrack *track, hipStream_t stream) {
+                 const AccelTrack *track, hipStream_t stream, const float *ray_origins = nullptr, const float *ray_dirs = nullptr) {
     if (P.tw <= 0 || P.th <= 0 || n_frames <= 0) return 0;
+    const bool rays = ray_origins != nullptr;
     AccelLaunch K;
     std::memset(static_cast<void *>(&K), 0, sizeof(K));
     K.P = P;
@@ -96,12 +99,13 @@ int launch_accel(const mnv_accel *accel, const FrameParams &P, const CamBlock *c
             }
         }
     }
-    K.fast_colour = accel->colour_math.load(std::memory_order_relaxed) > 0 ? 1 : 0;  // mnv_accel_set_colour_math: the accel's own setting (two renderers of one process may differ)
+    K.fast_colour = !rays && accel->colour_math.load(std::memory_order_relaxed) > 0 ? 1 : 0;  // mnv_accel_set_colour_math: the accel's own setting (two renderers of one process may differ)
     K.part_rank = part.rank;
     K.part_world = is_partitioned(part) ? part.world : 0;
     K.part_period = root_period_of(part);
     static const int env_wlog = knob_int(KNOB_TILE_WLOG, 3);
     K.tile_wlog = (env_wlog >= 0 && env_wlog <= 6) ? (uint32_t)env_wlog : 3u;
+    if (rays) K.tile_wlog = P.th == 1 ? 6u : 3u;  // a flat ray list: 64 x 1 tiles
     if (!is_partitioned(part)) {
         const uint32_t tile_w = 1u << K.tile_wlog, tile_h = 64u >> K.tile_wlog;
         K.tiles_x = (uint32_t)((P.tw + tile_w - 1) / tile_w);
@@ -109,6 +113,9 @@ int launch_accel(const mnv_accel *accel, const FrameParams &P, const CamBlock *c
         K.n_tiles = K.tiles_x * tiles_y;
         // contiguous bands of tile rows per queue
         for (int q = 0; q <= kNumQueues; ++q) K.band_begin[q] = (uint32_t)(((uint64_t)tiles_y * q) / kNumQueues) * K.tiles_x;
+        // ray images with fewer tile rows than queues (a flat list has one) are split by tile count: whole rows would leave queues empty
+        if (rays && tiles_y < (uint32_t)kNumQueues)
+            for (int q = 0; q <= kNumQueues; ++q) K.band_begin[q] = (uint32_t)(((uint64_t)K.n_tiles * q) / kNumQueues);
     } else {
         const mnv_rect rect = {P.x0, P.y0, P.tw, P.th};
         const uint32_t local = (uint32_t)partition_local_tiles(rect, part);
@@ -191,7 +198,7 @@ int launch_accel(const mnv_accel *accel, const FrameParams &P, const CamBlock *c
     static const bool env_stats = knob_set(KNOB_STATS);
     static const char *env_timeline = knob_str(KNOB_TIMELINE);
     static const char *env_footprint = knob_str(KNOB_FOOTPRINT);
-    K.stats = (env_stats || env_ablate || env_timeline || env_footprint) ? accel->stats : nullptr;  // all four run on the diagnostics instantiation
+    K.stats = (env_stats || env_ablate || env_timeline || env_footprint) && !rays ? accel->stats : nullptr;  // all four run on the diagnostics instantiation (camera frames only)
     if (env_footprint && !(track && track->fused)) {
         // one bit per 128-byte line of every array the march loads from; the bits of all launches accumulate until mnv_accel_destroy counts them
         if (!mut->line_bits) {
@@ -235,6 +242,7 @@ int launch_accel(const mnv_accel *accel, const FrameParams &P, const CamBlock *c
     K.refill_min = (env_refill > 0 && n_frames == 1) ? env_refill : 64;  // batches refill whole tiles (a grab must not straddle frames);  // sweep in DESIGN.md: 16 -> 0.606 ms, 32 -> 0.535, 48 -> 0.507, 56 -> 0.504, 64 -> 0.506
     int blocks_per_cu = lds_level >= 5 ? 1 : (lds_level == 4 ? 6 : 8);
     if ((K.split_track || K.sample_track || K.samples || K.visited) && blocks_per_cu > MNV_TRACK_WAVES) blocks_per_cu = MNV_TRACK_WAVES;
+    if (rays && blocks_per_cu > MNV_RAY_WAVES) blocks_per_cu = MNV_RAY_WAVES;
     if (env_bpc > 0) blocks_per_cu = env_bpc;
     int n_blocks = accel->num_cus * blocks_per_cu;
     const uint64_t n_waves_needed = (uint64_t)K.n_tiles * (uint64_t)n_frames;  // one initial 8x8 tile per wave
@@ -259,7 +267,14 @@ int launch_accel(const mnv_accel *accel, const FrameParams &P, const CamBlock *c
         K.timeline_tiles = (uint32_t)tiles;
     }
     int rc = kUnsupportedBasis;
-    if (track && track->fused) {
+    if (rays) {
+        const bool brick = K.A.grid2i && (b < 16 || colourless);  // as for camera frames, below
+        if (!brick) {
+            K.A.grid2i = nullptr;
+            K.A.recs = nullptr;
+        }
+        rc = launch_march_rays(K, ray_origins, ray_dirs, b, colourless, brick, n_blocks, lds_bytes, stream);
+    } else if (track && track->fused) {
         rc = launch_fused(accel, K, *track->fused, b, lds_level, n_waves_needed, stream);
     } else if (K.A.grid2i && (b < 16 || colourless)) {
         // (SH16 / SH25 rows are evaluated by the cooperative pass, which has no brick variant)
@@ -405,6 +420,43 @@ int mnv_render_voxels_accel_ex(const mnv_accel *accel, const mnv_camera *cam, co
                                const mnv_frame_inputs *inputs, float *rgba_out, uint8_t *rgba8_out, void *hip_stream) {
     const mnv_partition whole = {0, 1, 0, 0, 0};
     return render_accel(accel, cam, 1, opt, tile, whole, rgba_out, rgba8_out, nullptr, hip_stream, inputs);
+}
+
+int mnv_render_rays_accel(const mnv_accel *accel, const float *origins, const float *dirs, int32_t width, int32_t height,
+                          const mnv_render_options *opt, const mnv_frame_inputs *inputs, float *rgba_out, uint8_t *rgba8_out, void *hip_stream) {
+    // every argument before any device call
+    if (!origins || !dirs) return set_error(MNV_E_INVALID, "ray origins / directions are null");
+    if (!rgba_out && !rgba8_out) return set_error(MNV_E_INVALID, "both outputs are null");
+    if (width < 1 || height < 1) return set_error(MNV_E_INVALID, "a ray image needs width >= 1 and height >= 1");
+    if ((int64_t)width * (int64_t)height > ((int64_t)1 << 28)) return set_error(MNV_E_INVALID, "more than 2^28 rays in one call");
+    if (!opt) return set_error(MNV_E_INVALID, "options are null");
+    if (!accel) return set_error(MNV_E_INVALID, "accel is null");
+    const int b = (accel->view.format == MNV_FORMAT_SH && accel->view.basis_dim >= 0) ? accel->view.basis_dim : -1;
+    if (!(b == -1 || b == 1 || b == 4 || b == 9 || b == 16 || b == 25))
+        return set_error(MNV_E_UNSUPPORTED, "the ray march serves RGBA and SH1/4/9/16/25 rows");
+    mnv_camera shape = {};  // (fill_params wants an image size; the march reads no camera)
+    shape.width = width;
+    shape.height = height;
+    shape.fx = shape.fy = 1.f;
+    const mnv_rect whole_image = {0, 0, width, height};
+    FrameParams P;
+    std::memset(&P, 0, sizeof(P));
+    int rc = fill_params(P, &shape, opt, whole_image);
+    if (rc) return rc;
+    std::memcpy(P.offset, accel->view.offset, sizeof(P.offset));
+    std::memcpy(P.scale, accel->view.scale, sizeof(P.scale));
+    P.rgba = rgba_out;
+    P.rgba8 = rgba8_out;
+    if (inputs) {
+        P.tmax_px = inputs->tmax_px;
+        P.rgba8_init = inputs->rgba8_init;
+    }
+    CamBlock block;
+    std::memset(&block, 0, sizeof(block));
+    const mnv_partition whole = {0, 1, 0, 0, 0};
+    rc = launch_accel(accel, P, &block, 1, whole, nullptr, (hipStream_t)hip_stream, origins, dirs);
+    if (rc == kUnsupportedBasis) return set_error(MNV_E_UNSUPPORTED, "unsupported basis_dim for the ray march");
+    return check_hip((hipError_t)rc, "march_accel_kernel (rays)");
 }
 
 int mnv_render_voxels_accel_batch(const mnv_accel *accel, const mnv_camera *cams, int32_t n_cams,

@@ -7,6 +7,8 @@
 //   mnv_accel_capi.hip           launch planning (launch_accel), tile assembly, the C-ABI entry points
 #pragma once
 
+#include <type_traits>
+
 #include "mnv_accel.h"
 #include "mnv_internal.h"
 #include "mnv_mlp.h"
@@ -160,6 +162,15 @@ struct AccelLaunch {
     float min_position[3], range[3];
 };
 
+// The launch block of march_accel_kernel<.., RAYS> (mnv_render_rays_accel): + the caller's rays, world space, [P.th][P.tw][3] each.  A
+// block of its own behind the shared one: AccelLaunch is the FIRST argument of the fused guided kernels, so a member added to it would
+// move every offset of their second.
+struct AccelLaunchRays : AccelLaunch {
+    const float *ray_origins, *ray_dirs;
+};
+template <bool RAYS>
+using LaunchBlock = std::conditional_t<RAYS, AccelLaunchRays, AccelLaunch>;
+
 // ray id -> pixel of the rectangle (bx, by) and index of the pixel in the output buffer
 __device__ __forceinline__ bool ray_pixel(const AccelLaunch &K, uint32_t id, int &bx, int &by, uint32_t &pix) {
     const uint32_t tile = id >> 6, w = id & 63u;
@@ -234,6 +245,9 @@ struct FusedGuided {
 #ifndef MNV_TRACK_WAVES
 #define MNV_TRACK_WAVES 6  // tracker / sample modes carry six more live values per ray
 #endif
+#ifndef MNV_RAY_WAVES
+#define MNV_RAY_WAVES 8  // ray-list instantiations: a per-lane origin on top of the plain march's registers (figures in DESIGN.md 5.10)
+#endif
 #ifndef MNV_MIN_WAVES
 #define MNV_MIN_WAVES 8  // register budget for 8 waves per SIMD: the few spills land in the ray set-up (A/B in DESIGN.md)
 #endif
@@ -278,6 +292,10 @@ void launch_build_grid2(const uint32_t *nodes, uint32_t *grid2, uint32_t *grid2_
 int launch_march(const AccelLaunch &K, int basis, bool colourless, int n_blocks, size_t lds_bytes, hipStream_t stream);
 // the same on inline cell words / brick records (K.A.grid2i != NULL), every frame kind of the per-lane row formats (mnv_accel_march_brick.hip)
 int launch_march_brick(const AccelLaunch &K, int basis, bool colourless, int n_blocks, size_t lds_bytes, hipStream_t stream);
+// march_accel_kernel<.., RAYS> on the caller's rays (one frame, no partition): MODE 0, or MODE 5 when colourless; `brick` as launch_accel
+// chooses it (mnv_accel_march_rays.hip); kUnsupportedBasis or a hipError_t
+int launch_march_rays(const AccelLaunch &K, const float *ray_origins, const float *ray_dirs, int basis, bool colourless, bool brick, int n_blocks,
+                      size_t lds_bytes, hipStream_t stream);
 // guided_fused2_kernel / guided_fused_kernel (mnv_accel_fused.hip); kUnsupportedBasis or a hipError_t
 int launch_fused(const mnv_accel *accel, const AccelLaunch &K, const FusedGuided &fused, int basis, int lds_level, uint64_t n_waves_needed,
                  hipStream_t stream);

@@ -313,6 +313,70 @@ __device__ __forceinline__ void setup_ray(const FrameParams &P, const CamBlock &
     }
 }
 
+// setup_ray behind its pixel-to-direction arithmetic, for a ray the caller gives (the ray-list march, march_accel_kernel<.., RAYS>): `dir` is
+// the world-space direction (any length; overwritten), `cen` the tree-space origin offset + scale * origin.  A copy, statement for
+// statement, and not a function setup_ray calls: routing setup_ray through it reorders the instructions of the existing kernels.
+template <int BASIS>
+__device__ __forceinline__ void setup_ray_dir(const FrameParams &P, const float (&cen)[3], float (&dir)[3],
+                                              RaySetup<(BASIS > 0 ? BASIS : 1)> &r, float t_max) {
+    const float invnorm = 1.f / sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+    dir[0] *= invnorm;
+    dir[1] *= invnorm;
+    dir[2] *= invnorm;
+
+    float vdir[3] = {dir[0], dir[1], dir[2]};
+    if (P.rot_enabled) {  // renderer_kernel.cu:52-60
+        const float *k = P.rot_k;
+        float cross[3];
+        cross[0] = k[1] * vdir[2] - k[2] * vdir[1];
+        cross[1] = k[2] * vdir[0] - k[0] * vdir[2];
+        cross[2] = k[0] * vdir[1] - k[1] * vdir[0];
+        const float dot = k[0] * vdir[0] + k[1] * vdir[1] + k[2] * vdir[2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            vdir[i] = (float)((double)(vdir[i] * P.rot_cos + cross[i] * P.rot_sin) +
+                              (double)(k[i] * dot) * (1.0 - (double)P.rot_cos));
+        }
+    }
+
+    // _get_delta_scale, rt_core.cuh:102-115
+    dir[0] *= P.scale[0];
+    dir[1] *= P.scale[1];
+    dir[2] *= P.scale[2];
+    const float delta_scale = 1.f / sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+    dir[0] *= delta_scale;
+    dir[1] *= delta_scale;
+    dir[2] *= delta_scale;
+    r.delta_scale = delta_scale;
+    const float tmax_bg = t_max / delta_scale;  // :183 (t_max: 1e9f offscreen, the pixel's depth otherwise, renderer_kernel.cu:277-280)
+
+    float tmin = 0.0f, tmax = 1e4f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        r.dir[i] = dir[i];
+        r.invdir[i] = (float)(1.0 / ((double)dir[i] + 1e-9));  // :189
+        const double inv = (double)r.invdir[i];
+        const float t1 = (float)(((double)P.render_bbox[i] + 1e-6 - (double)cen[i]) * inv);
+        const float t2 = (float)(((double)P.render_bbox[i + 3] - 1e-6 - (double)cen[i]) * inv);
+        tmin = fmaxf(tmin, fminf(t1, t2));
+        tmax = fminf(tmax, fmaxf(t1, t2));
+    }
+    tmax = fminf(tmax, tmax_bg);
+    r.tmin = tmin;
+    r.tmax = tmax;
+    r.in_bbox = !(tmax < 0 || tmin > tmax);
+
+    constexpr int NB = (BASIS > 0 ? BASIS : 1);
+    if constexpr (BASIS > 0) {
+        sh_basis<BASIS>(vdir, r.basis);
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+            if (i < P.basis_min || i > P.basis_max) r.basis[i] = 0.f;  // :203-209
+    } else {
+        r.basis[0] = 0.f;
+    }
+}
+
 // Colour of one dense sample from a row of binary16 coefficients (rt_core.cuh:257-291).
 // `coef(k)` returns coefficient k of the row as float.  Summation order: DC, then the
 // groups 16-24, 9-15, 4-8, 1-3, each summed left to right before being added.

@@ -46,7 +46,8 @@ constexpr int kShadow = MNV_SHADOW_MASK;
 // lookup grids are plain shifts.  The in-leaf coordinates are fract(pos * 2^depth), which equals the
 // reference's iterated x*2 - floor(x*2) bit for bit (all three operations are exact in binary32).
 template <int BASIS, int BLOCK, int MODE /* 0 plain, 1 statistics, 2 refinement trackers, 3 trackers + emitted samples instead of colour, 4 plain with fast colour math, 5 depth image (render_depth) */,
-          bool BRICK = false /* the levels below the second lookup grid come from inline cell words (A.grid2i) and brick records (A.recs) instead of node loads */>
+          bool BRICK = false /* the levels below the second lookup grid come from inline cell words (A.grid2i) and brick records (A.recs) instead of node loads */,
+          bool RAYS = false /* the rays are the caller's (K.ray_origins / K.ray_dirs, indexed like the pixels) instead of a camera's: MODE 0 and 5 only (mnv_accel_march_rays.hip) */>
 // A/B knobs (tools/build_variant.sh): explicit register budgets on top of the launch bounds
 #if defined(MNV_NUM_VGPR) && defined(MNV_NUM_SGPR)
 #define MNV_EXTRA_KERNEL_ATTR __attribute__((amdgpu_num_vgpr(MNV_NUM_VGPR), amdgpu_num_sgpr(MNV_NUM_SGPR)))
@@ -55,7 +56,7 @@ template <int BASIS, int BLOCK, int MODE /* 0 plain, 1 statistics, 2 refinement 
 #else
 #define MNV_EXTRA_KERNEL_ATTR
 #endif
-__global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES : MNV_MIN_WAVES) MNV_EXTRA_KERNEL_ATTR void march_accel_kernel(const AccelLaunch K) {
+__global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES : RAYS ? MNV_RAY_WAVES : MNV_MIN_WAVES) MNV_EXTRA_KERNEL_ATTR void march_accel_kernel(const LaunchBlock<RAYS> K) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
     uint64_t *s_exp = reinterpret_cast<uint64_t *>(s_mem);  // 32 x 8 B
     constexpr int NB = BASIS > 0 ? BASIS : 1;
@@ -117,7 +118,13 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
     float *wave_ray = s_ray + (threadIdx.x & ~63);  // [k * BLOCK + lane]
 
     const CamBlock *__restrict__ Cp = K.cams;  // camera of the frame this wavefront's rays belong to (wave-uniform pointer: scalar loads)
-    float cen0 = Cp->cen[0], cen1 = Cp->cen[1], cen2 = Cp->cen[2];
+    // (RAYS: the origin is the ray's own -- three more vector registers in those instantiations only)
+    float cen0 = 0.f, cen1 = 0.f, cen2 = 0.f;
+    if constexpr (!RAYS) {
+        cen0 = Cp->cen[0];
+        cen1 = Cp->cen[1];
+        cen2 = Cp->cen[2];
+    }
     // per-lane ray state
     float t = 0.f, T = 1.f, o0 = 0.f, o1 = 0.f, o2 = 0.f;
     float dir0 = 0.f, dir1 = 0.f, dir2 = 0.f, inv0 = 0.f, inv1 = 0.f, inv2 = 0.f, tmax = 0.f;
@@ -372,7 +379,25 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         }
                         if constexpr (MODE == 3) ns = K.num_samples[pix];
                         RaySetup<NB> r;
-                        setup_ray<(BASIS > 0 ? BASIS : 0)>(P, *Cp, P.x0 + bx, P.y0 + by, r, frame_tmax(P, pix));
+                        if constexpr (RAYS) {
+                            // the ray of this image position as the caller gave it (world space, any length); the origin goes to tree
+                            // space with the host's expression for CamBlock::cen (fill_origin)
+                            const float *__restrict__ ro = K.ray_origins + (int64_t)pix * 3, *__restrict__ rd = K.ray_dirs + (int64_t)pix * 3;
+                            const float w0 = ro[0], w1 = ro[1], w2 = ro[2];
+                            float d[3] = {rd[0], rd[1], rd[2]};
+                            const float len2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+                            // a degenerate ray (no direction, or a non-finite direction or origin) is a miss: x - x is 0 for finite x only
+                            const bool valid = len2 > 0.f && len2 < __builtin_inff() && (w0 - w0) + (w1 - w1) + (w2 - w2) == 0.f;
+                            const float p0 = P.scale[0] * w0, p1 = P.scale[1] * w1, p2 = P.scale[2] * w2;
+                            const float cen[3] = {P.offset[0] + p0, P.offset[1] + p1, P.offset[2] + p2};
+                            setup_ray_dir<(BASIS > 0 ? BASIS : 0)>(P, cen, d, r, frame_tmax(P, pix));
+                            r.in_bbox = r.in_bbox && valid;
+                            cen0 = cen[0];
+                            cen1 = cen[1];
+                            cen2 = cen[2];
+                        } else {
+                            setup_ray<(BASIS > 0 ? BASIS : 0)>(P, *Cp, P.x0 + bx, P.y0 + by, r, frame_tmax(P, pix));
+                        }
                         if constexpr (BASIS == 0)
                             r.basis[0] = (0 < P.basis_min || 0 > P.basis_max) ? 0.f : (float)0.28209479177387814;
                         o0 = o1 = o2 = 0.f;

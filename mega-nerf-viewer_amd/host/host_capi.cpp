@@ -454,6 +454,14 @@ int mnv_renderer_set_antialiasing(mnv_renderer *r, int32_t samples, int32_t filt
     return MNV_OK;
 }
 
+int mnv_renderer_set_projection(mnv_renderer *r, int32_t projection) {
+    if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
+    if (projection != MNV_PROJ_PINHOLE && projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT)
+        return mnv::set_error(MNV_E_INVALID, "projection: unknown projection");
+    r->rend.projection = projection;  // (a combination render() cannot serve is refused there)
+    return MNV_OK;
+}
+
 int mnv_model_matrix(const float rotation[3], const float translation[3], float scale, float *matrix3x4_out) {
     if (!rotation || !translation || !matrix3x4_out) return mnv::set_error(MNV_E_INVALID, "mnv_model_matrix: null argument");
     viewer::model_matrix(rotation, translation, scale, matrix3x4_out);

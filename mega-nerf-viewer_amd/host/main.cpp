@@ -34,6 +34,10 @@
 //                    of a pixel's own samples, or a tent of one pixel radius over the samples of the 3x3 pixels around it.
 //                    Refused with --gpus: that path gathers RGBA8 tiles, and resolving across ranks would need the float sub-frames
 //                    of every rank on the wire -- out of scope.  Refused (by the renderer) while refining or sampling through a model.
+//   --projection pinhole|ortho|equirect   (default pinhole) an orthographic frame (--fx / --fy: pixels per world unit; the camera plane
+//                    belongs outside the volume; with --render_depth a height map) or a 360-degree equirectangular panorama from the
+//                    camera's centre (VolumeRenderer::projection: rays from mnv_generate_rays, marched by mnv_render_rays_accel).
+//                    Refused with --gpus, --grid, --mesh and --aa other than 1: those passes draw through a pinhole camera.
 //   --mesh PATH[,unlit]   draw a Wavefront OBJ file under the volume (viewer::Mesh::load_obj, VolumeRenderer::meshes); repeatable.
 //                    --mesh_color r,g,b (vertices without a colour; default white), --mesh_translate x,y,z, --mesh_rotate x,y,z
 //                    (axis-angle) and --mesh_scale s apply to the mesh named before them.  Refused with --gpus, as --grid is.
@@ -121,7 +125,7 @@ void usage() {
     std::puts("usage: mnv_render npz_file [--bg 0.0] [-s step_size] [-e stop_thresh] [-a sigma_thresh] [-c max_tree_capacity]\n"
               "                  [-w width] [-h height] [--fx 1111] [--fy -1] [--cx -1] [--cy -1] [--center x,y,z] [--back x,y,z]\n"
               "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--grid D] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
-              "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--gpus N [--reserve_cus R] [--root_period M]]\n"
+              "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--projection pinhole|ortho|equirect] [--gpus N [--reserve_cus R] [--root_period M]]\n"
               "                  [--mesh FILE.obj[,unlit] [--mesh_color r,g,b] [--mesh_translate x,y,z] [--mesh_rotate x,y,z] [--mesh_scale s]]...\n"
               "                  [--model_path MODEL.npz [--use_splitting] [--use_guided_sampling] [-x split_batch_size] [-v samples_per_voxel]\n"
               "                   [-y appearance_embedding] [-z max_guided_samples] [--max_depth D] [--max_sample_count C] [--seed S]\n"
@@ -595,6 +599,10 @@ int main(int argc, char **argv) {
         if (aa_filter != "box" && aa_filter != "tent") throw std::runtime_error("--aa_filter is box or tent");
         if (args.has("gpus") && args.l("aa", 1) != 1)
             throw std::runtime_error("--aa resolves its sub-frames on one GPU: it cannot be combined with --gpus");
+        const std::string projection = args.get("projection", "pinhole");
+        if (projection != "pinhole" && projection != "ortho" && projection != "equirect") throw std::runtime_error("--projection is pinhole, ortho or equirect");
+        if (projection != "pinhole" && (args.has("gpus") || args.has("grid") || !args.mesh_flags.empty() || args.l("aa", 1) != 1))
+            throw std::runtime_error("--projection " + projection + " marches a ray list: it cannot be combined with --gpus, --grid, --mesh or --aa other than 1");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 
@@ -634,6 +642,7 @@ int main(int argc, char **argv) {
         rend.guided_in_flight = args.has("guided_in_flight");
         rend.aa_samples = (int)args.l("aa", 1);
         rend.aa_filter = aa_filter == "box" ? MNV_AA_BOX : MNV_AA_TENT;
+        rend.projection = projection == "ortho" ? MNV_PROJ_ORTHO : projection == "equirect" ? MNV_PROJ_EQUIRECT : MNV_PROJ_PINHOLE;
         std::deque<std::pair<long, int>> pending;  // (frame, slot) rendered but not yet written
         auto write_oldest = [&]() {
             const long f = pending.front().first;

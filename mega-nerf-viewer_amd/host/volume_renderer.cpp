@@ -98,6 +98,7 @@ struct VolumeRenderer::Impl {
         float *grid_tmax = nullptr;                                       // show_grid: this slot's depth image and image under the volume
         uint8_t *grid_rgba8 = nullptr;
         float *aa_sub = nullptr;  // aa_samples > 1: this slot's K float sub-frames
+        float *ray_origins = nullptr, *ray_dirs = nullptr;  // projection != pinhole: this slot's rays, [height][width][3] each
     };
     std::vector<Slot> slots;
     int cur = 0;            // slot of the most recent render()
@@ -148,6 +149,9 @@ struct VolumeRenderer::Impl {
         aa_k = 1;
         aa_filter = -1;
     }
+    // projection == MNV_PROJ_EQUIRECT: the device table of mnv_equirect_tables (shared by the slots) and the size it was made for
+    float *equirect_dev = nullptr;
+    int equirect_w = 0, equirect_h = 0;
     // what draws this frame's inputs (set by render()): the grid, the visible meshes of VolumeRenderer::meshes, or both
     bool pass_grid = false;
     std::vector<const mnv_mesh *> pass_meshes;
@@ -190,6 +194,7 @@ struct VolumeRenderer::Impl {
     ~Impl() {
         free_frame();
         if (aa_weights_dev) (void)hipFree(aa_weights_dev);
+        if (equirect_dev) (void)hipFree(equirect_dev);
         if (wire) mnv_wireframe_destroy(wire);
         if (count_host) (void)hipHostFree(count_host);
         if (mlp) mnv_mlp_destroy(mlp);
@@ -212,6 +217,9 @@ struct VolumeRenderer::Impl {
             if (s.grid_rgba8) (void)hipFree(s.grid_rgba8);
             if (s.aa_sub) (void)hipFree(s.aa_sub);
             s.aa_sub = nullptr;
+            if (s.ray_origins) (void)hipFree(s.ray_origins);
+            if (s.ray_dirs) (void)hipFree(s.ray_dirs);
+            s.ray_origins = s.ray_dirs = nullptr;
             s.rgba = nullptr;
             s.rgba8 = nullptr;
             s.grid_tmax = nullptr;
@@ -555,6 +563,22 @@ void VolumeRenderer::render() {
     I.last_camera = cv;
     const mnv_rect full = {0, 0, I.width, I.height};
     stats = FrameStats();
+    if (projection != MNV_PROJ_PINHOLE) {  // refused before anything is touched: MNV_PROJ_PINHOLE renders again
+        if (projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT) throw StatusError(MNV_E_INVALID, "projection: unknown projection");
+        if (I.inputs.tmax_px || I.inputs.rgba8_init)
+            throw StatusError(MNV_E_INVALID, "projection: set_frame_inputs holds images of a pinhole camera; it cannot be combined with another projection");
+        if (I.comm) throw StatusError(MNV_E_INVALID, "projection: orthographic / equirectangular frames are for one rank (set_ranks)");
+        if (options.show_grid) throw StatusError(MNV_E_INVALID, "projection: the grid pass draws through a pinhole camera (show_grid)");
+        for (const mnv_mesh *m : meshes)
+            if (m && mnv_mesh_visible(m)) throw StatusError(MNV_E_INVALID, "projection: the mesh pass draws through a pinhole camera (a visible mesh)");
+        if (aa_samples != 1) throw StatusError(MNV_E_INVALID, "projection: anti-aliasing jitters a pinhole camera (aa_samples > 1)");
+        if (I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling))
+            throw StatusError(MNV_E_INVALID, "projection: use_splitting / use_guided_sampling march a pinhole camera's rays");
+        if (I.tree == nullptr || I.tree->N <= 0 || !I.tree->device.accel)
+            throw StatusError(MNV_E_INVALID, "projection: ray lists need a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)");
+        render_projected(cv);
+        return;
+    }
     if (aa_samples != 1) {  // refused before anything is touched: aa_samples = 1 renders again
         if (aa_samples < 1 || aa_samples > MNV_MAX_BATCH) throw StatusError(MNV_E_INVALID, "anti-aliasing: aa_samples must be 1 .. MNV_MAX_BATCH");
         if (aa_filter != MNV_AA_BOX && aa_filter != MNV_AA_TENT) throw StatusError(MNV_E_INVALID, "anti-aliasing: unknown aa_filter");
@@ -833,6 +857,58 @@ void VolumeRenderer::render_aa(const mnv_camera &cv, bool grid) {
                   "mnv_render_voxels_accel_batch");
     }
     mnv_check(mnv_resolve_samples(S.aa_sub, K, I.width, I.height, I.aa_weights_dev, I.aa_radius, I.rgba, I.rgba8, S.stream), "mnv_resolve_samples");
+    stats.used_accel = true;
+    stats.capacity = tree.capacity;
+    ++I.frame;
+}
+
+// render() with an orthographic or equirectangular projection (the combinations it cannot serve were refused by render()): the frame's
+// rays on the frame's slot and stream, then the ray march into the slot's frame
+void VolumeRenderer::render_projected(const mnv_camera &cv) {
+    Impl &I = *impl_;
+    N3Tree &tree = *I.tree;
+    if (I.accel_stale) {  // (left behind by refinement frames that were switched off since)
+        if (I.overlapped) I.sync_all();
+        tree.rebuild_accel(I.stream);
+        I.accel_stale = false;
+        I.tree_stream_dirty = true;
+    }
+    if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
+        I.sync_all();  // frames in flight read the old table
+        if (I.equirect_dev) (void)hipFree(I.equirect_dev);
+        I.equirect_dev = nullptr;
+        std::vector<float> table(((size_t)I.width + I.height) * 2);
+        mnv_check(mnv_equirect_tables(I.width, I.height, table.data()), "mnv_equirect_tables");
+        hip_check(hipMalloc((void **)&I.equirect_dev, table.size() * sizeof(float)), "hipMalloc(equirectangular table)");
+        hip_check(hipMemcpy(I.equirect_dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice), "upload equirectangular table");
+        I.equirect_w = I.width;
+        I.equirect_h = I.height;
+    }
+    // the slot, as for a plain frame
+    if (overlaps_next()) {
+        if (I.tree_stream_dirty) {
+            hip_check(hipStreamSynchronize(I.stream), "hipStreamSynchronize");
+            I.tree_stream_dirty = false;
+        }
+        I.ensure_slots(frames_in_flight);
+        I.use_slot((I.cur + 1) % frames_in_flight);
+        I.overlapped = true;
+    } else {
+        if (I.overlapped) I.sync_all();
+        I.use_slot(0);
+    }
+    Impl::Slot &S = I.slots[I.cur];
+    S.counted = false;
+    const size_t ray_bytes = (size_t)I.width * I.height * 3 * sizeof(float);
+    if (!S.ray_origins) {
+        hip_check(hipMalloc((void **)&S.ray_origins, ray_bytes), "hipMalloc(ray origins)");
+        hip_check(hipMalloc((void **)&S.ray_dirs, ray_bytes), "hipMalloc(ray directions)");
+    }
+    const mnv_rect full = {0, 0, I.width, I.height};
+    mnv_check(mnv_generate_rays(projection, &cv, full, projection == MNV_PROJ_EQUIRECT ? I.equirect_dev : nullptr, S.ray_origins, S.ray_dirs, S.stream),
+              "mnv_generate_rays");
+    mnv_check(mnv_render_rays_accel(tree.device.accel, S.ray_origins, S.ray_dirs, I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
+              "mnv_render_rays_accel");
     stats.used_accel = true;
     stats.capacity = tree.capacity;
     ++I.frame;

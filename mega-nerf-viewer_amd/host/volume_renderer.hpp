@@ -130,6 +130,15 @@ struct VolumeRenderer {
     // a packed accel, aa_samples outside 1 .. MNV_MAX_BATCH, an unknown aa_filter.
     int aa_samples = 1;
     int aa_filter = MNV_AA_TENT;
+    // Other projections than the pinhole camera (the reference has none).  MNV_PROJ_PINHOLE: render() is what it is without this field.
+    // MNV_PROJ_ORTHO (camera.fx / fy: pixels per world unit; put the camera plane outside the volume) / MNV_PROJ_EQUIRECT (a panorama from
+    // camera.center): the frame takes its slot as a plain frame does and, on the slot's stream, generates its rays with mnv_generate_rays
+    // into per-slot buffers (width * height * 24 bytes, allocated at the first such frame, freed by resize()) and marches them with
+    // mnv_render_rays_accel into the slot's rgba / rgba8; the equirectangular table is rebuilt when the size changes.  With
+    // options.render_depth an orthographic frame from above is a height map.
+    // Refused (StatusError, MNV_E_INVALID) with another projection than the pinhole: set_frame_inputs, set_ranks, options.show_grid, a
+    // visible mesh, aa_samples > 1, a model with use_splitting / use_guided_sampling, a tree without a packed accel, an unknown projection.
+    int projection = MNV_PROJ_PINHOLE;
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
@@ -157,6 +166,7 @@ struct VolumeRenderer {
 private:
     void render_ranks();
     void render_aa(const mnv_camera &cv, bool grid);
+    void render_projected(const mnv_camera &cv);
     struct Impl;
     std::unique_ptr<Impl> impl_;
 };
