@@ -933,6 +933,69 @@ int mnv_generate_rays(int32_t projection, const mnv_camera *cam, mnv_rect tile, 
                       float *origins_out, float *dirs_out, void *hip_stream);
 int mnv_equirect_tables(int32_t width, int32_t height, float *out /* host [(width + height)][2] */);
 
+/* ------------------------------------------------ frame metrics: squared error (PSNR) and SSIM against a target image, on the device
+ * What a user of a batch renderer does with a frame is score it -- against a photograph of the data set, the frame of the unrefined tree,
+ * the frame of another build.  mnv_frame_metrics compares a float frame (what every launcher writes) with an RGBA8 target on the device and
+ * leaves 40 bytes of integer sums; the frame itself never crosses the bus.  The reference has no counterpart.
+ *
+ * Metric contract (float32, this order, products and sums rounded separately -- no contraction -- and a correctly rounded division):
+ *   per pixel and channel c = 0 .. 2, v = rgba[y][x][c]:
+ *     t = (float)target8[y][x][c] / 255.f
+ *     x = v > 0 ? (v < 1 ? v : 1) : 0                              (a NaN becomes 0)
+ *     MNV_METRIC_QUANTISED: x = (float)pack(v) / 255.f, pack the truncating pack stated at mnv_resolve_samples (s = v * 255; 0 unless
+ *       s > 0, 255 if s >= 255, else (uint8)s) -- the file `mnv_render --out` writes against the file that was read
+ *   a pixel is INCLUDED unless MNV_METRIC_MASK_ALPHA is set and target8[y][x][3] == 0
+ *   squared error:  e_c = x_c - t_c;  se = (e0*e0 + e1*e1) + e2*e2
+ *   SSIM (MNV_METRIC_SSIM; Wang et al.: 11 x 11 Gaussian window, valid windows only, data range 1), per channel, for every window origin
+ *   (x', y') with x' <= width - 11 and y' <= height - 11.  Each of the five maps v = x, t, x*x, t*t, x*t is filtered the same way,
+ *     along x:  h = 0;  for i = 0 .. 10:  h = h + g[i] * v[y][x' + i]
+ *     along y:  m = 0;  for j = 0 .. 10:  m = m + g[j] * h[y' + j][x']
+ *   giving mx, my, exx, eyy, exy; then
+ *     mxx = mx*mx;  myy = my*my;  mxy = mx*my;  sxx = exx - mxx;  syy = eyy - myy;  sxy = exy - mxy
+ *     num = (2.f*mxy + C1) * (2.f*sxy + C2);  den = ((mxx + myy) + C1) * ((sxx + syy) + C2);  s = num / den      C1 = 1e-4f, C2 = 9e-4f
+ *   a window is included iff all of its 121 pixels are included (counted with integers).
+ *   `window`: HOST float [11], copied into the kernel's arguments; NULL = the standard window of mnv_ssim_window.
+ * Sums (mnv_metric_sums, five int64 in DEVICE memory, zeroed by the call on its stream before the kernel):
+ *     n_px      included pixels                      se_q32    sum over included pixels of llrint((double)se * 2^32)
+ *     n_win     included windows                     ssim_q32  sum over included windows and the 3 channels of llrint((double)s * 2^32)
+ *   Every term is rounded once, to nearest even, at 2^-32; from there on every addition is an integer addition, so the words do not depend
+ *   on tile shape, lane mapping, reduction tree or atomic order, and a numpy restatement reproduces them exactly (tests/metrics_ref.py).
+ *   Headroom: 3 * 2^32 * 2^28 < 2^62, so width * height > 2^28 is refused.
+ * Optional maps (either NULL): se_map_out float [height][width], 0 where the pixel is excluded; ssim_map_out float
+ * [height - 10][width - 10][3], 0 where the window is excluded.
+ * MNV_METRIC_SSIM on a frame narrower or lower than 11 is no error: n_win = 0 (and ssim_map_out is not touched).
+ * MNV_E_INVALID, before any device call: null rgba / target8 / sums, non-positive sizes, width * height > 2^28, rgba not 16-byte aligned,
+ * target8 or a map not 4-byte aligned, sums not 8-byte aligned, unknown flag bits.
+ *
+ * mnv_ssim_window (host; no GPU needed): out[i] = exp(-(i - 5)^2 / 4.5) in double (sigma = 1.5), divided by the sum of the eleven taken
+ * in index order, rounded to float.
+ * mnv_metrics_finish (host, double): from a HOST copy of the sums, mse = se_q32 / 2^32 / (3 n_px); psnr = -10 log10(mse) (+inf for
+ * mse 0, NaN for n_px 0); ssim = ssim_q32 / 2^32 / (3 n_win) (NaN for n_win 0); and the two counts.
+ */
+#define MNV_METRIC_QUANTISED 1
+#define MNV_METRIC_MASK_ALPHA 2
+#define MNV_METRIC_SSIM 4
+typedef struct mnv_metric_sums {
+    int64_t n_px, se_q32, n_win, ssim_q32, reserved;
+} mnv_metric_sums;
+typedef struct mnv_frame_metric_values {
+    double mse, psnr, ssim;
+    int64_t n_px, n_win;
+} mnv_frame_metric_values;
+int mnv_frame_metrics(const float *rgba /* device [height][width][4] */, const uint8_t *target8 /* device [height][width][4] */, int32_t width,
+                      int32_t height, int32_t flags, const float *window /* HOST [11] or NULL */, mnv_metric_sums *sums /* DEVICE */,
+                      float *se_map_out /* device or NULL */, float *ssim_map_out /* device or NULL */, void *hip_stream);
+int mnv_ssim_window(float *out /* host [11] */);
+int mnv_metrics_finish(const mnv_metric_sums *host_copy, mnv_frame_metric_values *out);
+/* Binary PNM files on the host (no GPU needed): P6 (3 channels, what `mnv_render --out` writes) and P5 (1 channel), maxval 255, `#`
+ * comments in the header.  Size-query convention of mnv_obj_read: *width, *height and *channels are always set once the header is read
+ * (any may be NULL); data NULL with cap_bytes 0 asks for them alone; a buffer shorter than width * height * channels is MNV_E_INVALID.
+ * expect_width / expect_height > 0: a file of another size is refused.  MNV_E_IO (mnv_last_error says what): a file that cannot be
+ * read, another magic, a malformed or truncated header, a maxval other than 255, an unexpected size, fewer data bytes than the header
+ * promises. */
+int mnv_pnm_read(const char *path, int32_t expect_width, int32_t expect_height, uint8_t *data /* host */, int64_t cap_bytes, int32_t *width,
+                 int32_t *height, int32_t *channels);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -1061,6 +1124,17 @@ int mnv_renderer_set_antialiasing(mnv_renderer *r, int32_t samples, int32_t filt
  * than the pinhole meets caller-set frame inputs, several ranks, options.show_grid, a visible mesh, antialiasing with more than one sample,
  * a model with use_splitting / use_guided_sampling, or a tree without a packed accel (MNV_PROJ_PINHOLE renders again). */
 int mnv_renderer_set_projection(mnv_renderer *r, int32_t projection);
+/* VolumeRenderer::set_target (default NULL: every frame is what it is without this call, byte for byte).  rgba8_device non-NULL: every
+ * mnv_renderer_render is followed, on the frame slot's stream, by mnv_frame_metrics(`flags`, the standard window) of the slot's float
+ * frame against that DEVICE array [height][width][4] into the slot's own device sums, and by a 40-byte copy of them to pinned host
+ * memory -- whatever the frame kind (plain, in flight, anti-aliased, orthographic, equirectangular, grid, meshes, frame inputs,
+ * refinement and guided frames).  The frames themselves do not change.  The pointer is sampled at each render: it may change per frame,
+ * and an array must stay valid until its slot has been collected.  mnv_renderer_slot_metrics waits for the frame of `slot` only and
+ * finishes its sums (mnv_metrics_finish); MNV_E_INVALID when the last frame of that slot was not scored.  A resize to another size clears the target,
+ * and so does rgba8_device NULL (collect the frames in flight first: their scores go with it).  MNV_E_INVALID: unknown flag bits; a
+ * target together with mnv_renderer_set_ranks, in either order. */
+int mnv_renderer_set_target(mnv_renderer *r, const uint8_t *rgba8_device, int32_t flags);
+int mnv_renderer_slot_metrics(mnv_renderer *r, int32_t slot, mnv_frame_metric_values *out);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

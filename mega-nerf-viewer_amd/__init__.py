@@ -147,6 +147,19 @@ class RendererStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class MetricSums(C.Structure):
+    """mnv_metric_sums: the five int64 words mnv_frame_metrics leaves in device memory."""
+    _fields_ = [("n_px", C.c_int64), ("se_q32", C.c_int64), ("n_win", C.c_int64), ("ssim_q32", C.c_int64), ("reserved", C.c_int64)]
+
+
+class FrameMetricValues(C.Structure):
+    """mnv_frame_metric_values: what mnv_metrics_finish makes of the sums."""
+    _fields_ = [("mse", C.c_double), ("psnr", C.c_double), ("ssim", C.c_double), ("n_px", C.c_int64), ("n_win", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SynthRandomParams(C.Structure):
     _fields_ = [
         ("depth", C.c_int32),
@@ -361,6 +374,12 @@ _SIGNATURES = {
     "mnv_generate_rays": (C.c_int, [C.c_int32, C.POINTER(CameraStruct), Rect, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mnv_equirect_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
     "mnv_renderer_set_projection": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mnv_frame_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_ssim_window": (C.c_int, [C.c_void_p]),
+    "mnv_metrics_finish": (C.c_int, [C.POINTER(MetricSums), C.POINTER(FrameMetricValues)]),
+    "mnv_pnm_read": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mnv_renderer_set_target": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "mnv_renderer_slot_metrics": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FrameMetricValues)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1169,6 +1188,8 @@ class Renderer:
 
     def resize(self, width: int, height: int) -> None:
         _check(lib().mnv_renderer_resize(self._h, width, height))
+        if (width, height) != (self.width, self.height) and self.width:   # the renderer dropped a target of the old size
+            self._target, self._slot_targets = None, {}
         self.width, self.height = width, height
 
     def set_camera(self, center, back, up=(0.0, 0.0, 1.0), fx: float = -1.0, fy: float = -1.0) -> None:
@@ -1184,6 +1205,8 @@ class Renderer:
             if a:
                 _fused_defaults(a)
         _check(lib().mnv_renderer_render(self._h, C.byref(st)))
+        if getattr(self, "_target", None) is not None:   # the frame's slot reads this tensor until it is collected
+            self._slot_targets[self.last_slot()] = self._target
         return st.as_dict()
 
     def download(self, want_rgba8=False):
@@ -1246,6 +1269,30 @@ class Renderer:
         refuses with another projection (frame inputs, ranks, show_grid, a visible mesh, anti-aliasing, refinement, no packed accel)
         raises there, with MNV_E_INVALID."""
         _check(lib().mnv_renderer_set_projection(self._h, int(projection)))
+
+    def set_target(self, target=None, flags: int = 0) -> None:
+        """VolumeRenderer::set_target: score every frame against `target`, a contiguous uint8 device tensor [height, width, 4], on the
+        device (METRIC_QUANTISED / METRIC_MASK_ALPHA / METRIC_SSIM); metrics(slot) collects a frame's score.  The tensor may change per
+        frame; this object keeps it alive (and the tensor of every slot's last frame).  None (the default): frames are not scored."""
+        if target is None:
+            self._target, self._slot_targets = None, {}
+            _check(lib().mnv_renderer_set_target(self._h, None, 0))
+            return
+        import torch
+
+        if not target.is_cuda or not target.is_contiguous() or target.dtype != torch.uint8 or target.numel() != self.width * self.height * 4:
+            raise MnvError(MNV_E_INVALID, f"target must be a contiguous uint8 device tensor of {self.height} x {self.width} x 4 elements")
+        _check(lib().mnv_renderer_set_target(self._h, C.c_void_p(target.data_ptr()), int(flags)))
+        self._target = target
+        if not hasattr(self, "_slot_targets"):
+            self._slot_targets = {}
+
+    def metrics(self, slot=None) -> dict:
+        """mnv_renderer_slot_metrics: wait for the frame of `slot` (None: the last frame's) and return its score as a dict (mse, psnr, ssim,
+        n_px, n_win); raises MnvError (MNV_E_INVALID) when that frame was not scored."""
+        v = FrameMetricValues()
+        _check(lib().mnv_renderer_slot_metrics(self._h, self.last_slot() if slot is None else int(slot), C.byref(v)))
+        return v.as_dict()
 
     def add_mesh(self, mesh: "Mesh") -> None:
         """VolumeRenderer::meshes: while a listed mesh is visible every frame draws the list (over the grid, if show_grid is set) with
@@ -1497,6 +1544,64 @@ def resolve_samples(sub, weights, radius: int, rgba=None, rgba8=None, stream: in
     _check_out("rgba8", rgba8, w * h, "u8")
     with _timed(stream):
         _check(lib().mnv_resolve_samples(sub.data_ptr(), n, w, h, weights.data_ptr(), int(radius), _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
+
+
+METRIC_QUANTISED, METRIC_MASK_ALPHA, METRIC_SSIM = 1, 2, 4
+
+
+def ssim_window() -> np.ndarray:
+    """mnv_ssim_window: the standard SSIM window, float32 [11] (Gaussian, sigma 1.5, normalised in double, rounded to float)."""
+    out = np.zeros(11, np.float32)
+    _check(lib().mnv_ssim_window(out.ctypes.data))
+    return out
+
+
+def metrics_finish(sums) -> dict:
+    """mnv_metrics_finish: (n_px, se_q32, n_win, ssim_q32[, reserved]) -- a MetricSums, a sequence or the int64 tensor frame_metrics
+    returns -- to a dict of mse, psnr, ssim (Python floats; inf / nan as the header states) and the two counts."""
+    if not isinstance(sums, MetricSums):
+        w = [int(x) for x in (sums.tolist() if hasattr(sums, "tolist") else sums)]
+        sums = MetricSums(*(w + [0] * (5 - len(w))))
+    v = FrameMetricValues()
+    _check(lib().mnv_metrics_finish(C.byref(sums), C.byref(v)))
+    return v.as_dict()
+
+
+def frame_metrics(rgba, target8, flags: int = 0, window=None, sums=None, se_map=None, ssim_map=None, stream: int = 0):
+    """mnv_frame_metrics (asynchronous on `stream`): rgba float32 device tensor [h, w, 4] against target8 uint8 device tensor [h, w, 4].
+    Returns `sums`, an int64 device tensor [5] (n_px, se_q32, n_win, ssim_q32, 0; allocated when None, zeroed by the call).  window: None
+    (the standard one) or 11 floats (host).  se_map float32 [h, w] / ssim_map float32 [h - 10, w - 10, 3]: optional device outputs."""
+    import torch
+
+    if not rgba.is_cuda or not rgba.is_contiguous() or rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4:
+        raise MnvError(MNV_E_INVALID, "rgba must be a contiguous float32 device tensor [height, width, 4]")
+    h, w = int(rgba.shape[0]), int(rgba.shape[1])
+    if not target8.is_cuda or not target8.is_contiguous() or target8.dtype != torch.uint8 or target8.numel() != w * h * 4:
+        raise MnvError(MNV_E_INVALID, f"target8 must be a contiguous uint8 device tensor of {h} x {w} x 4 elements")
+    if sums is None:
+        sums = torch.empty(5, dtype=torch.int64, device=rgba.device)
+    if not sums.is_cuda or not sums.is_contiguous() or sums.dtype != torch.int64 or sums.numel() < 5:
+        raise MnvError(MNV_E_INVALID, "sums must be a contiguous int64 device tensor of 5 elements")
+    for name, t, n in (("se_map", se_map, w * h), ("ssim_map", ssim_map, max(w - 10, 0) * max(h - 10, 0) * 3)):
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or t.numel() < n):
+            raise MnvError(MNV_E_INVALID, f"{name} must be a contiguous float32 device tensor with at least {n} elements")
+    g = None if window is None else np.ascontiguousarray(window, np.float32).reshape(-1)
+    if g is not None and g.size != 11:
+        raise MnvError(MNV_E_INVALID, "window has 11 entries")
+    with _timed(stream):
+        _check(lib().mnv_frame_metrics(rgba.data_ptr(), target8.data_ptr(), w, h, int(flags), g.ctypes.data if g is not None else None, sums.data_ptr(),
+                                       _ptr(se_map), _ptr(ssim_map), C.c_void_p(stream)))
+    return sums
+
+
+def pnm_read(path: str, expect_width: int = 0, expect_height: int = 0) -> np.ndarray:
+    """mnv_pnm_read: a binary PPM (P6) / PGM (P5) file with maxval 255 as uint8 [height, width, channels]; a malformed file, or one of
+    another size than expected, raises MnvError (MNV_E_IO)."""
+    w, h, ch = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().mnv_pnm_read(os.fsencode(path), int(expect_width), int(expect_height), None, 0, C.byref(w), C.byref(h), C.byref(ch)))
+    out = np.empty((h.value, w.value, ch.value), np.uint8)
+    _check(lib().mnv_pnm_read(os.fsencode(path), int(expect_width), int(expect_height), out.ctypes.data, out.size, C.byref(w), C.byref(h), C.byref(ch)))
+    return out
 
 
 PROJ_PINHOLE, PROJ_ORTHO, PROJ_EQUIRECT = 0, 1, 2

@@ -462,6 +462,22 @@ int mnv_renderer_set_projection(mnv_renderer *r, int32_t projection) {
     return MNV_OK;
 }
 
+int mnv_renderer_set_target(mnv_renderer *r, const uint8_t *rgba8_device, int32_t flags) {
+    if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
+    return guarded([&] {
+        r->rend.set_target(rgba8_device, flags);
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_slot_metrics(mnv_renderer *r, int32_t slot, mnv_frame_metric_values *out) {
+    if (!r || !out) return mnv::set_error(MNV_E_INVALID, "null argument");
+    return guarded([&] {
+        r->rend.slot_metrics(slot, out);
+        return MNV_OK;
+    });
+}
+
 int mnv_model_matrix(const float rotation[3], const float translation[3], float scale, float *matrix3x4_out) {
     if (!rotation || !translation || !matrix3x4_out) return mnv::set_error(MNV_E_INVALID, "mnv_model_matrix: null argument");
     viewer::model_matrix(rotation, translation, scale, matrix3x4_out);

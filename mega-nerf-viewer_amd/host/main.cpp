@@ -41,6 +41,13 @@
 //   --mesh PATH[,unlit]   draw a Wavefront OBJ file under the volume (viewer::Mesh::load_obj, VolumeRenderer::meshes); repeatable.
 //                    --mesh_color r,g,b (vertices without a colour; default white), --mesh_translate x,y,z, --mesh_rotate x,y,z
 //                    (axis-angle) and --mesh_scale s apply to the mesh named before them.  Refused with --gpus, as --grid is.
+//   --target PREFIX  score frame f against PREFIX_%04d.ppm (the P6 files --out writes) on the device (VolumeRenderer::set_target,
+//                    mnv_frame_metrics with MNV_METRIC_QUANTISED: the file --out would write against the file that was read) and print
+//                    "frame F: psnr ..." when the frame is collected, then the means over the frames.  --ssim adds SSIM (11 x 11 Gaussian
+//                    window, valid windows only).  --target_mask PREFIX reads PREFIX_%04d.pgm (P5) per frame: pixels whose mask byte is 0
+//                    are excluded (Mega-NeRF's per-image masks).  Files of another size than the frame are refused.  Refused with --gpus.
+//                    Out of scope: pose lists (the camera poses stay --orbit or the API) and LPIPS (it needs a network this repository
+//                    does not have).
 #include <hip/hip_runtime_api.h>
 
 #include <sys/mman.h>
@@ -95,7 +102,7 @@ Args parse(int argc, char **argv) {
         {"s", "step_size"}, {"e", "stop_thresh"}, {"a", "sigma_thresh"}, {"c", "max_tree_capacity"}, {"x", "split_batch_size"},
         {"n", "nerf_batch_size"}, {"v", "samples_per_voxel"}, {"b", "bounds_only"}, {"y", "appearance_embedding"},
         {"z", "max_guided_samples"}, {"w", "width"}, {"h", "height"}};
-    static const char *flags[] = {"bounds_only", "raw", "help", "use_splitting", "use_guided_sampling", "guided_in_flight"};
+    static const char *flags[] = {"bounds_only", "raw", "help", "use_splitting", "use_guided_sampling", "guided_in_flight", "ssim"};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string t = argv[i];
@@ -127,6 +134,9 @@ void usage() {
               "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--grid D] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
               "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--projection pinhole|ortho|equirect] [--gpus N [--reserve_cus R] [--root_period M]]\n"
               "                  [--mesh FILE.obj[,unlit] [--mesh_color r,g,b] [--mesh_translate x,y,z] [--mesh_rotate x,y,z] [--mesh_scale s]]...\n"
+              "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
+              "                   0 = excluded): PSNR and, with --ssim, SSIM per frame and their means; not with --gpus.  Out of scope: pose\n"
+              "                   lists (poses stay --orbit or the API) and LPIPS (it needs a network this repository does not have)\n"
               "                  [--model_path MODEL.npz [--use_splitting] [--use_guided_sampling] [-x split_batch_size] [-v samples_per_voxel]\n"
               "                   [-y appearance_embedding] [-z max_guided_samples] [--max_depth D] [--max_sample_count C] [--seed S]\n"
               "                   [--save_tree FILE.npz]]");
@@ -603,6 +613,9 @@ int main(int argc, char **argv) {
         if (projection != "pinhole" && projection != "ortho" && projection != "equirect") throw std::runtime_error("--projection is pinhole, ortho or equirect");
         if (projection != "pinhole" && (args.has("gpus") || args.has("grid") || !args.mesh_flags.empty() || args.l("aa", 1) != 1))
             throw std::runtime_error("--projection " + projection + " marches a ray list: it cannot be combined with --gpus, --grid, --mesh or --aa other than 1");
+        if (args.has("gpus") && (args.has("target") || args.has("target_mask") || args.has("ssim")))
+            throw std::runtime_error("--target scores the frames of one GPU: it cannot be combined with --gpus");
+        if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 
@@ -643,11 +656,56 @@ int main(int argc, char **argv) {
         rend.aa_samples = (int)args.l("aa", 1);
         rend.aa_filter = aa_filter == "box" ? MNV_AA_BOX : MNV_AA_TENT;
         rend.projection = projection == "ortho" ? MNV_PROJ_ORTHO : projection == "equirect" ? MNV_PROJ_EQUIRECT : MNV_PROJ_PINHOLE;
+        // --target: one device image per frame slot, filled before the frame that takes the slot is issued
+        const std::string target = args.get("target", ""), target_mask = args.get("target_mask", "");
+        const bool score = !target.empty(), ssim = args.has("ssim");
+        const int score_flags = MNV_METRIC_QUANTISED | (target_mask.empty() ? 0 : MNV_METRIC_MASK_ALPHA) | (ssim ? MNV_METRIC_SSIM : 0);
+        const size_t frame_px = (size_t)width * height;
+        std::vector<uint8_t *> target_dev(score ? (size_t)rend.frames_in_flight : 0, nullptr);
+        std::vector<uint8_t> target_rgb, target_alpha, target_rgba;
+        auto load_target = [&](long f, int slot) {
+            char name[4096];
+            int32_t w = 0, h = 0, ch = 0;
+            std::snprintf(name, sizeof(name), "%s_%04ld.ppm", target.c_str(), f);
+            target_rgb.resize(frame_px * 3);
+            mnv_ok(mnv_pnm_read(name, width, height, target_rgb.data(), (int64_t)target_rgb.size(), &w, &h, &ch), "--target");
+            if (ch != 3) throw std::runtime_error(std::string("--target: ") + name + " is not a P6 file");
+            target_alpha.assign(frame_px, 255);
+            if (!target_mask.empty()) {
+                std::snprintf(name, sizeof(name), "%s_%04ld.pgm", target_mask.c_str(), f);
+                mnv_ok(mnv_pnm_read(name, width, height, target_alpha.data(), (int64_t)target_alpha.size(), &w, &h, &ch), "--target_mask");
+                if (ch != 1) throw std::runtime_error(std::string("--target_mask: ") + name + " is not a P5 file");
+            }
+            target_rgba.resize(frame_px * 4);
+            for (size_t p = 0; p < frame_px; ++p) {
+                target_rgba[p * 4 + 0] = target_rgb[p * 3 + 0];
+                target_rgba[p * 4 + 1] = target_rgb[p * 3 + 1];
+                target_rgba[p * 4 + 2] = target_rgb[p * 3 + 2];
+                target_rgba[p * 4 + 3] = target_alpha[p];
+            }
+            if (!target_dev[slot]) hip_ok(hipMalloc((void **)&target_dev[slot], frame_px * 4), "hipMalloc(target image)");
+            hip_ok(hipMemcpy(target_dev[slot], target_rgba.data(), frame_px * 4, hipMemcpyHostToDevice), "upload target image");
+            rend.set_target(target_dev[slot], score_flags);
+        };
+        double psnr_sum = 0.0, ssim_sum = 0.0;
+        long scored = 0;
         std::deque<std::pair<long, int>> pending;  // (frame, slot) rendered but not yet written
         auto write_oldest = [&]() {
             const long f = pending.front().first;
             const int slot = pending.front().second;
             pending.pop_front();
+            if (score) {
+                mnv_frame_metric_values m{};
+                rend.slot_metrics(slot, &m);
+                if (ssim)
+                    std::printf("frame %ld: psnr %.4f ssim %.6f\n", f, m.psnr, m.ssim);
+                else
+                    std::printf("frame %ld: psnr %.4f\n", f, m.psnr);
+                psnr_sum += m.psnr;
+                ssim_sum += m.ssim;
+                ++scored;
+            }
+            if (out.empty()) return;
             rend.download_slot(slot, args.has("raw") ? &rgba : nullptr, &rgba8);
             if (refine && rend.guided_in_flight) std::printf("frame %ld: guided samples %ld\n", f, rend.slot_guided_samples(slot));
             write_frame(out, f, width, height, rgba8.data(), args.has("raw") ? rgba.data() : nullptr);
@@ -661,13 +719,23 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < pending.size(); ++i)
                 if (pending[i].second == next) keep = pending.size() - 1 - i;
             while (pending.size() > keep) write_oldest();
+            if (score) load_target(f, next);
             rend.render();
             if (refine) print_refine_stats(f, rend.stats);
-            if (!out.empty()) pending.emplace_back(f, rend.last_slot());
+            if (!out.empty() || score) pending.emplace_back(f, rend.last_slot());
             if (orbit != 0.0) orbit_step(rend.camera, orbit);
         }
         while (!pending.empty()) write_oldest();
         rend.sync_tree_streams();
+        if (score) {
+            rend.set_target(nullptr);
+            for (uint8_t *p : target_dev)
+                if (p) (void)hipFree(p);
+            if (ssim)
+                std::printf("mean over %ld frame(s): psnr %.4f ssim %.6f\n", scored, psnr_sum / std::max<long>(scored, 1), ssim_sum / std::max<long>(scored, 1));
+            else
+                std::printf("mean over %ld frame(s): psnr %.4f\n", scored, psnr_sum / std::max<long>(scored, 1));
+        }
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         if (args.has("save_tree") && tree.N > 0) {
             rend.sync_tree();

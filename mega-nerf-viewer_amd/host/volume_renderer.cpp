@@ -99,6 +99,8 @@ struct VolumeRenderer::Impl {
         uint8_t *grid_rgba8 = nullptr;
         float *aa_sub = nullptr;  // aa_samples > 1: this slot's K float sub-frames
         float *ray_origins = nullptr, *ray_dirs = nullptr;  // projection != pinhole: this slot's rays, [height][width][3] each
+        mnv_metric_sums *sums_dev = nullptr, *sums_host = nullptr;  // set_target: this slot's sums and their pinned copy
+        bool scored = false;                                         // ... which the last frame on this slot has written (or is about to)
     };
     std::vector<Slot> slots;
     int cur = 0;            // slot of the most recent render()
@@ -109,6 +111,12 @@ struct VolumeRenderer::Impl {
     uint8_t *rgba8 = nullptr;
     int width = 0, height = 0;
     bool initial_resize = true;
+    const uint8_t *target = nullptr;  // set_target: the caller's device image every frame is scored against, and the flags of the score
+    int target_flags = 0;
+    void clear_target() {
+        target = nullptr;
+        for (Slot &s : slots) s.scored = false;
+    }
 
     // refinement state (cuda_renderer.cpp:441-468,571-600)
     mnv_mlp *mlp = nullptr;
@@ -201,6 +209,8 @@ struct VolumeRenderer::Impl {
         for (Slot &s : slots) {
             if (s.count_dev) (void)hipFree(s.count_dev);
             if (s.count_host) (void)hipHostFree(s.count_host);
+            if (s.sums_dev) (void)hipFree(s.sums_dev);
+            if (s.sums_host) (void)hipHostFree(s.sums_host);
             if (s.stream) (void)hipStreamDestroy(s.stream);
         }
     }
@@ -522,6 +532,7 @@ void VolumeRenderer::set_frame_inputs(const float *tmax_px_device, const uint8_t
 
 void VolumeRenderer::set_ranks(mnv_comm *comm, int tile_w, int tile_h) {
     Impl &I = *impl_;
+    if (comm && I.target) throw StatusError(MNV_E_INVALID, "set_target scores the frame of one rank: it cannot be combined with set_ranks");
     if (comm && (I.inputs.tmax_px || I.inputs.rgba8_init)) throw std::runtime_error("frame inputs (offscreen == false) are for one rank");
     I.sync_all();
     I.comm = comm;
@@ -543,6 +554,7 @@ void VolumeRenderer::resize(int width, int height) {
         if (camera.default_cx != -1) camera.cx *= wr;
         if (camera.default_cy != -1) camera.cy *= hr;
     }
+    if (!impl_->initial_resize) impl_->clear_target();  // an image of the old size (the first call only sets the size, also when render() makes it)
     impl_->initial_resize = false;
     camera.width = width;
     camera.height = height;
@@ -555,7 +567,50 @@ void VolumeRenderer::resize(int width, int height) {
     impl_->use_slot(0);
 }
 
+void VolumeRenderer::set_target(const uint8_t *rgba8_device, int flags) {
+    Impl &I = *impl_;
+    if (!rgba8_device) {
+        I.clear_target();
+        return;
+    }
+    if ((flags & ~(MNV_METRIC_QUANTISED | MNV_METRIC_MASK_ALPHA | MNV_METRIC_SSIM)) != 0) throw StatusError(MNV_E_INVALID, "set_target: unknown flag bits");
+    if (I.comm) throw StatusError(MNV_E_INVALID, "set_target scores the frame of one rank: it cannot be combined with set_ranks");
+    I.target = rgba8_device;
+    I.target_flags = flags;
+}
+
+void VolumeRenderer::slot_metrics(int slot, mnv_frame_metric_values *out) {
+    Impl &I = *impl_;
+    if (slot < 0 || slot >= (int)I.slots.size() || !I.slots[slot].scored)
+        throw StatusError(MNV_E_INVALID, "slot_metrics: the last frame of this slot was not scored (set_target)");
+    hip_check(hipStreamSynchronize(I.slots[slot].stream), "slot_metrics");
+    mnv_check(mnv_metrics_finish(I.slots[slot].sums_host, out), "mnv_metrics_finish");
+}
+
+// the frame, then its score: on the frame's slot and stream, whatever kind of frame it was
 void VolumeRenderer::render() {
+    Impl &I = *impl_;
+    const uint8_t *target = I.target;
+    if (!target) {
+        render_frame();
+        I.slots[I.cur].scored = false;
+        return;
+    }
+    if (I.comm) throw StatusError(MNV_E_INVALID, "set_target scores the frame of one rank: it cannot be combined with set_ranks");
+    render_frame();
+    Impl::Slot &S = I.slots[I.cur];
+    S.scored = false;
+    if (!S.sums_dev) {
+        hip_check(hipMalloc((void **)&S.sums_dev, sizeof(mnv_metric_sums)), "hipMalloc(metric sums)");
+        hip_check(hipHostMalloc((void **)&S.sums_host, sizeof(mnv_metric_sums), hipHostMallocDefault), "hipHostMalloc(metric sums)");
+    }
+    const int rc = mnv_frame_metrics(S.rgba, target, I.width, I.height, I.target_flags, nullptr, S.sums_dev, nullptr, nullptr, S.stream);
+    if (rc != MNV_OK) throw StatusError(rc, std::string("mnv_frame_metrics: ") + mnv_last_error());
+    hip_check(hipMemcpyAsync(S.sums_host, S.sums_dev, sizeof(mnv_metric_sums), hipMemcpyDeviceToHost, S.stream), "read metric sums");
+    S.scored = true;
+}
+
+void VolumeRenderer::render_frame() {
     Impl &I = *impl_;
     if (!I.slots[0].rgba) resize(camera.width, camera.height);
     camera._update();

@@ -139,6 +139,17 @@ struct VolumeRenderer {
     // Refused (StatusError, MNV_E_INVALID) with another projection than the pinhole: set_frame_inputs, set_ranks, options.show_grid, a
     // visible mesh, aa_samples > 1, a model with use_splitting / use_guided_sampling, a tree without a packed accel, an unknown projection.
     int projection = MNV_PROJ_PINHOLE;
+    // Score every frame against a target image on the device (mnv_frame_metrics; the reference has none).  Null (the default): render() is
+    // what it is without this call.  Otherwise every render() -- whatever the frame kind -- is followed, on the frame slot's stream, by
+    // mnv_frame_metrics(flags, the standard window) of the slot's float frame against `rgba8_device` ([height][width][4] uint8) into the
+    // slot's own device sums and by a 40-byte copy of them to pinned host memory; the frame itself does not change.  The pointer is sampled
+    // at render(): it may change per frame, and the caller keeps an array valid until its slot was collected.  slot_metrics() waits for
+    // that slot only and finishes the sums (mnv_metrics_finish); StatusError(MNV_E_INVALID) when the slot's last frame was not scored.
+    // A resize() that changes the size clears the target (the first one only sets the size); so does a null pointer, together with the
+    // scores not yet collected.
+    // Refused (StatusError, MNV_E_INVALID): unknown flag bits; a target together with set_ranks, in either order.
+    void set_target(const uint8_t *rgba8_device, int flags = 0);
+    void slot_metrics(int slot, mnv_frame_metric_values *out);
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
@@ -164,6 +175,7 @@ struct VolumeRenderer {
     RenderOptions options;
 
 private:
+    void render_frame();  // render() but for the score
     void render_ranks();
     void render_aa(const mnv_camera &cv, bool grid);
     void render_projected(const mnv_camera &cv);
