@@ -772,42 +772,58 @@ def _check_out(name: str, t, pixels: int, dtype_name: str) -> None:
 
 
 def _pixels(tile, n_frames: int, part) -> int:
-    """Pixels the launch may write: frames x tile, or frames x j_max macro tiles for a partitioned launch."""
+    """Pixels the launch may write: frames x tile; under a partition the rank's own macro tiles, or frames x j_max macro tiles for a batch."""
     _, _, w, h = tile
     if part is None or not (part[1] > 1 or (part[1] == 1 and part[2] > 0)):
         return n_frames * w * h
     rank, world, tw, th = part[:4]
     period = part[4] if len(part) > 4 else 0
+    if n_frames == 1:
+        return partition_local_tiles(tile, rank, world, tw, th, period) * tw * th
     j_max = max(partition_local_tiles(tile, r, world, tw, th, period) for r in range(world))
     return n_frames * j_max * tw * th
+
+
+def _accel_frame(cam: Camera, tile, rgba, rgba8, tmax_px=None, rgba8_init=None, n_frames: int = 1, part=None):
+    """What every wrapper of a packed-layout entry point derives first: the default tile (the camera's image), the output tensors checked
+    against the pixels of the launch, and mnv_frame_inputs.  Returns (mnv_rect, inputs by reference or None)."""
+    if tile is None:
+        tile = (0, 0, cam.width, cam.height)
+    px = _pixels(tile, n_frames, part)
+    _check_out("rgba", rgba, px, "f32")
+    _check_out("rgba8", rgba8, px, "u8")
+    inputs = _frame_inputs(tmax_px, rgba8_init, tile[2] * tile[3])
+    return Rect(*tile), (C.byref(inputs) if inputs is not None else None)
+
+
+def _march_accel(accel: int, cam: Camera, opt: RenderOptions, frame, rgba, rgba8, stream: int, split_track=None, sample_track=None, sample_counts=None,
+                 visited=None, parent=None, part=None) -> None:
+    """The launch behind render_voxels_accel[_track|_visit|_part]: the most general entry point of the whole-frame / the partitioned family,
+    NULL for the extras a caller does not use.  frame: what _accel_frame returned."""
+    rect, inputs = frame
+    extras = (_ptr(rgba), _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent), C.c_void_p(stream))
+    if part is None:
+        _check(lib().mnv_render_voxels_accel_visit_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), rect, inputs, *extras))
+        return
+    if inputs is not None:
+        raise MnvError(MNV_E_INVALID, "frame inputs are for whole-frame launches")
+    _check(lib().mnv_render_voxels_accel_visit_part(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), rect, Partition(*part), *extras))
 
 
 def render_voxels_accel(accel: int, cam: Camera, opt: RenderOptions, tile=None, rgba=None, rgba8=None, stream: int = 0, tmax_px=None,
                         rgba8_init=None) -> None:
     """The tuned march on the packed layout (asynchronous on `stream`); tmax_px / rgba8_init as in render_voxels."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
-    _check_out("rgba", rgba, tile[2] * tile[3], "f32")
-    _check_out("rgba8", rgba8, tile[2] * tile[3], "u8")
-    inputs = _frame_inputs(tmax_px, rgba8_init, tile[2] * tile[3])
+    frame = _accel_frame(cam, tile, rgba, rgba8, tmax_px, rgba8_init)
     with _timed(stream):
-        if inputs is not None:
-            _check(lib().mnv_render_voxels_accel_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), C.byref(inputs), _ptr(rgba),
-                                                    _ptr(rgba8), C.c_void_p(stream)))
-            return
-        _check(lib().mnv_render_voxels_accel(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), _ptr(rgba), _ptr(rgba8),
-                                             C.c_void_p(stream)))
+        _march_accel(accel, cam, opt, frame, rgba, rgba8, stream)
 
 
 def render_voxels_accel_track(accel: int, cam: Camera, opt: RenderOptions, tile=None, rgba=None, rgba8=None,
                               split_track=None, sample_track=None, sample_counts=None, stream: int = 0) -> None:
     """The tuned march with the refinement trackers (rows as render_voxels writes them)."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
+    frame = _accel_frame(cam, tile, rgba, rgba8)
     with _timed(stream):
-        _check(lib().mnv_render_voxels_accel_track(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), _ptr(rgba),
-                                                   _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts),
-                                                   C.c_void_p(stream)))
+        _march_accel(accel, cam, opt, frame, rgba, rgba8, stream, split_track, sample_track, sample_counts)
 
 
 def render_voxels_accel_visit(accel: int, cam: Camera, opt: RenderOptions, visited, parent, tile=None, rgba=None, rgba8=None, split_track=None,
@@ -815,44 +831,19 @@ def render_voxels_accel_visit(accel: int, cam: Camera, opt: RenderOptions, visit
     """Tracker march on the packed accel that also leaves the reference's visit marks (march marks leaf chunks, closure adds ancestors).
     part = (rank, world, tile_w, tile_h[, root_period]): only that rank's macro tiles, pixels and tracker rows in compact tile order.
     tmax_px / rgba8_init: the reference's offscreen == false inputs (whole-frame launches only)."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
-    inputs = _frame_inputs(tmax_px, rgba8_init, tile[2] * tile[3])
-    if inputs is not None:
-        if part is not None:
-            raise MnvError(MNV_E_INVALID, "frame inputs are for whole-frame launches")
-        _check(lib().mnv_render_voxels_accel_visit_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), C.byref(inputs), _ptr(rgba), _ptr(rgba8),
-                                                      _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent),
-                                                      C.c_void_p(stream)))
-        return
-    if part is not None:
-        px = _pixels(tile, 1, part)
-        _check_out("rgba", rgba, px, "f32")
-        _check_out("rgba8", rgba8, px, "u8")
-        _check(lib().mnv_render_voxels_accel_visit_part(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), Partition(*part), _ptr(rgba), _ptr(rgba8),
-                                                        _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent),
-                                                        C.c_void_p(stream)))
-        return
-    _check(lib().mnv_render_voxels_accel_visit(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), _ptr(rgba), _ptr(rgba8), _ptr(split_track),
-                                               _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent), C.c_void_p(stream)))
+    frame = _accel_frame(cam, tile, rgba, rgba8, tmax_px, rgba8_init, part=part)
+    _march_accel(accel, cam, opt, frame, rgba, rgba8, stream, split_track, sample_track, sample_counts, visited, parent, part)
 
 
 def get_samples_from_voxels_accel_visit(accel: int, cam: Camera, opt: RenderOptions, visited, parent, num_samples, samples, cluster_indices,
                                         grid: ClusterGrid, split_track=None, sample_track=None, sample_counts=None, tile=None, stream: int = 0,
                                         tmax_px=None) -> None:
     """tmax_px: the depth attachment of the reference's offscreen == false call (every ray stops there), indexed like the pixels."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
-    inputs = _frame_inputs(tmax_px, None, tile[2] * tile[3])
-    if inputs is not None:
-        _check(lib().mnv_get_samples_from_voxels_accel_visit_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), C.byref(inputs),
-                                                                _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent),
-                                                                _ptr(num_samples), _ptr(samples), int(samples.shape[-1]), _ptr(cluster_indices),
-                                                                C.byref(grid), C.c_void_p(stream)))
-        return
-    _check(lib().mnv_get_samples_from_voxels_accel_visit(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), _ptr(split_track), _ptr(sample_track),
-                                                         _ptr(sample_counts), _ptr(visited), _ptr(parent), _ptr(num_samples), _ptr(samples),
-                                                         int(samples.shape[-1]), _ptr(cluster_indices), C.byref(grid), C.c_void_p(stream)))
+    rect, inputs = _accel_frame(cam, tile, None, None, tmax_px)
+    _check(lib().mnv_get_samples_from_voxels_accel_visit_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), rect, inputs, _ptr(split_track),
+                                                            _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent), _ptr(num_samples),
+                                                            _ptr(samples), int(samples.shape[-1]), _ptr(cluster_indices), C.byref(grid),
+                                                            C.c_void_p(stream)))
 
 
 def accel_set_colour_math(accel: int, mode: int) -> None:
@@ -951,14 +942,10 @@ def render_voxels_accel_part(accel: int, cam: Camera, opt: RenderOptions, rank: 
                              tile=None, rgba=None, rgba8=None, stream: int = 0, root_period: int = 0) -> None:
     """Render the macro tiles of `rank` (m % world == rank, or the root-relieving deal of mnv_partition.root_period) of `tile` into a
     compact local-tile-major buffer [local_tiles][tile_h][tile_w][4] (see mnv_partition in include/mnv.h)."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
-    n_local = partition_local_tiles(tile, rank, world, tile_w, tile_h, root_period)
-    _check_out("rgba", rgba, n_local * tile_w * tile_h, "f32")
-    _check_out("rgba8", rgba8, n_local * tile_w * tile_h, "u8")
+    part = (rank, world, tile_w, tile_h, root_period)
+    frame = _accel_frame(cam, tile, rgba, rgba8, part=part)
     with _timed(stream):
-        _check(lib().mnv_render_voxels_accel_part(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile),
-                                                  Partition(rank, world, tile_w, tile_h, root_period), _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
+        _march_accel(accel, cam, opt, frame, rgba, rgba8, stream, part=part)
 
 
 def get_samples_from_voxels(tree_view: TreeView, cam: Camera, opt: RenderOptions, num_samples, samples, cluster_indices,
@@ -982,15 +969,8 @@ def get_samples_from_voxels(tree_view: TreeView, cam: Camera, opt: RenderOptions
 def get_samples_from_voxels_accel(accel: int, cam: Camera, opt: RenderOptions, num_samples, samples, cluster_indices, grid: ClusterGrid,
                                   split_track=None, sample_track=None, sample_counts=None, tile=None, stream: int = 0, tmax_px=None) -> None:
     """get_samples_from_voxels on the packed accel (no visit marks)."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
-    if tmax_px is not None:
-        get_samples_from_voxels_accel_visit(accel, cam, opt, None, None, num_samples, samples, cluster_indices, grid, split_track, sample_track,
-                                            sample_counts, tile, stream, tmax_px)
-        return
-    _check(lib().mnv_get_samples_from_voxels_accel(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), _ptr(split_track),
-                                                   _ptr(sample_track), _ptr(sample_counts), _ptr(num_samples), _ptr(samples),
-                                                   int(samples.shape[-1]), _ptr(cluster_indices), C.byref(grid), C.c_void_p(stream)))
+    get_samples_from_voxels_accel_visit(accel, cam, opt, None, None, num_samples, samples, cluster_indices, grid, split_track, sample_track,
+                                        sample_counts, tile, stream, tmax_px)
 
 
 def render_nerf_results(tree_view: TreeView, cam: Camera, opt: RenderOptions, sample_values, z_vals, offsets, rgba=None,
@@ -1009,18 +989,11 @@ def render_guided_fused(accel: int, cam: Camera, opt: RenderOptions, mlp: "Mlp",
     """The guided-sampling frame as one kernel (mnv_render_guided_fused[_track]).  `sample_counter`: optional device int64 tensor,
     incremented by the number of network evaluations; trackers / visit marks as in render_voxels_accel_visit.  tmax_px: the depth
     attachment of the reference's offscreen == false frame (the image under the volume has weight 0 in that frame: not an input)."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
+    rect, inputs = _accel_frame(cam, tile, rgba, rgba8, tmax_px)
     _fused_defaults(accel)
-    inputs = _frame_inputs(tmax_px, None, tile[2] * tile[3])
-    if inputs is not None:
-        _check(lib().mnv_render_guided_fused_track_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), C.byref(inputs), mlp._h, C.byref(grid),
-                                                      _ptr(rgba), _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited),
-                                                      _ptr(parent), _ptr(sample_counter), C.c_void_p(stream)))
-        return
-    _check(lib().mnv_render_guided_fused_track(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), mlp._h, C.byref(grid), _ptr(rgba),
-                                               _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent),
-                                               _ptr(sample_counter), C.c_void_p(stream)))
+    _check(lib().mnv_render_guided_fused_track_ex(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), rect, inputs, mlp._h, C.byref(grid), _ptr(rgba),
+                                                  _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited), _ptr(parent),
+                                                  _ptr(sample_counter), C.c_void_p(stream)))
 
 
 def render_guided_fused_part(accel: int, cam: Camera, opt: RenderOptions, mlp: "Mlp", grid: ClusterGrid, part, tile=None, rgba=None, rgba8=None,
@@ -1028,19 +1001,11 @@ def render_guided_fused_part(accel: int, cam: Camera, opt: RenderOptions, mlp: "
                              parent=None) -> None:
     """One rank's macro tiles of the fused guided-sampling frame (part = (rank, world, tile_w, tile_h[, root_period])); with trackers /
     visit marks: mnv_render_guided_fused_track_part (rows in the compact tile order of the pixels)."""
-    if tile is None:
-        tile = (0, 0, cam.width, cam.height)
-    px = _pixels(tile, 1, part)
-    _check_out("rgba", rgba, px, "f32")
-    _check_out("rgba8", rgba8, px, "u8")
+    rect, _ = _accel_frame(cam, tile, rgba, rgba8, part=part)
     _fused_defaults(accel)
-    if split_track is not None or sample_track is not None or visited is not None:
-        _check(lib().mnv_render_guided_fused_track_part(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), Partition(*part), mlp._h, C.byref(grid),
-                                                        _ptr(rgba), _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited),
-                                                        _ptr(parent), _ptr(sample_counter), C.c_void_p(stream)))
-        return
-    _check(lib().mnv_render_guided_fused_part(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), Rect(*tile), Partition(*part), mlp._h, C.byref(grid),
-                                              _ptr(rgba), _ptr(rgba8), _ptr(sample_counter), C.c_void_p(stream)))
+    _check(lib().mnv_render_guided_fused_track_part(C.c_void_p(accel), C.byref(cam.c), C.byref(opt), rect, Partition(*part), mlp._h, C.byref(grid),
+                                                    _ptr(rgba), _ptr(rgba8), _ptr(split_track), _ptr(sample_track), _ptr(sample_counts), _ptr(visited),
+                                                    _ptr(parent), _ptr(sample_counter), C.c_void_p(stream)))
 
 
 def tree_edit(child, parent, offset, scale, capacity: int) -> TreeEdit:
@@ -1677,15 +1642,10 @@ def render_voxels_accel_batch(accel: int, cams, opt: RenderOptions, tile=None, p
     if n < 1 or n > MAX_BATCH:
         raise MnvError(MNV_E_INVALID, f"need 1 .. {MAX_BATCH} cameras, got {n}")
     arr = (CameraStruct * n)(*[c.c for c in cams])
-    if tile is None:
-        tile = (0, 0, cams[0].width, cams[0].height)
     p = Partition(0, 1, 0, 0) if part is None else Partition(*part)
-    px = _pixels(tile, n, part)
-    _check_out("rgba", rgba, px, "f32")
-    _check_out("rgba8", rgba8, px, "u8")
+    rect, _ = _accel_frame(cams[0], tile, rgba, rgba8, n_frames=n, part=part)
     with _timed(stream):
-        _check(lib().mnv_render_voxels_accel_batch(C.c_void_p(accel), arr, n, C.byref(opt), Rect(*tile), p, _ptr(rgba), _ptr(rgba8),
-                                                   C.c_void_p(stream)))
+        _check(lib().mnv_render_voxels_accel_batch(C.c_void_p(accel), arr, n, C.byref(opt), rect, p, _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
 
 
 def accel_info(accel: int, coverage: bool = False) -> dict:

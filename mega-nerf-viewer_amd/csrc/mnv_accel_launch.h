@@ -1,10 +1,11 @@
 // mnv_accel_launch.h -- what the translation units of the packed-layout ("accel") path share: the launch block of the march
-// kernels, the row / lookup-grid index helpers, the tracker block of a launch and the functions that cross the unit boundaries.
+// kernels, the row / lookup-grid index helpers, the frame request (AccelFrame) and the functions that cross the unit boundaries.
 //   mnv_accel_build.hip          build kernels, mnv_accel_create / _rebuild / _destroy
 //   mnv_accel_refresh_prune.hip  mnv_accel_refresh (patch after a refinement step), accel_apply_prune (the layout follows a prune)
-//   mnv_march_accel_kernel.h     march_accel_kernel (the tuned march), instantiated by mnv_accel_march.hip
+//   mnv_march_accel_kernel.h     march_accel_kernel (the tuned march)
+//   mnv_march_launch.h           its launcher and MODE choice, shared by the instantiation units mnv_accel_march[_brick|_rays].hip
 //   mnv_guided_fused*.h          the guided-sampling frame as one kernel, instantiated by mnv_accel_fused.hip
-//   mnv_accel_capi.hip           launch planning (launch_accel), tile assembly, the C-ABI entry points
+//   mnv_accel_capi.hip           request validation (render_accel), launch planning (launch_accel), tile assembly, the C-ABI entry points
 #pragma once
 
 #include <type_traits>
@@ -257,20 +258,42 @@ inline bool is_partitioned(mnv_partition part) { return part.world > 1 || (part.
 inline int32_t root_period_of(mnv_partition part) { return part.world > 1 && part.root_period >= 2 ? part.root_period : 0; }
 inline int row_bytes_for(int basis) { return row_bytes_pow2(basis); }
 
-// Refinement trackers of one launch (all device pointers; rows indexed like the pixels).
-struct AccelTrack {
-    float *split_track, *sample_track;
-    const int16_t *sample_counts;
-    int32_t max_depth, max_sample_count;
-    // sample emission (MODE 3) when samples != NULL
-    int16_t *num_samples;
-    float *samples;
-    int16_t *cluster_indices;
-    int32_t max_guided_samples, samples_dim, need_viewdir, appearance_embedding;
-    const mnv_cluster_grid *grid;
-    const FusedGuided *fused;  // non-NULL: guided_fused_kernel instead of the march (no trackers, one frame)
-    int32_t *visited;          // visit marks (tracker / sample modes) ...
-    const int32_t *parent;     // ... closed under the parent words after the march
+// One frame on an accel with its optional extras: what every C-ABI entry point of the packed layout fills in and render_accel
+// (mnv_accel_capi.hip) validates and launches.  All arrays are device pointers; tracker rows are indexed like the pixels.  A
+// default-constructed request is a plain, whole-tile, one-camera, offscreen frame.
+struct AccelFrame {
+    // family of the entry point: which arguments it must be given, and the wording of its null-argument errors
+    enum Entry { kPlain, kTracked, kSamples, kFused, kRays };
+    Entry entry = kPlain;
+    const mnv_accel *accel = nullptr;
+    const mnv_render_options *opt = nullptr;
+    hipStream_t stream = nullptr;
+    const mnv_camera *cams = nullptr;  // [n_cams], same image size
+    int32_t n_cams = 1;
+    mnv_rect tile = {0, 0, 0, 0};
+    mnv_partition part = {0, 1, 0, 0, 0};
+    float *rgba = nullptr;
+    uint8_t *rgba8 = nullptr;
+    mnv_frame_inputs inputs = {nullptr, nullptr};  // offscreen == false: per-pixel ray limit and the image under the volume
+    const float *xform = nullptr;  // offset[3] + scale[3] of the caller's tree view when they may differ from the ones the accel was built with
+    // refinement trackers; visit marks (tracker / sample modes), closed under the parent words after the march
+    float *split_track = nullptr, *sample_track = nullptr;
+    const int16_t *sample_counts = nullptr;
+    int32_t *visited = nullptr;
+    const int32_t *parent = nullptr;
+    // kSamples: sample emission (MODE 3) instead of an image; kSamples / kFused: the cluster grid
+    int16_t *num_samples = nullptr;
+    float *samples = nullptr;
+    int32_t samples_dim = 0;
+    int16_t *cluster_indices = nullptr;
+    const mnv_cluster_grid *grid = nullptr;
+    // kFused: guided_fused*_kernel instead of the march (one frame); render_accel derives `fused` from the network
+    const mnv_mlp *mlp = nullptr;
+    unsigned long long *sample_counter = nullptr;
+    const FusedGuided *fused = nullptr;
+    // kRays: the caller's rays, world space, [ray_height][ray_width][3] each (one frame, no partition, no trackers; `cams` is unused)
+    const float *ray_origins = nullptr, *ray_dirs = nullptr;
+    int32_t ray_width = 0, ray_height = 0;
 };
 
 constexpr int kUnsupportedBasis = -1000;  // not a hipError_t

@@ -1,0 +1,43 @@
+// mnv_march_launch.h -- the one launcher of march_accel_kernel and the choice of its MODE, for the units that instantiate the kernel
+// (mnv_accel_march.hip: node words; mnv_accel_march_brick.hip: inline cell words / brick records; mnv_accel_march_rays.hip: ray lists).
+// A unit instantiates what its calls of launch_march_mode name: the BASIS values of its switch times the MODEs below.
+#pragma once
+
+#include "mnv_march_accel_kernel.h"
+
+namespace mnv {
+
+template <int BASIS, int MODE, bool BRICK, bool RAYS>
+static int launch_march_kernel(const LaunchBlock<RAYS> &K, int n_blocks, size_t lds_bytes, hipStream_t stream) {
+    constexpr int BLOCK = 256;
+    auto kern = march_accel_kernel<BASIS, BLOCK, MODE, BRICK, RAYS>;
+    if (lds_bytes > 65536) {  // diagnostics only (MNV_LDS_LEVEL=5); the attribute is per device, so set it on every such launch
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(BLOCK), lds_bytes, stream, K);
+    return (int)hipGetLastError();
+}
+
+// MODE of a launch: statistics -> 1, emitted samples -> 3, trackers / visit marks -> 2, depth image -> 5, fast colour math -> 4, else 0.
+// Modes 1, 3 and 5 exist for BASIS 9 only: 1 is the diagnostics build (MNV_STATS / MNV_ABLATE ...) of the headline variant, 3 and 5 read
+// no colour rows, so one instantiation serves every row format.  Ray lists have the plain march and the depth image.
+template <int BASIS, bool BRICK, bool RAYS>
+static int launch_march_mode(const LaunchBlock<RAYS> &K, int n_blocks, size_t lds_bytes, hipStream_t stream) {
+    if constexpr (!RAYS) {
+        if constexpr (BASIS == 9) {
+            if (K.stats) return launch_march_kernel<BASIS, 1, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+            if (K.samples) return launch_march_kernel<BASIS, 3, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+        }
+        if (K.split_track || K.sample_track || K.visited) return launch_march_kernel<BASIS, 2, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+    }
+    if constexpr (BASIS == 9) {
+        if (K.P.render_depth) return launch_march_kernel<BASIS, 5, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+    }
+    if constexpr (!RAYS && BASIS >= 1) {
+        if (K.fast_colour) return launch_march_kernel<BASIS, 4, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+    }
+    return launch_march_kernel<BASIS, 0, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+}
+
+}  // namespace mnv
