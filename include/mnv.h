@@ -825,6 +825,86 @@ int mnv_obj_read(const char *path, const float *default_color, float *vert, int6
 int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv_camera *cam, const mnv_render_options *opt, mnv_rect tile,
                       const mnv_frame_inputs *under, float *tmax_px_out, uint8_t *rgba8_out, void *hip_stream);
 
+/* ------------------------------------------------ geometry out of a tree: point queries, an iso-surface of the density, an OBJ writer
+ * mnv_accel_sample_points: "what is the tree at this point" for n world-space points (device float [n][3]).  Each output is a device array
+ * of n elements and may be NULL: voxel = chunk * 8 + child of the leaf, depth = its depth (the root chunk's voxels have depth 1), sigma =
+ * its binary16 density as binary32.  The leaf is the one query_single_from_root (rt_core.cuh:125-150) reaches, in binary32 without
+ * contraction: u_a = offset[a] + p_a * scale[a], clamped to [0, 1 - 1e-6f] (max(min(u, 1 - 1e-6f), 0)); per level u_a *= 2, the child bit is
+ * floorf(u_a) (x most significant), u_a -= the bit.  A point with a non-finite coordinate gives voxel = -1, depth = 0, sigma = 0.
+ * Asynchronous on hip_stream.  The descent is bounded by the accel's depth (at most 23 levels) and a child link outside [1, capacity) is not
+ * followed: such points answer voxel = -1, depth = 0, sigma = 0 too, and mnv_extract_surface reports MNV_E_INVALID for such a tree.
+ * MNV_E_INVALID: null accel or points with n > 0, negative n. */
+int mnv_accel_sample_points(const mnv_accel *accel, const float *points, int64_t n, int32_t *voxel_out, int32_t *depth_out, float *sigma_out,
+                            void *hip_stream);
+
+/*
+ * mnv_extract_surface: the iso-surface of the density as an indexed triangle mesh with a normal and a colour per vertex ("surface nets":
+ * one vertex per sign-changing dual cell, no case table), built on the device in a canonical order: the same accel, level, iso and
+ * colour switch give the same bytes whatever the hardware schedule.  Waits for hip_stream (it sizes the outputs).
+ *
+ * Contract (binary32, operations in the stated order, no contraction, correctly rounded division and square root), n = 2^level:
+ *   Samples.  S(i, j, k), 0 <= i, j, k < n, is the sigma of the leaf the descent of mnv_accel_sample_points reaches from the TREE-space point
+ *     ((i + 0.5) / n, (j + 0.5) / n, (k + 0.5) / n) (exact in binary32; in a tree deeper than `level` the point is a corner of finer voxels
+ *     and the descent's floor rule picks the one with the larger coordinates).  Sigma bits that are not finite read as 0.  A sample is
+ *     inside when S > iso.
+ *   Cells.  Dual cell c = (cx, cy, cz) exists for 0 <= c_a <= n - 2 and spans the samples c + (dx, dy, dz); corner index 4 dx + 2 dy + dz.  A
+ *     cell is active when its eight corners are neither all inside nor all outside.  Nothing is capped at the tree's boundary: the surface
+ *     is open where the density reaches the outermost sample layer.
+ *   Vertex position.  One vertex per active cell.  The 12 cell edges in the order axis a = 0, 1, 2; within an axis ascending lower corner
+ *     k0; upper corner k1 = k0 with the bit of axis a set (axis 0: bit 4, axis 1: bit 2, axis 2: bit 1).  Every edge whose ends differ in
+ *     side crosses at t = (iso - S[k0]) / (S[k1] - S[k0]): the point is corner k0's offset (dx, dy, dz) with component a replaced by t.
+ *     local = (the sum of the crossing points in that order, per component, starting from 0) / (their count as a float);
+ *     u_a = (((float)c_a + local_a) + 0.5f) * 2^-level; world position (u_a - offset[a]) / scale[a].
+ *   Normal.  g_a = (((S[k] summed over the four corners with the bit of axis a set, ascending k, left to right)) - (the same over the four
+ *     with it clear); w_a = -(g_a * scale[a]); len = sqrtf((w0*w0 + w1*w1) + w2*w2); normal = w / len, or (0, 0, 1) when len is 0 or not finite.
+ *   Colour (MNV_EXTRACT_COLOUR; otherwise (1, 1, 1)).  The leaf of the corner with the largest S (the first in corner order on ties) seen
+ *     along d = -normal, as the march colours a sample: SH rows 1.f / (1.f + expf(-tmp)) per channel with tmp over the whole basis of d
+ *     (rt_core.cuh:12-68, :257-281; the exact expf of the frames); RGBA rows the three halfs as floats (rt_core.cuh:285-289).  rot_dirs and
+ *     basis_minmax do not enter.  Row formats other than RGBA and SH 1 / 4 / 9 / 16 / 25: MNV_E_UNSUPPORTED.
+ *   Order.  Cells are ordered by brick, then inside the brick: a brick is 8 x 8 x 8 cells, nb = n / 8 bricks per axis, brick index
+ *     (bx * nb + by) * nb + bz, index inside ((cx & 7) * 8 + (cy & 7)) * 8 + (cz & 7).  A vertex's id is the rank of its cell among the
+ *     active cells in that order.
+ *   Faces.  For a cell p and an axis a with (b, c) the next two axes cyclically: if p_b >= 1, p_c >= 1 and the sides of the samples p and
+ *     p + e_a differ, a quad over the cells q0 = p - e_b - e_c, q1 = p - e_c, q2 = p, q3 = p - e_b (all active by construction), in the order
+ *     q0 q1 q2 q3 when sample p is inside and q0 q3 q2 q1 otherwise (the face normal points from inside to outside), written as the
+ *     triangles (0, 1, 2) and (0, 2, 3).  Faces are ordered by owner cell p in the order above, then by axis.
+ * Vertices are 9 floats (position, colour, normal: the mnv_mesh layout), indices uint32, three per triangle.
+ *
+ * MNV_EXTRACT_ALL_BRICKS (diagnostic) visits every brick instead of the ones an empty-space test over the top of the tree keeps; the bytes
+ * are identical.  Device memory beside the outputs is proportional to the number of bricks (100 bytes each: 210 MB at level 10).
+ * MNV_E_INVALID: null argument, level outside 3 .. 10, a NaN iso, unknown flag bits, a tree with a child link outside [1, capacity).
+ * MNV_E_UNSUPPORTED: more than 2^31 - 1 vertices or indices. */
+#define MNV_EXTRACT_COLOUR 1
+#define MNV_EXTRACT_ALL_BRICKS 2
+typedef struct mnv_extract_params {
+    int32_t level; /* 3 .. 10: the sample lattice has 2^level points per axis */
+    float iso;
+    int32_t flags; /* MNV_EXTRACT_* */
+} mnv_extract_params;
+typedef struct mnv_surface mnv_surface;
+/* what the last extraction did: bricks of the lattice, bricks the passes visited, device milliseconds per pass (HIP events on the stream) */
+typedef struct mnv_surface_stats {
+    int64_t bricks, candidate_bricks;
+    float ms_candidates, ms_count, ms_scan, ms_emit, ms_colour, ms_total;
+} mnv_surface_stats;
+int mnv_extract_surface(const mnv_accel *accel, const mnv_extract_params *params, void *hip_stream, mnv_surface **out);
+void mnv_surface_destroy(mnv_surface *s);
+int mnv_surface_counts(const mnv_surface *s, int64_t *n_verts, int64_t *n_indices);
+int mnv_surface_stats_get(const mnv_surface *s, mnv_surface_stats *out);
+/* host copies: vert float [n_verts][9], faces uint32 [n_indices]; either may be NULL; a capacity (in floats / indices) below the size is
+ * MNV_E_INVALID */
+int mnv_surface_download(const mnv_surface *s, float *vert, int64_t cap_floats, uint32_t *faces, int64_t cap_indices);
+/* the device arrays themselves (owned by the surface; NULL when it is empty) */
+int mnv_surface_device(const mnv_surface *s, const float **vert, const uint32_t **faces);
+/* a device-to-device copy as a triangle mesh that mnv_render_meshes and mnv_renderer_add_mesh draw; an empty surface is MNV_E_INVALID */
+int mnv_surface_to_mesh(const mnv_surface *s, int unlit, mnv_mesh **out);
+/* Writes a Wavefront OBJ file on the host: `v x y z r g b` and `vn x y z` per vertex, then `f a//a b//b c//c` (face_size 3), `l a b`
+ * (face_size 2) per primitive; floats as %.9g, so that mnv_obj_read returns the same bits (it forms vertices in order of first use by a
+ * face: a vertex no face names is not read back).  faces NULL with n_indices 0 writes the vertices alone.  MNV_E_INVALID: null path or
+ * vertices with n_verts > 0, a face_size other than 2 or 3, an index count that is no multiple of it, an index >= n_verts; MNV_E_IO: the file
+ * cannot be written. */
+int mnv_obj_write(const char *path, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int32_t face_size);
+
 /* ------------------------------------------------ anti-aliased frames: jittered sub-frames in one launch, filtered resolve
  * Every march kernel sends one ray through each pixel centre.  A supersampled frame is K frames of the SAME camera whose principal point is
  * shifted by a sub-pixel offset (mnv_camera carries cx, cy per camera, and mnv_render_voxels_accel_batch marches up to MNV_MAX_BATCH cameras

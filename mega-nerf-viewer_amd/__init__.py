@@ -196,6 +196,23 @@ class SynthShellParams(C.Structure):
     ]
 
 
+class ExtractParams(C.Structure):
+    """mnv_extract_params"""
+    _fields_ = [("level", C.c_int32), ("iso", C.c_float), ("flags", C.c_int32)]
+
+
+class SurfaceStats(C.Structure):
+    """mnv_surface_stats: bricks of the lattice, bricks the passes visited, device milliseconds per pass."""
+    _fields_ = [("bricks", C.c_int64), ("candidate_bricks", C.c_int64), ("ms_candidates", C.c_float), ("ms_count", C.c_float), ("ms_scan", C.c_float),
+                ("ms_emit", C.c_float), ("ms_colour", C.c_float), ("ms_total", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+EXTRACT_COLOUR, EXTRACT_ALL_BRICKS = 1, 2
+
+
 # every symbol include/mnv.h declares (tests/test_capi_symbols.py checks the export list)
 _SIGNATURES = {
     "mnv_version": (C.c_int, []),
@@ -380,6 +397,15 @@ _SIGNATURES = {
     "mnv_pnm_read": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mnv_renderer_set_target": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mnv_renderer_slot_metrics": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FrameMetricValues)]),
+    "mnv_accel_sample_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_extract_surface": (C.c_int, [C.c_void_p, C.POINTER(ExtractParams), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mnv_surface_destroy": (None, [C.c_void_p]),
+    "mnv_surface_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mnv_surface_stats_get": (C.c_int, [C.c_void_p, C.POINTER(SurfaceStats)]),
+    "mnv_surface_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "mnv_surface_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "mnv_surface_to_mesh": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "mnv_obj_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1467,6 +1493,97 @@ def render_meshes(meshes, cam: Camera, opt: RenderOptions, tile=None, under=None
     _check(lib().mnv_render_meshes(handles, len(meshes), C.byref(cam.c), C.byref(opt), Rect(*tile), C.byref(inputs) if inputs is not None else None,
                                    tmax_px.data_ptr(), rgba8.data_ptr(), C.c_void_p(stream)))
     return tmax_px, rgba8
+
+
+def obj_write(path: str, vert, faces=None, face_size: int = 3) -> None:
+    """mnv_obj_write: vert float32 [n, 9] (position, colour, normal) and faces uint32 [m, face_size] (or None) as a Wavefront OBJ file whose
+    floats obj_read returns bit for bit."""
+    v = np.ascontiguousarray(vert, np.float32).reshape(-1, 9)
+    f = None if faces is None else np.ascontiguousarray(faces, np.uint32).reshape(-1)
+    _check(lib().mnv_obj_write(os.fsencode(path), v.ctypes.data if v.size else None, v.shape[0], f.ctypes.data if f is not None and f.size else None,
+                               0 if f is None else f.size, int(face_size)))
+
+
+def sample_points(accel: int, points, voxel: bool = True, depth: bool = True, sigma: bool = True, stream: int = 0):
+    """mnv_accel_sample_points: the leaf under each world-space point of a float32 device tensor [n, 3].  Returns (voxel int32 [n], depth
+    int32 [n], sigma float32 [n]) device tensors; an output that is switched off is None (and NULL in the call).  A point with a
+    non-finite coordinate answers (-1, 0, 0)."""
+    import torch
+
+    if not points.is_cuda or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3:
+        raise MnvError(MNV_E_INVALID, "points must be a contiguous float32 device tensor [n, 3]")
+    n = points.shape[0]
+    vo = torch.empty(n, dtype=torch.int32, device="cuda") if voxel else None
+    de = torch.empty(n, dtype=torch.int32, device="cuda") if depth else None
+    sg = torch.empty(n, dtype=torch.float32, device="cuda") if sigma else None
+    _check(lib().mnv_accel_sample_points(C.c_void_p(accel), points.data_ptr(), n, _ptr(vo), _ptr(de), _ptr(sg), C.c_void_p(stream)))
+    return vo, de, sg
+
+
+class Surface:
+    """mnv_surface: an extracted iso-surface on the device (extract_surface)."""
+
+    def __init__(self, handle: int):
+        self._h = C.c_void_p(handle)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                lib().mnv_surface_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def counts(self):
+        nv, ni = C.c_int64(0), C.c_int64(0)
+        _check(lib().mnv_surface_counts(self._h, C.byref(nv), C.byref(ni)))
+        return nv.value, ni.value
+
+    def stats(self) -> dict:
+        st = SurfaceStats()
+        _check(lib().mnv_surface_stats_get(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def vertices(self) -> np.ndarray:
+        """float32 [n_verts, 9] on the host: position, colour, normal"""
+        nv, _ = self.counts()
+        out = np.empty((nv, 9), np.float32)
+        _check(lib().mnv_surface_download(self._h, out.ctypes.data if nv else None, out.size, None, 0))
+        return out
+
+    def faces(self) -> np.ndarray:
+        """uint32 [n_triangles, 3] on the host"""
+        _, ni = self.counts()
+        out = np.empty((ni // 3, 3), np.uint32)
+        _check(lib().mnv_surface_download(self._h, None, 0, out.ctypes.data if ni else None, out.size))
+        return out
+
+    def device_pointers(self):
+        """(vertices, indices) device addresses of the surface's own arrays (0 when it is empty); they live as long as the surface"""
+        v, f = C.c_void_p(), C.c_void_p()
+        _check(lib().mnv_surface_device(self._h, C.byref(v), C.byref(f)))
+        return v.value or 0, f.value or 0
+
+    def to_mesh(self, unlit: bool = False) -> "Mesh":
+        """A device-to-device copy as a Mesh that render_meshes and Renderer.add_mesh draw."""
+        h = C.c_void_p()
+        _check(lib().mnv_surface_to_mesh(self._h, int(bool(unlit)), C.byref(h)))
+        m = Mesh.__new__(Mesh)
+        m._h = h
+        return m
+
+    def save_obj(self, path: str) -> None:
+        obj_write(path, self.vertices(), self.faces(), 3)
+
+
+def extract_surface(accel: int, level: int, iso: float, colour: bool = True, all_bricks: bool = False, stream: int = 0) -> Surface:
+    """mnv_extract_surface: the iso-surface of the density on a lattice of 2^level samples per axis (3 <= level <= 10) as an indexed
+    triangle mesh with a normal and a colour per vertex; include/mnv.h states every value.  all_bricks switches the empty-space skip off
+    (same bytes)."""
+    p = ExtractParams(int(level), float(iso), (EXTRACT_COLOUR if colour else 0) | (EXTRACT_ALL_BRICKS if all_bricks else 0))
+    h = C.c_void_p()
+    _check(lib().mnv_extract_surface(C.c_void_p(accel), C.byref(p), C.c_void_p(stream), C.byref(h)))
+    return Surface(h.value)
 
 
 MAX_BATCH = 64

@@ -31,4 +31,7 @@ int render_accel_for_tree(const mnv_accel *accel, const mnv_tree_view *tree, con
                           const mnv_frame_inputs *inputs, float *rgba_out, uint8_t *rgba8_out, float *split_track, float *sample_track,
                           hipStream_t stream);
 
+// a mesh handle over device arrays the caller allocated (hipMalloc) and hands over (mnv_mesh.hip)
+int mesh_adopt_device(float *vert, int64_t n_verts, uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit, mnv_mesh **out);
+
 }  // namespace mnv

@@ -423,6 +423,22 @@ int validate_mesh_arrays(const float *vert, int64_t n_verts, const uint32_t *fac
 
 }  // namespace
 
+// A triangle / line / point mesh over device arrays the caller allocated with hipMalloc and hands over (mnv_surface_to_mesh): the handle
+// owns them from a MNV_OK on.  The indices are the producer's and are not read back for validation.
+int mnv::mesh_adopt_device(float *vert, int64_t n_verts, uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit, mnv_mesh **out) {
+    if (!out || !vert || n_verts <= 0 || face_size < 1 || face_size > 3 || (faces ? n_indices <= 0 || n_indices % face_size != 0 : n_indices != 0) ||
+        n_verts > (int64_t)UINT32_MAX)
+        return set_error(MNV_E_INVALID, "mnv_mesh: bad device arrays");
+    mnv_mesh *m = new mnv_mesh();
+    m->vert = vert, m->faces = faces;
+    m->n_verts = n_verts;
+    m->n_prims = faces ? n_indices / face_size : n_verts / face_size;
+    m->face_size = face_size;
+    m->unlit = unlit != 0;
+    *out = m;
+    return MNV_OK;
+}
+
 extern "C" {
 
 static int upload_mesh(mnv_mesh *m, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit) {

@@ -501,6 +501,14 @@ int mnv_obj_read(const char *path, const float *default_color, float *vert, int6
     });
 }
 
+int mnv_obj_write(const char *path, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int32_t face_size) {
+    if (!path) return mnv::set_error(MNV_E_INVALID, "mnv_obj_write: null path");
+    return guarded([&] {
+        viewer::write_obj(path, vert, n_verts, faces, n_indices, face_size);
+        return MNV_OK;
+    });
+}
+
 int mnv_renderer_add_mesh(mnv_renderer *r, const mnv_mesh *mesh) {
     if (!r || !mesh) return mnv::set_error(MNV_E_INVALID, "null argument");
     r->rend.meshes.push_back(mesh);

@@ -41,6 +41,11 @@
 //   --mesh PATH[,unlit]   draw a Wavefront OBJ file under the volume (viewer::Mesh::load_obj, VolumeRenderer::meshes); repeatable.
 //                    --mesh_color r,g,b (vertices without a colour; default white), --mesh_translate x,y,z, --mesh_rotate x,y,z
 //                    (axis-angle) and --mesh_scale s apply to the mesh named before them.  Refused with --gpus, as --grid is.
+//   --extract_mesh OUT.obj   write the iso-surface of the density as a Wavefront OBJ file with a colour and a normal per vertex
+//                    (N3Tree::extract_surface, mnv_extract_surface: --extract_level L, default 7, the lattice has 2^L samples per axis;
+//                    --extract_iso S, default 10, the density the surface follows).  Frames rendered by the same run draw the mesh under
+//                    the volume like --mesh (--extract_unlit: with its vertex colours alone); --frames 0 writes the file only.  Refused
+//                    with --gpus and a projection other than pinhole, as --mesh is.
 //   --target PREFIX  score frame f against PREFIX_%04d.ppm (the P6 files --out writes) on the device (VolumeRenderer::set_target,
 //                    mnv_frame_metrics with MNV_METRIC_QUANTISED: the file --out would write against the file that was read) and print
 //                    "frame F: psnr ..." when the frame is collected, then the means over the frames.  --ssim adds SSIM (11 x 11 Gaussian
@@ -102,7 +107,7 @@ Args parse(int argc, char **argv) {
         {"s", "step_size"}, {"e", "stop_thresh"}, {"a", "sigma_thresh"}, {"c", "max_tree_capacity"}, {"x", "split_batch_size"},
         {"n", "nerf_batch_size"}, {"v", "samples_per_voxel"}, {"b", "bounds_only"}, {"y", "appearance_embedding"},
         {"z", "max_guided_samples"}, {"w", "width"}, {"h", "height"}};
-    static const char *flags[] = {"bounds_only", "raw", "help", "use_splitting", "use_guided_sampling", "guided_in_flight", "ssim"};
+    static const char *flags[] = {"bounds_only", "raw", "help", "use_splitting", "use_guided_sampling", "guided_in_flight", "ssim", "extract_unlit"};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string t = argv[i];
@@ -134,6 +139,7 @@ void usage() {
               "                  [--origin x,y,z] [--world_up x,y,z] [-b] [--grid D] [--out PREFIX] [--raw] [--frames N] [--orbit DEG] [--gpu ID]\n"
               "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--projection pinhole|ortho|equirect] [--gpus N [--reserve_cus R] [--root_period M]]\n"
               "                  [--mesh FILE.obj[,unlit] [--mesh_color r,g,b] [--mesh_translate x,y,z] [--mesh_rotate x,y,z] [--mesh_scale s]]...\n"
+              "                  [--extract_mesh OUT.obj [--extract_level L] [--extract_iso S] [--extract_unlit]]   the density's iso-surface as a mesh\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
               "                   0 = excluded): PSNR and, with --ssim, SSIM per frame and their means; not with --gpus.  Out of scope: pose\n"
               "                   lists (poses stay --orbit or the API) and LPIPS (it needs a network this repository does not have)\n"
@@ -605,14 +611,15 @@ int main(int argc, char **argv) {
         }
         if (args.has("gpus") && args.has("grid")) throw std::runtime_error("--grid draws on one GPU: it cannot be combined with --gpus");
         if (args.has("gpus") && !args.mesh_flags.empty()) throw std::runtime_error("--mesh draws on one GPU: it cannot be combined with --gpus");
+        if (args.has("gpus") && args.has("extract_mesh")) throw std::runtime_error("--extract_mesh extracts on one GPU: it cannot be combined with --gpus");
         const std::string aa_filter = args.get("aa_filter", "tent");
         if (aa_filter != "box" && aa_filter != "tent") throw std::runtime_error("--aa_filter is box or tent");
         if (args.has("gpus") && args.l("aa", 1) != 1)
             throw std::runtime_error("--aa resolves its sub-frames on one GPU: it cannot be combined with --gpus");
         const std::string projection = args.get("projection", "pinhole");
         if (projection != "pinhole" && projection != "ortho" && projection != "equirect") throw std::runtime_error("--projection is pinhole, ortho or equirect");
-        if (projection != "pinhole" && (args.has("gpus") || args.has("grid") || !args.mesh_flags.empty() || args.l("aa", 1) != 1))
-            throw std::runtime_error("--projection " + projection + " marches a ray list: it cannot be combined with --gpus, --grid, --mesh or --aa other than 1");
+        if (projection != "pinhole" && (args.has("gpus") || args.has("grid") || !args.mesh_flags.empty() || args.has("extract_mesh") || args.l("aa", 1) != 1))
+            throw std::runtime_error("--projection " + projection + " marches a ray list: it cannot be combined with --gpus, --grid, --mesh, --extract_mesh or --aa other than 1");
         if (args.has("gpus") && (args.has("target") || args.has("target_mask") || args.has("ssim")))
             throw std::runtime_error("--target scores the frames of one GPU: it cannot be combined with --gpus");
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
@@ -637,6 +644,19 @@ int main(int argc, char **argv) {
         rend.resize(width, height);
         std::vector<viewer::Mesh> meshes;
         load_meshes(args, meshes, rend);
+        const long frames = args.l("frames", 1);
+        viewer::Mesh extracted;  // --extract_mesh: written, then drawn under the volume by the frames of this run
+        if (args.has("extract_mesh")) {
+            if (tree.N <= 0) throw std::runtime_error("--extract_mesh needs a tree (N > 0)");
+            extracted = tree.extract_surface((int)args.l("extract_level", 7), args.f("extract_iso", 10.f), true);
+            extracted.save_obj(args.get("extract_mesh", ""));
+            std::printf("extract_mesh: %zu vertices, %zu triangles -> %s\n", extracted.vert.size() / 9, extracted.faces.size() / 3, args.get("extract_mesh", "").c_str());
+            if (frames > 0 && !extracted.faces.empty()) {
+                extracted.unlit = args.has("extract_unlit");
+                extracted.update();
+                rend.meshes.push_back(extracted.handle());
+            }
+        }
         if (args.has("model_path")) {  // main.cpp:585-589
             rend.load_model(args.get("model_path", ""));
             rend.options.use_splitting = args.has("use_splitting");
@@ -646,7 +666,6 @@ int main(int argc, char **argv) {
             rend.seed = (uint64_t)args.l("seed", 0);
         }
 
-        const long frames = args.l("frames", 1);
         const double orbit = args.f("orbit", 0.f) * M_PI / 180.0;
         const std::string out = args.get("out", "");
         std::vector<float> rgba;
@@ -742,7 +761,7 @@ int main(int argc, char **argv) {
             tree.save_npz(args.get("save_tree", ""));
         }
         std::printf("%s: %ld frame(s) %dx%d, %.3f ms/frame wall (%d in flight%s), %.1f Mrays/s\n", rend.get_backend(), frames,
-                    width, height, wall_ms / frames, refine && !rend.overlaps_next() ? 1 : rend.frames_in_flight, out.empty() ? "" : ", incl. download + file output",
+                    width, height, wall_ms / std::max<long>(frames, 1), refine && !rend.overlaps_next() ? 1 : rend.frames_in_flight, out.empty() ? "" : ", incl. download + file output",
                     wall_ms > 0 ? (double)width * height * frames / wall_ms / 1e3 : 0.0);
         return 0;
     } catch (const std::exception &e) {

@@ -2,6 +2,7 @@
 #include "mesh.hpp"
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -211,6 +212,40 @@ Mesh Mesh::load_obj(const std::string &path, const float color[3], bool unlit) {
         m.faces = segs;
     }
     return m;
+}
+
+void write_obj(const std::string &path, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int face_size) {
+    if (n_verts < 0 || (n_verts > 0 && !vert)) throw StatusError(MNV_E_INVALID, "mnv_obj_write: null vertex array");
+    if (n_indices < 0 || (n_indices > 0 && !faces)) throw StatusError(MNV_E_INVALID, "mnv_obj_write: null index array with a non-zero count");
+    if (n_indices > 0 && face_size != 2 && face_size != 3) throw StatusError(MNV_E_INVALID, "mnv_obj_write: face_size must be 2 (lines) or 3 (triangles)");
+    if (n_indices > 0 && n_indices % face_size != 0) throw StatusError(MNV_E_INVALID, "mnv_obj_write: the index count must be a multiple of face_size");
+    for (int64_t i = 0; i < n_indices; ++i)
+        if ((int64_t)faces[i] >= n_verts) throw StatusError(MNV_E_INVALID, "mnv_obj_write: a face index >= n_verts");
+    std::FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::runtime_error(path + ": cannot open for writing");
+    bool ok = true;
+    for (int64_t i = 0; i < n_verts && ok; ++i) {
+        const float *v = vert + i * 9;
+        ok = std::fprintf(f, "v %.9g %.9g %.9g %.9g %.9g %.9g\n", v[0], v[1], v[2], v[3], v[4], v[5]) > 0;
+    }
+    for (int64_t i = 0; i < n_verts && ok; ++i) {
+        const float *v = vert + i * 9;
+        ok = std::fprintf(f, "vn %.9g %.9g %.9g\n", v[6], v[7], v[8]) > 0;
+    }
+    for (int64_t i = 0; i + face_size <= n_indices && ok; i += face_size) {
+        if (face_size == 3) {
+            const unsigned long a = faces[i] + 1ul, b = faces[i + 1] + 1ul, c = faces[i + 2] + 1ul;
+            ok = std::fprintf(f, "f %lu//%lu %lu//%lu %lu//%lu\n", a, a, b, b, c, c) > 0;
+        } else {
+            ok = std::fprintf(f, "l %lu %lu\n", faces[i] + 1ul, faces[i + 1] + 1ul) > 0;
+        }
+    }
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) throw std::runtime_error(path + ": write failed");
+}
+
+void Mesh::save_obj(const std::string &path) const {
+    write_obj(path, vert.data(), (int64_t)(vert.size() / 9), faces.empty() ? nullptr : faces.data(), (int64_t)faces.size(), face_size);
 }
 
 }  // namespace viewer

@@ -41,6 +41,8 @@ struct Mesh {
     // A vertex without r g b takes `color`.  A file with both `f` and `l`, an index outside the file, a malformed number, a face with
     // fewer than three corners or a polyline with fewer than two: std::runtime_error naming "line N".
     static Mesh load_obj(const std::string &path, const float color[3] = nullptr, bool unlit = false);
+    // The vertex and index lists as a Wavefront OBJ file (write_obj below); face_size 2 or 3.
+    void save_obj(const std::string &path) const;
 
     // Vertex list: position, colour, normal
     std::vector<float> vert;
@@ -58,5 +60,10 @@ struct Mesh {
 private:
     mnv_mesh *handle_ = nullptr;
 };
+
+// mnv_obj_write (include/mnv.h): `v x y z r g b` and `vn x y z` per vertex, then `f a//a b//b c//c` or `l a b` per primitive, every float as
+// %.9g (load_obj reads the same bits back).  StatusError(MNV_E_INVALID) for arrays that are no mesh, std::runtime_error when the file cannot
+// be written.
+void write_obj(const std::string &path, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int face_size);
 
 }  // namespace viewer

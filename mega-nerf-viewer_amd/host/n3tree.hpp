@@ -18,6 +18,7 @@
 
 #include "../../include/mnv.h"
 #include "data_format.hpp"
+#include "mesh.hpp"
 
 namespace viewer {
 
@@ -94,6 +95,11 @@ struct N3Tree {
     std::vector<float> gen_wireframe(int max_depth = 100000) const;
     int64_t gen_wireframe_floats(int max_depth = 100000) const;
     void gen_wireframe_into(int max_depth, float *out) const;
+
+    // The iso-surface of the density as a triangle mesh with per-vertex colour and normal (mnv_extract_surface, include/mnv.h: the
+    // contract, level 3 .. 10), extracted on the device from the packed accel and downloaded; colour == false leaves the vertices white.
+    // Needs move_to_device (StatusError(MNV_E_INVALID) before).  The mesh has no device handle yet: update() uploads it for drawing.
+    Mesh extract_surface(int level, float iso, bool colour = true, void *hip_stream = nullptr) const;
 
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;
