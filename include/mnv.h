@@ -1137,7 +1137,7 @@ mnv_render_options *mnv_renderer_options(mnv_renderer *r);
 /* VolumeRenderer::camera pose and focal length (fx <= 0 keeps the current one; fy <= 0 means fy = fx) */
 int mnv_renderer_set_camera(mnv_renderer *r, float fx, float fy, const float center[3], const float v_back[3],
                             const float v_world_up[3]);
-/* seed of the sample jitter (torch::rand in the reference); accel_rebuild_after < 0 keeps the default */
+/* seed of the sample jitter (torch::rand in the reference); accel_rebuild_after is not read: the accel follows every edit */
 int mnv_renderer_set_seed(mnv_renderer *r, uint64_t seed, int32_t accel_rebuild_after);
 int mnv_renderer_render(mnv_renderer *r, mnv_renderer_stats *stats /* may be NULL */);
 /* wait for the frame and copy it to host buffers [height][width][4] (either may be NULL) */

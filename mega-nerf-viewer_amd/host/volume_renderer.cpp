@@ -80,6 +80,36 @@ struct DeviceBuffer {
     }
 };
 
+// What the next render() does, decided from the renderer's state and options alone (VolumeRenderer::plan()).  render() issues exactly
+// this; overlaps_next() / next_slot() report it.
+struct VolumeRenderer::FramePlan {
+    enum Kind {
+        BACKGROUND,        // no tree: the background (over the meshes) on slot 0
+        PLAIN,             // the march on the packed accel, beside the frames in flight
+        GUIDED_IN_FLIGHT,  // the fused guided kernel with nothing but the picture wanted from it, beside the frames in flight
+        TREE,              // alone on slot 0, may edit the tree: march() names the entry points
+        RANKS,             // this rank's share of a frame of several ranks (set_ranks), alone on slot 0
+        AA,                // aa_samples jittered sub-frames and their resolve
+        PROJECTED          // the ray list of an orthographic / equirectangular camera
+    } kind = BACKGROUND;
+    bool overlaps = false;   // takes the next slot beside the frames in flight; false: waits for them and runs alone on slot 0
+    bool show_grid = false;  // draws its own inputs: the grid pass, ...
+    bool draws_inputs = false;  // ... the visible meshes, or both
+    bool refines = false;    // a TREE / RANKS frame with a model and use_splitting / use_guided_sampling: trackers, visit marks, tree edits
+    // TREE: which march.  Whether the frame takes visit marks is known only once the prelude has read camera.has_changed(), a latch that
+    // frames which pass their refusals alone may consume; marks on the packed layout need the tree's parent array, a marks frame of a
+    // tree without one reads the reference layout.
+    bool guided = false, fused = false, packed = false, has_parent = false;
+    enum March { FUSED_GUIDED, FOUR_STEP_GUIDED, TRACKED_ACCEL, REFERENCE_LAYOUT };
+    bool on_accel(bool track_visit) const { return packed && (!track_visit || has_parent); }  // (FOUR_STEP_GUIDED: its sample march)
+    March march(bool track_visit) const {
+        if (guided) return fused && on_accel(track_visit) ? FUSED_GUIDED : FOUR_STEP_GUIDED;
+        return on_accel(track_visit) ? TRACKED_ACCEL : REFERENCE_LAYOUT;
+    }
+    const char *refusal = nullptr;   // refused (nothing else of the plan is filled in) ...
+    bool refusal_is_status = false;  // ... with StatusError(MNV_E_INVALID); false: std::runtime_error
+};
+
 struct VolumeRenderer::Impl {
     N3Tree *tree = nullptr;
     long max_tree_capacity = 0;
@@ -106,7 +136,7 @@ struct VolumeRenderer::Impl {
     int cur = 0;            // slot of the most recent render()
     bool overlapped = false;  // plain frames may still be running on slots other than 0
     bool tree_stream_dirty = false;  // slot 0's stream may still be editing the tree / accel (a frame other than a plain one ran last)
-    hipStream_t stream = nullptr;  // = slots[0].stream: refinement, tree upload, accel rebuild
+    hipStream_t stream = nullptr;  // = slots[0].stream: refinement, tree upload, accel patches
     float *rgba = nullptr;         // = slots[cur]
     uint8_t *rgba8 = nullptr;
     int width = 0, height = 0;
@@ -125,7 +155,6 @@ struct VolumeRenderer::Impl {
     DeviceBuffer split_tracker, sample_tracker, visit_tracker, num_samples, cluster_indices, guided_samples;
     DeviceBuffer offsets, z_vals, sample_rows, sample_clusters, nerf_results;
     DeviceBuffer nodes, rand_sample, rand_clusters, results, fused_counter;
-    bool patch_after_prune = true;
     // several ranks (set_ranks): this rank's share of the frame in compact tile-major order, the gather table on rank 0, the marks table
     mnv_comm *comm = nullptr;
     mnv_partition part = {0, 1, 0, 0, 0};
@@ -133,9 +162,8 @@ struct VolumeRenderer::Impl {
     DeviceBuffer local, local8, table, table8, marks_table;
     int64_t tracker_rows() const { return comm ? rank_px * part.world : (int64_t)width * height; }
     bool fused_inputs_ok = false;  // the model's encoded input fits the fused guided kernel (<= 64 features)
-    bool prune_happened = false, can_reuse_results = false, accel_stale = false;
+    bool prune_happened = false, can_reuse_results = false;
     bool marks_fresh = false, want_marks = false;  // see render(): prune only after a track_visit frame
-    int quiet_frames = 0;
     long reuse_total = 0;
     uint64_t frame = 0;
     // show_grid: the device edge list, the depth and the tree structure it was made for (tree_version counts set / splits / prunes)
@@ -177,6 +205,10 @@ struct VolumeRenderer::Impl {
                                         S.grid_tmax, S.grid_rgba8, st),
                       "mnv_render_meshes");
         return in;
+    }
+    // the inputs of a frame on the slot it has taken: drawn by the frame itself, or the caller's (set_frame_inputs)
+    mnv_frame_inputs frame_inputs(const FramePlan &P, const mnv_camera &cv, const RenderOptions &o) {
+        return P.draws_inputs ? grid_inputs(slots[cur], slots[cur].stream, cv, o) : inputs;
     }
     // the fused guided kernel's sample count: copied to pinned memory behind the kernel and read at the frame's LAST wait (the vote's,
     // the tree edit's) instead of at a wait of its own right behind the march -- 20-40 us of a refinement frame
@@ -259,6 +291,29 @@ struct VolumeRenderer::Impl {
         rgba = slots[i].rgba;
         rgba8 = slots[i].rgba8;
     }
+    // The frame's slot: the next one beside the frames in flight, or slot 0 alone once they have finished.
+    Slot &take_slot(const FramePlan &P, int frames_in_flight) {
+        if (P.overlaps) {
+            // Slot streams are not ordered among each other.  Whatever slot 0's stream still holds from a frame that changed the tree
+            // or its accel (splits, resampled leaves, accel patches, a prune's renumbering: asynchronous on that stream) must be
+            // finished before a frame on another stream reads those arrays: once, on the way from such frames to overlapped ones.
+            if (tree_stream_dirty) {
+                hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+                tree_stream_dirty = false;
+            }
+            ensure_slots(frames_in_flight);
+            use_slot((cur + 1) % frames_in_flight);
+            overlapped = true;
+        } else {
+            if (overlapped) sync_all();
+            use_slot(0);
+            // What follows runs on slot 0's stream and may edit the tree.  Anti-aliased and projected frames only read it; they never
+            // raised the flag, and raising it now would add a wait on the way back to frames in flight (frames_in_flight raised since).
+            if (P.kind != FramePlan::AA && P.kind != FramePlan::PROJECTED) tree_stream_dirty = true;
+        }
+        slots[cur].counted = false;  // (a guided frame in flight raises it; every other kind's sample count is in `stats`)
+        return slots[cur];
+    }
     void fill_f32(float *p, size_t n, float v) {
         uint32_t bits;
         std::memcpy(&bits, &v, 4);
@@ -278,10 +333,42 @@ struct VolumeRenderer::Impl {
     }
     int sample_cols(const RenderOptions &o) const { return 3 + (o.need_viewdir ? 3 : 0) + (o.appearance_embedding != -1 ? 1 : 0); }
 
-    void tree_changed() {
-        accel_stale = true;
-        quiet_frames = 0;
-        can_reuse_results = false;
+    // The refinement prelude of a TREE / RANKS frame (cuda_renderer.cpp:97-107): whether the frame takes visit marks, and the tracker
+    // rows of the whole frame (tracker_rows(); on several ranks block r holds rank r's rows), of which this frame writes those from
+    // `first_row` on.
+    struct Trackers {
+        bool track_visit = false;
+        float *split = nullptr, *sample = nullptr, *my_split = nullptr, *my_sample = nullptr;  // null: no splitting
+        int32_t *visited = nullptr;
+    };
+    Trackers begin_refinement(const FramePlan &P, Camera &camera, const RenderOptions &o, FrameStats &st, int64_t first_row) {
+        Trackers T;
+        const bool camera_has_changed = camera.has_changed();
+        T.track_visit = P.refines && ((camera_has_changed && tree->capacity > max_tree_capacity * 3 / 4) || prune_happened || want_marks);
+        if (camera_has_changed) can_reuse_results = false;
+        st.track_visit = T.track_visit;
+        T.visited = visit_tracker.get<int32_t>((size_t)std::max<long>(max_tree_capacity, 1));
+        if (P.refines && o.use_splitting) {
+            const int64_t rows = tracker_rows();
+            T.split = split_tracker.get<float>(rows * 3);
+            T.sample = sample_tracker.get<float>(rows * 3);
+            // The fused kernel writes all three words of both rows for every pixel it renders, so a healthy fused frame does not need
+            // the fill (50 us of a 3 ms configs[4] frame) -- but a wavefront that its watchdog abandoned (MNV_E_FAULT, reported by the
+            // NEXT fused call) leaves its pixels' rows unwritten, and refine_after_frame edits the tree from these rows in this same
+            // frame: stale (chunk, child) pairs of an earlier frame may name chunks a prune has renumbered since.  -1 rows name nothing.
+            fill_f32(T.split, rows * 3, -1.f);
+            fill_f32(T.sample, rows * 3, -1.f);
+            T.my_split = T.split + first_row * 3;
+            T.my_sample = T.sample + first_row * 3;
+        }
+        return T;
+    }
+    // ... and the epilogue of every frame of a tree: the vote and the tree edits of a refinement frame, the frame's last wait
+    void finish_frame(const FramePlan &P, RenderOptions &o, FrameStats &st, uint64_t seed, bool track_visit) {
+        if (P.refines) refine_after_frame(o, st, seed, track_visit);
+        finish_count(st);
+        ++frame;
+        st.capacity = tree->capacity;
     }
 
     // cuda_renderer.cpp:205-272
@@ -346,7 +433,7 @@ void VolumeRenderer::Impl::expand_voxels(RenderOptions &o, FrameStats &st, uint6
     ++tree_version;
     st.added = n;
     can_reuse_results = false;
-    if (!accel_stale) tree->refresh_accel(old_capacity, nullptr, 0, stream);  // the packed layout follows the split
+    tree->refresh_accel(old_capacity, nullptr, 0, stream);  // the packed layout follows the split
 }
 
 void VolumeRenderer::Impl::get_more_samples(RenderOptions &o, FrameStats &st, uint64_t seed) {
@@ -371,7 +458,7 @@ void VolumeRenderer::Impl::get_more_samples(RenderOptions &o, FrameStats &st, ui
               "mnv_apply_sample_results");
     st.resampled = n;
     can_reuse_results = false;
-    if (!accel_stale) tree->refresh_accel(tree->capacity, d_nodes, n, stream);  // new sigma / colour rows of the resampled leaves
+    tree->refresh_accel(tree->capacity, d_nodes, n, stream);  // new sigma / colour rows of the resampled leaves
 }
 
 void VolumeRenderer::Impl::prune_tree(FrameStats &st) {
@@ -380,21 +467,14 @@ void VolumeRenderer::Impl::prune_tree(FrameStats &st) {
     // sample_counts is compacted with the other arrays; the reference forgets it (cuda_renderer.cpp:357-369)
     // A prune renumbers the chunks; the packed accel follows in place (mnv_prune_tree_accel: renumbered node words and lookup grids,
     // compacted colour rows), so that the next frame -- a visit-mark frame, cuda_renderer.cpp:101-102 -- runs on the tuned kernel as well.
-    mnv_accel *follow = (tree->device.accel && !accel_stale && patch_after_prune) ? tree->device.accel : nullptr;
     mnv_check(mnv_prune_tree_accel(&e, tree->device.data, tree->data_dim, tree->device.sample_counts, visit_tracker.get<int32_t>(max_tree_capacity),
-                                   (int32_t)max_tree_capacity, follow, &new_cap, &n_del, stream),
+                                   (int32_t)max_tree_capacity, tree->device.accel, &new_cap, &n_del, stream),
               "mnv_prune_tree_accel");
     st.pruned = n_del > 0 ? n_del : -1;
     if (n_del > 0) {
         tree->capacity = new_cap;
         ++tree_version;
-        tree_changed();
-        if (follow) {
-            accel_stale = false;
-        } else if (tree->device.accel) {  // no patch (switched off, or the accel was stale already): rebuild in place, 2.9 ms on the 1.5 M-chunk tree
-            tree->rebuild_accel(stream);
-            accel_stale = false;
-        }
+        can_reuse_results = false;
     }
 }
 
@@ -402,7 +482,6 @@ void VolumeRenderer::Impl::prune_tree(FrameStats &st) {
 void VolumeRenderer::Impl::refine_after_frame(RenderOptions &options, FrameStats &stats, uint64_t seed, bool track_visit) {
     Impl &I = *this;
     N3Tree &tree = *I.tree;
-    ++I.quiet_frames;
     // The capacity check runs only while splitting is on: the reference's unconditional
     // check would prune a tree that was merely loaded with max_tree_capacity close to its size.
     if (options.use_splitting) {
@@ -442,8 +521,7 @@ void VolumeRenderer::set(N3Tree &tree, long max_tree_capacity) {
     const int32_t one = 1;
     hip_check(hipMemcpyAsync(visited, &one, 4, hipMemcpyHostToDevice, impl_->stream), "mark root");
     hip_check(hipStreamSynchronize(impl_->stream), "set");
-    impl_->prune_happened = impl_->can_reuse_results = impl_->accel_stale = impl_->marks_fresh = impl_->want_marks = false;
-    impl_->quiet_frames = 0;
+    impl_->prune_happened = impl_->can_reuse_results = impl_->marks_fresh = impl_->want_marks = false;
     options.basis_minmax[0] = 0;
     options.basis_minmax[1] = std::max(tree.data_format.basis_dim - 1, 0);
 }
@@ -591,15 +669,10 @@ void VolumeRenderer::slot_metrics(int slot, mnv_frame_metric_values *out) {
 void VolumeRenderer::render() {
     Impl &I = *impl_;
     const uint8_t *target = I.target;
-    if (!target) {
-        render_frame();
-        I.slots[I.cur].scored = false;
-        return;
-    }
-    if (I.comm) throw StatusError(MNV_E_INVALID, "set_target scores the frame of one rank: it cannot be combined with set_ranks");
     render_frame();
     Impl::Slot &S = I.slots[I.cur];
     S.scored = false;
+    if (!target) return;
     if (!S.sums_dev) {
         hip_check(hipMalloc((void **)&S.sums_dev, sizeof(mnv_metric_sums)), "hipMalloc(metric sums)");
         hip_check(hipHostMalloc((void **)&S.sums_host, sizeof(mnv_metric_sums), hipHostMallocDefault), "hipHostMalloc(metric sums)");
@@ -610,260 +683,123 @@ void VolumeRenderer::render() {
     S.scored = true;
 }
 
-void VolumeRenderer::render_frame() {
+VolumeRenderer::FramePlan VolumeRenderer::plan() const {
+    const Impl &I = *impl_;
+    FramePlan P;
+    const N3Tree *tree = I.tree != nullptr && I.tree->N > 0 ? I.tree : nullptr;
+    const bool packed = tree && tree->device.accel;  // a tree with the packed accel: N == 2, RGBA or SH1/4/9/16/25 rows
+    const bool model_on = I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling);
+    const bool guided = I.mlp != nullptr && options.use_guided_sampling;
+    // the network is one the fused guided kernel covers
+    const bool covered = tree && I.mlp_desc.hidden_width == 64 && I.fused_inputs_ok &&
+                         (tree->data_format.format != DataFormat::SH || tree->data_format.basis_dim == 1 || tree->data_format.basis_dim == 4 ||
+                          tree->data_format.basis_dim == 9 || tree->data_format.basis_dim == 16);
+    const bool out_dim_differs = tree && model_on && I.mlp_desc.out_dim != tree->data_dim + 1;
+    const bool inputs_set = I.inputs.tmax_px || I.inputs.rgba8_init;
+    bool mesh_visible = false;
+    for (const mnv_mesh *m : meshes) mesh_visible = mesh_visible || (m && mnv_mesh_visible(m));
+    const bool projected = projection != MNV_PROJ_PINHOLE, aa = !projected && aa_samples != 1, ranks = !projected && !aa && I.comm;
+    P.kind = projected ? FramePlan::PROJECTED : aa ? FramePlan::AA : ranks ? FramePlan::RANKS : tree ? FramePlan::TREE : FramePlan::BACKGROUND;
+    // show_grid / meshes: the grid pass and the mesh pass produce this frame's inputs (cuda_renderer.cpp:68-90 draws them before the march)
+    P.show_grid = !projected && options.show_grid && tree;
+    P.draws_inputs = !projected && (P.show_grid || mesh_visible);
+    const bool grid_draws = P.draws_inputs && P.show_grid, meshes_draw = P.draws_inputs && !P.show_grid;
+
+    // Every combination render() cannot serve; the first row that holds is reported.
+    const struct {
+        bool holds, is_status;
+        const char *text;
+    } refusals[] = {
+        {I.target && I.comm, true, "set_target scores the frame of one rank: it cannot be combined with set_ranks"},
+        {projected && projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT, true, "projection: unknown projection"},
+        {projected && inputs_set, true, "projection: set_frame_inputs holds images of a pinhole camera; it cannot be combined with another projection"},
+        {projected && I.comm, true, "projection: orthographic / equirectangular frames are for one rank (set_ranks)"},
+        {projected && options.show_grid, true, "projection: the grid pass draws through a pinhole camera (show_grid)"},
+        {projected && mesh_visible, true, "projection: the mesh pass draws through a pinhole camera (a visible mesh)"},
+        {projected && aa_samples != 1, true, "projection: anti-aliasing jitters a pinhole camera (aa_samples > 1)"},
+        {projected && model_on, true, "projection: use_splitting / use_guided_sampling march a pinhole camera's rays"},
+        {projected && !packed, true, "projection: ray lists need a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)"},
+        {aa && (aa_samples < 1 || aa_samples > MNV_MAX_BATCH), true, "anti-aliasing: aa_samples must be 1 .. MNV_MAX_BATCH"},
+        {aa && aa_filter != MNV_AA_BOX && aa_filter != MNV_AA_TENT, true, "anti-aliasing: unknown aa_filter"},
+        {aa && inputs_set, true, "anti-aliasing jitters the camera: it cannot be combined with set_frame_inputs (images of one fixed camera)"},
+        {aa && I.comm, true, "anti-aliasing is for one rank: it cannot be combined with set_ranks"},
+        {aa && model_on, true, "anti-aliasing cannot be combined with use_splitting / use_guided_sampling (refinement votes per ray of one camera)"},
+        {aa && !packed, true, "anti-aliasing needs a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)"},
+        {grid_draws && inputs_set, true, "show_grid draws the frame inputs itself: it cannot be combined with set_frame_inputs"},
+        {meshes_draw && inputs_set, true, "a mesh list draws the frame inputs itself: it cannot be combined with set_frame_inputs"},
+        {grid_draws && I.comm, true, "show_grid is for one rank: it cannot be combined with set_ranks"},
+        {meshes_draw && I.comm, true, "a mesh list is for one rank: it cannot be combined with set_ranks"},
+        {ranks && !packed, false, "several ranks need a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)"},
+        {!projected && !aa && out_dim_differs, false, "the model's out_dim must be the tree's data_dim + 1 (cuda_renderer.cpp:255-257)"},
+        {ranks && options.render_depth && model_on, false, "several ranks: no depth mode while refining"},
+        {ranks && guided && !covered, false, "several ranks: guided sampling needs a network the fused kernel covers (64 wide, at most 64 encoded inputs)"},
+    };
+    for (const auto &r : refusals)
+        if (r.holds) {
+            P.refusal = r.text;
+            P.refusal_is_status = r.is_status;
+            return P;
+        }
+
+    // A frame that leaves the tree alone takes the next slot beside the frames in flight; everything else runs alone on slot 0.  With
+    // a model switched on that is a guided-sampling frame that wants nothing but the picture: the fused kernel, no splitting, no visit
+    // marks (a tree below 3/4 of its capacity and no prune pending: track_visit is then false whatever the camera did).
+    const bool leaves_tree_alone = !model_on || (guided_in_flight && use_fused_guided && guided && !options.use_splitting && !options.render_depth && covered &&
+                                                 !I.prune_happened && !I.want_marks && tree->capacity <= I.max_tree_capacity * 3 / 4);
+    P.overlaps = !I.comm && frames_in_flight > 1 && packed && leaves_tree_alone;
+    if (P.kind == FramePlan::TREE && P.overlaps) P.kind = guided ? FramePlan::GUIDED_IN_FLIGHT : FramePlan::PLAIN;
+    P.refines = model_on && (P.kind == FramePlan::TREE || P.kind == FramePlan::RANKS);
+    P.guided = guided;
+    P.fused = guided && use_fused_guided && !options.render_depth && covered;
+    P.packed = packed;
+    P.has_parent = tree && tree->device.parent;
+    return P;
+}
+
+bool VolumeRenderer::overlaps_next() const { return plan().overlaps; }
+int VolumeRenderer::next_slot() const { return plan().overlaps ? (impl_->cur + 1) % frames_in_flight : 0; }
+
+// What the slots share is brought up to date before the frame takes its slot: each step that replaces something frames in flight read
+// or write waits for them first (sync_all clears `overlapped`, so none of this may follow take_slot).
+void VolumeRenderer::update_shared(const FramePlan &P) {
     Impl &I = *impl_;
-    if (!I.slots[0].rgba) resize(camera.width, camera.height);
-    camera._update();
-    const mnv_camera cv = camera.c_abi();
-    I.last_camera = cv;
-    const mnv_rect full = {0, 0, I.width, I.height};
-    stats = FrameStats();
-    if (projection != MNV_PROJ_PINHOLE) {  // refused before anything is touched: MNV_PROJ_PINHOLE renders again
-        if (projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT) throw StatusError(MNV_E_INVALID, "projection: unknown projection");
-        if (I.inputs.tmax_px || I.inputs.rgba8_init)
-            throw StatusError(MNV_E_INVALID, "projection: set_frame_inputs holds images of a pinhole camera; it cannot be combined with another projection");
-        if (I.comm) throw StatusError(MNV_E_INVALID, "projection: orthographic / equirectangular frames are for one rank (set_ranks)");
-        if (options.show_grid) throw StatusError(MNV_E_INVALID, "projection: the grid pass draws through a pinhole camera (show_grid)");
-        for (const mnv_mesh *m : meshes)
-            if (m && mnv_mesh_visible(m)) throw StatusError(MNV_E_INVALID, "projection: the mesh pass draws through a pinhole camera (a visible mesh)");
-        if (aa_samples != 1) throw StatusError(MNV_E_INVALID, "projection: anti-aliasing jitters a pinhole camera (aa_samples > 1)");
-        if (I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling))
-            throw StatusError(MNV_E_INVALID, "projection: use_splitting / use_guided_sampling march a pinhole camera's rays");
-        if (I.tree == nullptr || I.tree->N <= 0 || !I.tree->device.accel)
-            throw StatusError(MNV_E_INVALID, "projection: ray lists need a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)");
-        render_projected(cv);
+    if (P.kind == FramePlan::PROJECTED) {  // (draws no inputs; anti-aliasing buffers of earlier frames stay until the next pinhole frame)
+        if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
+            I.sync_all();  // frames in flight read the old table
+            if (I.equirect_dev) (void)hipFree(I.equirect_dev);
+            I.equirect_dev = nullptr;
+            std::vector<float> table(((size_t)I.width + I.height) * 2);
+            mnv_check(mnv_equirect_tables(I.width, I.height, table.data()), "mnv_equirect_tables");
+            hip_check(hipMalloc((void **)&I.equirect_dev, table.size() * sizeof(float)), "hipMalloc(equirectangular table)");
+            hip_check(hipMemcpy(I.equirect_dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice), "upload equirectangular table");
+            I.equirect_w = I.width;
+            I.equirect_h = I.height;
+        }
         return;
     }
-    if (aa_samples != 1) {  // refused before anything is touched: aa_samples = 1 renders again
-        if (aa_samples < 1 || aa_samples > MNV_MAX_BATCH) throw StatusError(MNV_E_INVALID, "anti-aliasing: aa_samples must be 1 .. MNV_MAX_BATCH");
-        if (aa_filter != MNV_AA_BOX && aa_filter != MNV_AA_TENT) throw StatusError(MNV_E_INVALID, "anti-aliasing: unknown aa_filter");
-        if (I.inputs.tmax_px || I.inputs.rgba8_init)
-            throw StatusError(MNV_E_INVALID, "anti-aliasing jitters the camera: it cannot be combined with set_frame_inputs (images of one fixed camera)");
-        if (I.comm) throw StatusError(MNV_E_INVALID, "anti-aliasing is for one rank: it cannot be combined with set_ranks");
-        if (I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling))
-            throw StatusError(MNV_E_INVALID, "anti-aliasing cannot be combined with use_splitting / use_guided_sampling (refinement votes per ray of one camera)");
-        if (I.tree == nullptr || I.tree->N <= 0 || !I.tree->device.accel)
-            throw StatusError(MNV_E_INVALID, "anti-aliasing needs a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)");
-    } else if (I.aa_k != 1) {  // the buffers of earlier anti-aliased frames go; from here on render() is what it is without the feature
+    if (P.kind != FramePlan::AA && I.aa_k != 1) {  // the buffers of earlier anti-aliased frames go; from here on render() is what it is without the feature
         I.sync_all();
         I.free_aa();
     }
-    // show_grid / meshes: the grid pass and the mesh pass produce this frame's inputs (cuda_renderer.cpp:68-90 draws them before the march)
-    const bool show_grid = options.show_grid && I.tree != nullptr && I.tree->N > 0;
+    I.pass_grid = P.show_grid;
     I.pass_meshes.clear();
     for (const mnv_mesh *m : meshes)
         if (m && mnv_mesh_visible(m)) I.pass_meshes.push_back(m);
-    const bool grid = show_grid || !I.pass_meshes.empty();  // (from here on: "this frame draws its inputs itself")
-    I.pass_grid = show_grid;
-    if (grid) {
-        const char *who = show_grid ? "show_grid" : "a mesh list";
-        if (I.inputs.tmax_px || I.inputs.rgba8_init)
-            throw StatusError(MNV_E_INVALID, std::string(who) + " draws the frame inputs itself: it cannot be combined with set_frame_inputs");
-        if (I.comm) throw StatusError(MNV_E_INVALID, std::string(who) + " is for one rank: it cannot be combined with set_ranks");
-        if (!I.pass_meshes.empty()) I.can_reuse_results = false;  // (a mesh may have moved: the samples of the last guided frame were limited by it)
+    if (!I.pass_meshes.empty()) I.can_reuse_results = false;  // (a mesh may have moved: the samples of the last guided frame were limited by it)
+    if (P.show_grid && (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version)) {
+        I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
+        const mnv_tree_view dv = I.tree->device_view();
+        const int rc = I.wire ? mnv_wireframe_update(I.wire, &dv, options.grid_max_depth, I.stream)
+                              : mnv_wireframe_create(&dv, options.grid_max_depth, I.stream, &I.wire);
+        if (rc != MNV_OK) throw StatusError(rc, std::string("show_grid: ") + mnv_last_error());  // keeps the code (N != 2: unsupported)
+        I.wire_depth = options.grid_max_depth;
+        I.wire_version = I.tree_version;
+        I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
     }
-    if (show_grid) {
-        if (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version) {
-            I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
-            const mnv_tree_view dv = I.tree->device_view();
-            const int rc = I.wire ? mnv_wireframe_update(I.wire, &dv, options.grid_max_depth, I.stream)
-                                  : mnv_wireframe_create(&dv, options.grid_max_depth, I.stream, &I.wire);
-            if (rc != MNV_OK) throw StatusError(rc, std::string("show_grid: ") + mnv_last_error());  // keeps the code (N != 2: unsupported)
-            I.wire_depth = options.grid_max_depth;
-            I.wire_version = I.tree_version;
-            I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
-        }
-    }
-    if (aa_samples != 1) {
-        render_aa(cv, grid);
-        return;
-    }
-    {
-        // a plain frame of a tree with a current accel takes the next slot; everything else runs alone on slot 0
-        if (overlaps_next()) {
-            // Slot streams are not ordered among each other.  Whatever slot 0's stream still holds from a frame that changed the tree
-            // or its accel (splits, resampled leaves, accel patches, a prune's renumbering: asynchronous on that stream) must be
-            // finished before a frame on another stream reads those arrays: once, on the way from such frames to plain ones.
-            if (I.tree_stream_dirty) {
-                hip_check(hipStreamSynchronize(I.stream), "hipStreamSynchronize");
-                I.tree_stream_dirty = false;
-            }
-            I.ensure_slots(frames_in_flight);
-            I.use_slot((I.cur + 1) % frames_in_flight);
-            I.overlapped = true;
-            Impl::Slot &S = I.slots[I.cur];
-            const mnv_frame_inputs in = grid ? I.grid_inputs(S, S.stream, cv, options) : I.inputs;
-            if (I.mlp != nullptr && options.use_guided_sampling) {  // (overlaps_next: a guided-sampling frame that changes nothing, guided_in_flight)
-                if (!S.count_dev) {
-                    hip_check(hipMalloc((void **)&S.count_dev, sizeof(unsigned long long)), "hipMalloc(sample counter)");
-                    hip_check(hipHostMalloc((void **)&S.count_host, sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc(sample count)");
-                }
-                hip_check(hipMemsetAsync(S.count_dev, 0, sizeof(unsigned long long), S.stream), "clear sample counter");
-                mnv_check(mnv_render_guided_fused_track_ex(I.tree->device.accel, &cv, options.c_abi(), full, &in, I.mlp, &I.grid, I.rgba, I.rgba8, nullptr,
-                                                           nullptr, nullptr, nullptr, nullptr, S.count_dev, S.stream),
-                          "mnv_render_guided_fused_track_ex");
-                hip_check(hipMemcpyAsync(S.count_host, S.count_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream), "read sample counter");
-                S.counted = true;
-                stats.fused = true;
-                stats.guided_samples = -1;  // in flight: slot_guided_samples(last_slot())
-                ++I.quiet_frames;           // (what refine_after_frame does for a frame without splitting)
-            } else {
-                S.counted = false;
-                mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, S.stream),
-                          "mnv_render_voxels_accel_ex");
-            }
-            stats.used_accel = true;
-            stats.capacity = I.tree->capacity;
-            ++I.frame;
-            return;
-        }
-        if (I.overlapped) I.sync_all();
-        I.use_slot(0);
-        I.slots[0].counted = false;  // (this frame's sample count is in `stats`)
-        I.tree_stream_dirty = true;  // what follows runs on slot 0's stream and may edit the tree
-    }
-    if (I.comm) {
-        render_ranks();
-        return;
-    }
-    if (I.tree == nullptr || I.tree->N <= 0) {
-        mnv_tree_view empty = {};  // N == 0: background only (renderer_kernel.cu:266)
-        const mnv_frame_inputs in0 = grid ? I.grid_inputs(I.slots[0], I.stream, cv, options) : I.inputs;
-        mnv_check(mnv_render_voxels_ex(&empty, &cv, options.c_abi(), full, &in0, I.rgba, I.rgba8, nullptr, nullptr, nullptr, 0, I.stream),
-                  "mnv_render_voxels_ex");
-        return;
-    }
-    N3Tree &tree = *I.tree;
-    const mnv_frame_inputs in = grid ? I.grid_inputs(I.slots[0], I.stream, cv, options) : I.inputs;
-    const int64_t n_px = (int64_t)I.width * I.height;
-    const bool refine = I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling);
-    if (refine && I.mlp_desc.out_dim != tree.data_dim + 1)
-        throw std::runtime_error("the model's out_dim must be the tree's data_dim + 1 (cuda_renderer.cpp:255-257)");
-
-    // cuda_renderer.cpp:98-107
-    const bool camera_has_changed = camera.has_changed();
-    const bool track_visit = refine && ((camera_has_changed && tree.capacity > I.max_tree_capacity * 3 / 4) || I.prune_happened || I.want_marks);
-    if (camera_has_changed) I.can_reuse_results = false;
-    stats.track_visit = track_visit;
-    float *split = nullptr, *sample = nullptr;
-    int32_t *visited = I.visit_tracker.get<int32_t>((size_t)std::max<long>(I.max_tree_capacity, 1));
-    if (refine && options.use_splitting) {
-        split = I.split_tracker.get<float>(n_px * 3);
-        sample = I.sample_tracker.get<float>(n_px * 3);
-    }
-    // splits and resampled leaves are patched into the packed accel as they happen (mnv_accel_refresh); a prune renumbers
-    // the chunks, after which the march reads the reference-layout arrays until the accel has been rebuilt -- once the
-    // tree has been left alone for accel_rebuild_after frames
-    if (I.accel_stale && I.quiet_frames >= accel_rebuild_after) {
-        tree.rebuild_accel(I.stream);
-        I.accel_stale = false;
-    }
-    const mnv_tree_view dv = tree.device_view();
-
-    // the guided-sampling frame as ONE kernel (march + networks + composite [+ trackers + visit marks], no sample buffer) whenever
-    // the accel is current and the network is one the fused kernel covers
-    const bool fuse = refine && options.use_guided_sampling && use_fused_guided && tree.device.accel && !I.accel_stale &&
-                      (!track_visit || tree.device.parent) && !options.render_depth && I.mlp_desc.hidden_width == 64 && I.fused_inputs_ok &&
-                      (tree.data_format.format != DataFormat::SH || tree.data_format.basis_dim == 1 || tree.data_format.basis_dim == 4 ||
-                       tree.data_format.basis_dim == 9 || tree.data_format.basis_dim == 16);
-    if (split) {
-        // cuda_renderer.cpp:97-98.  The fused kernel writes all three words of both rows for every pixel it renders, so a healthy fused
-        // frame does not need the fill (50 us of a 3 ms configs[4] frame) -- but a wavefront that its watchdog abandoned (MNV_E_FAULT, reported
-        // by the NEXT fused call) leaves its pixels' rows unwritten, and refine_after_frame edits the tree from these rows in this same
-        // frame: stale (chunk, child) pairs of an earlier frame may name chunks a prune has renumbered since.  -1 rows name nothing.
-        I.fill_f32(split, n_px * 3, -1.f);
-        I.fill_f32(sample, n_px * 3, -1.f);
-    }
-    if (fuse) {
-        unsigned long long *counter = I.fused_counter.get<unsigned long long>(1);
-        hip_check(hipMemsetAsync(counter, 0, sizeof(unsigned long long), I.stream), "clear sample counter");
-        // with refinement on as well (configs[4]) the same kernel also writes the trackers and the visit marks
-        mnv_check(mnv_render_guided_fused_track_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.mlp, &I.grid, I.rgba, I.rgba8, split, sample,
-                                                   split ? tree.device.sample_counts : nullptr, track_visit ? visited : nullptr, tree.device.parent,
-                                                   counter, I.stream),
-                  "mnv_render_guided_fused_track_ex");
-        I.read_count_later(counter);
-        stats.used_accel = true;
-        stats.fused = true;
-        I.can_reuse_results = false;
-    } else if (refine && options.use_guided_sampling) {
-        // cuda_renderer.cpp:109-139
-        const int samples_dim = 1 + I.sample_cols(options), max_g = options.max_guided_samples, dd = tree.data_dim;
-        int64_t *offsets = I.offsets.get<int64_t>(n_px);
-        if (!I.can_reuse_results) {
-            int16_t *num = I.num_samples.get<int16_t>(n_px);
-            int16_t *clusters = I.cluster_indices.get<int16_t>(n_px * max_g);
-            float *guided = I.guided_samples.get<float>((size_t)n_px * max_g * samples_dim);
-            hip_check(hipMemsetAsync(num, 0, n_px * 2, I.stream), "clear num_samples");
-            if (tree.device.accel && !I.accel_stale && (!track_visit || tree.device.parent)) {
-                // visit marks on the packed layout: the march marks leaf chunks, a closure pass adds their ancestors
-                stats.used_accel = true;
-                mnv_check(mnv_get_samples_from_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, split, sample,
-                                                                     tree.device.sample_counts, track_visit ? visited : nullptr, tree.device.parent, num, guided,
-                                                                     samples_dim, clusters, &I.grid, I.stream),
-                          "mnv_get_samples_from_voxels_accel_visit_ex");
-            } else {
-                mnv_check(mnv_get_samples_from_voxels_ex(&dv, &cv, options.c_abi(), full, &in, split, sample, visited, track_visit, num, guided,
-                                                         samples_dim, clusters, &I.grid, I.stream),
-                          "mnv_get_samples_from_voxels_ex");
-            }
-            // one call in the steady state: the packed buffers keep the size of the previous frames and grow when a frame
-            // emits more (the call then reports the total it needs)
-            int64_t total = 0, cap_rows = (int64_t)(I.z_vals.bytes / sizeof(float));
-            float *z = nullptr, *rows = nullptr, *values = nullptr;
-            int16_t *row_clusters = nullptr;
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                z = I.z_vals.get<float>((size_t)std::max<int64_t>(cap_rows, 1));
-                rows = I.sample_rows.get<float>((size_t)std::max<int64_t>(cap_rows, 1) * (samples_dim - 1));
-                row_clusters = I.sample_clusters.get<int16_t>((size_t)std::max<int64_t>(cap_rows, 1));
-                const int rc = mnv_compact_guided_samples(num, guided, clusters, n_px, max_g, samples_dim, offsets, z, rows, row_clusters, cap_rows, &total,
-                                                          I.stream);
-                if (rc == MNV_OK) break;
-                if (total <= cap_rows || attempt == 1) mnv_check(rc, "mnv_compact_guided_samples");
-                cap_rows = total + total / 8;
-            }
-            values = I.nerf_results.get<float>((size_t)std::max<int64_t>(total, 1) * (dd + 1));
-            if (total > 0)
-                mnv_check(mnv_query_submodules(I.mlp, row_clusters, rows, samples_dim - 1, total, values, dd + 1, I.stream), "mnv_query_submodules");
-            I.reuse_total = total;
-            I.can_reuse_results = true;
-        }
-        stats.guided_samples = I.reuse_total;
-        mnv_check(mnv_render_nerf_results(&dv, &cv, options.c_abi(), full, I.nerf_results.get<float>(1), tree.data_dim + 1, I.z_vals.get<float>(1), offsets,
-                                          I.rgba, I.rgba8, I.stream),
-                  "mnv_render_nerf_results");
-    } else if (tree.device.accel && !I.accel_stale && (!track_visit || tree.device.parent)) {
-        stats.used_accel = true;
-        mnv_check(mnv_render_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, split, sample,
-                                                   tree.device.sample_counts, track_visit ? visited : nullptr, tree.device.parent, I.stream),
-                  "mnv_render_voxels_accel_visit_ex");
-    } else {
-        mnv_check(mnv_render_voxels_ex(&dv, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, split, sample, visited, track_visit, I.stream),
-                  "mnv_render_voxels_ex");
-    }
-
-    if (refine) I.refine_after_frame(options, stats, seed, track_visit);
-    I.finish_count(stats);
-    ++I.frame;
-    stats.capacity = tree.capacity;
-}
-
-// render() with aa_samples > 1 (the combinations it cannot serve were refused by render()): K jittered sub-frames on the frame's slot
-// and stream, then the resolve into the slot's frame
-void VolumeRenderer::render_aa(const mnv_camera &cv, bool grid) {
-    Impl &I = *impl_;
-    N3Tree &tree = *I.tree;
-    const int K = aa_samples;
-    if (I.accel_stale) {  // (left behind by refinement frames that were switched off since): every sub-frame runs on the packed layout
-        if (I.overlapped) I.sync_all();
-        tree.rebuild_accel(I.stream);
-        I.accel_stale = false;
-        I.tree_stream_dirty = true;
-    }
-    if (K != I.aa_k || aa_filter != I.aa_filter) {
+    if (P.kind == FramePlan::AA && (aa_samples != I.aa_k || aa_filter != I.aa_filter)) {
+        const int K = aa_samples;
         I.sync_all();  // frames in flight read the old table and write the old sub-frame buffers
-        const bool resized = K != I.aa_k;
-        if (resized || !I.aa_weights_dev) {
+        if (K != I.aa_k || !I.aa_weights_dev) {
             I.free_aa();
             hip_check(hipMalloc((void **)&I.aa_weights_dev, (size_t)K * 25 * sizeof(float)), "hipMalloc(filter weights)");
         }
@@ -876,21 +812,163 @@ void VolumeRenderer::render_aa(const mnv_camera &cv, bool grid) {
         I.aa_k = K;
         I.aa_filter = aa_filter;
     }
-    // the slot, as for a plain frame
-    if (overlaps_next()) {
-        if (I.tree_stream_dirty) {
-            hip_check(hipStreamSynchronize(I.stream), "hipStreamSynchronize");
-            I.tree_stream_dirty = false;
-        }
-        I.ensure_slots(frames_in_flight);
-        I.use_slot((I.cur + 1) % frames_in_flight);
-        I.overlapped = true;
-    } else {
-        if (I.overlapped) I.sync_all();
-        I.use_slot(0);
+}
+
+void VolumeRenderer::render_frame() {
+    Impl &I = *impl_;
+    if (!I.slots[0].rgba) resize(camera.width, camera.height);
+    camera._update();
+    const mnv_camera cv = camera.c_abi();
+    I.last_camera = cv;
+    stats = FrameStats();
+    const FramePlan P = plan();
+    if (P.refusal) {  // before a slot, a stream or a buffer is touched: the same call renders once the obstacle is gone
+        if (P.refusal_is_status) throw StatusError(MNV_E_INVALID, P.refusal);
+        throw std::runtime_error(P.refusal);
     }
+    update_shared(P);
+    I.take_slot(P, frames_in_flight);
+    bool track_visit = false;
+    switch (P.kind) {
+        case FramePlan::BACKGROUND: issue_background(P, cv); return;  // (no tree: nothing to refine or count)
+        case FramePlan::PLAIN: issue_plain(P, cv); break;
+        case FramePlan::GUIDED_IN_FLIGHT: issue_guided_in_flight(P, cv); break;
+        case FramePlan::TREE: track_visit = issue_tree(P, cv); break;
+        case FramePlan::RANKS: track_visit = issue_ranks(P, cv); break;
+        case FramePlan::AA: issue_aa(P, cv); break;
+        case FramePlan::PROJECTED: issue_projected(cv); break;
+    }
+    I.finish_frame(P, options, stats, seed, track_visit);
+}
+
+void VolumeRenderer::issue_background(const FramePlan &P, const mnv_camera &cv) {
+    Impl &I = *impl_;
+    mnv_tree_view empty = {};  // N == 0: background only (renderer_kernel.cu:266)
+    const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
+    mnv_check(mnv_render_voxels_ex(&empty, &cv, options.c_abi(), {0, 0, I.width, I.height}, &in, I.rgba, I.rgba8, nullptr, nullptr, nullptr, 0, I.stream),
+              "mnv_render_voxels_ex");
+}
+
+void VolumeRenderer::issue_plain(const FramePlan &P, const mnv_camera &cv) {
+    Impl &I = *impl_;
+    const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
+    mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cv, options.c_abi(), {0, 0, I.width, I.height}, &in, I.rgba, I.rgba8, I.slots[I.cur].stream),
+              "mnv_render_voxels_accel_ex");
+    stats.used_accel = true;
+}
+
+void VolumeRenderer::issue_guided_in_flight(const FramePlan &P, const mnv_camera &cv) {
+    Impl &I = *impl_;
     Impl::Slot &S = I.slots[I.cur];
-    S.counted = false;
+    const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
+    if (!S.count_dev) {
+        hip_check(hipMalloc((void **)&S.count_dev, sizeof(unsigned long long)), "hipMalloc(sample counter)");
+        hip_check(hipHostMalloc((void **)&S.count_host, sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc(sample count)");
+    }
+    hip_check(hipMemsetAsync(S.count_dev, 0, sizeof(unsigned long long), S.stream), "clear sample counter");
+    mnv_check(mnv_render_guided_fused_track_ex(I.tree->device.accel, &cv, options.c_abi(), {0, 0, I.width, I.height}, &in, I.mlp, &I.grid, I.rgba, I.rgba8,
+                                               nullptr, nullptr, nullptr, nullptr, nullptr, S.count_dev, S.stream),
+              "mnv_render_guided_fused_track_ex");
+    hip_check(hipMemcpyAsync(S.count_host, S.count_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream), "read sample counter");
+    S.counted = true;
+    stats.used_accel = true;
+    stats.fused = true;
+    stats.guided_samples = -1;  // in flight: slot_guided_samples(last_slot())
+}
+
+// a frame alone on slot 0 that may refine the tree; returns whether it took visit marks
+bool VolumeRenderer::issue_tree(const FramePlan &P, const mnv_camera &cv) {
+    Impl &I = *impl_;
+    N3Tree &tree = *I.tree;
+    const mnv_rect full = {0, 0, I.width, I.height};
+    const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
+    const Impl::Trackers T = I.begin_refinement(P, camera, options, stats, 0);
+    const bool track_visit = T.track_visit;
+    const mnv_tree_view dv = tree.device_view();
+    switch (P.march(track_visit)) {
+        case FramePlan::FUSED_GUIDED: {
+            // the guided-sampling frame as ONE kernel (march + networks + composite, no sample buffer); with refinement on as well
+            // (configs[4]) the same kernel also writes the trackers and the visit marks
+            unsigned long long *counter = I.fused_counter.get<unsigned long long>(1);
+            hip_check(hipMemsetAsync(counter, 0, sizeof(unsigned long long), I.stream), "clear sample counter");
+            mnv_check(mnv_render_guided_fused_track_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.mlp, &I.grid, I.rgba, I.rgba8, T.split, T.sample,
+                                                       T.split ? tree.device.sample_counts : nullptr, track_visit ? T.visited : nullptr, tree.device.parent,
+                                                       counter, I.stream),
+                      "mnv_render_guided_fused_track_ex");
+            I.read_count_later(counter);
+            stats.used_accel = true;
+            stats.fused = true;
+            I.can_reuse_results = false;
+            break;
+        }
+        case FramePlan::FOUR_STEP_GUIDED: {
+            // cuda_renderer.cpp:109-139
+            const int64_t n_px = (int64_t)I.width * I.height;
+            const int samples_dim = 1 + I.sample_cols(options), max_g = options.max_guided_samples, dd = tree.data_dim;
+            int64_t *offsets = I.offsets.get<int64_t>(n_px);
+            if (!I.can_reuse_results) {
+                int16_t *num = I.num_samples.get<int16_t>(n_px);
+                int16_t *clusters = I.cluster_indices.get<int16_t>(n_px * max_g);
+                float *guided = I.guided_samples.get<float>((size_t)n_px * max_g * samples_dim);
+                hip_check(hipMemsetAsync(num, 0, n_px * 2, I.stream), "clear num_samples");
+                if (P.on_accel(track_visit)) {
+                    // visit marks on the packed layout: the march marks leaf chunks, a closure pass adds their ancestors
+                    stats.used_accel = true;
+                    mnv_check(mnv_get_samples_from_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, T.split, T.sample,
+                                                                         tree.device.sample_counts, track_visit ? T.visited : nullptr, tree.device.parent, num,
+                                                                         guided, samples_dim, clusters, &I.grid, I.stream),
+                              "mnv_get_samples_from_voxels_accel_visit_ex");
+                } else {
+                    mnv_check(mnv_get_samples_from_voxels_ex(&dv, &cv, options.c_abi(), full, &in, T.split, T.sample, T.visited, track_visit, num, guided,
+                                                             samples_dim, clusters, &I.grid, I.stream),
+                              "mnv_get_samples_from_voxels_ex");
+                }
+                // one call in the steady state: the packed buffers keep the size of the previous frames and grow when a frame
+                // emits more (the call then reports the total it needs)
+                int64_t total = 0, cap_rows = (int64_t)(I.z_vals.bytes / sizeof(float));
+                float *z = nullptr, *rows = nullptr, *values = nullptr;
+                int16_t *row_clusters = nullptr;
+                for (int attempt = 0; attempt < 2; ++attempt) {
+                    z = I.z_vals.get<float>((size_t)std::max<int64_t>(cap_rows, 1));
+                    rows = I.sample_rows.get<float>((size_t)std::max<int64_t>(cap_rows, 1) * (samples_dim - 1));
+                    row_clusters = I.sample_clusters.get<int16_t>((size_t)std::max<int64_t>(cap_rows, 1));
+                    const int rc = mnv_compact_guided_samples(num, guided, clusters, n_px, max_g, samples_dim, offsets, z, rows, row_clusters, cap_rows,
+                                                              &total, I.stream);
+                    if (rc == MNV_OK) break;
+                    if (total <= cap_rows || attempt == 1) mnv_check(rc, "mnv_compact_guided_samples");
+                    cap_rows = total + total / 8;
+                }
+                values = I.nerf_results.get<float>((size_t)std::max<int64_t>(total, 1) * (dd + 1));
+                if (total > 0)
+                    mnv_check(mnv_query_submodules(I.mlp, row_clusters, rows, samples_dim - 1, total, values, dd + 1, I.stream), "mnv_query_submodules");
+                I.reuse_total = total;
+                I.can_reuse_results = true;
+            }
+            stats.guided_samples = I.reuse_total;
+            mnv_check(mnv_render_nerf_results(&dv, &cv, options.c_abi(), full, I.nerf_results.get<float>(1), tree.data_dim + 1, I.z_vals.get<float>(1), offsets,
+                                              I.rgba, I.rgba8, I.stream),
+                      "mnv_render_nerf_results");
+            break;
+        }
+        case FramePlan::TRACKED_ACCEL:
+            stats.used_accel = true;
+            mnv_check(mnv_render_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, T.split, T.sample,
+                                                       tree.device.sample_counts, track_visit ? T.visited : nullptr, tree.device.parent, I.stream),
+                      "mnv_render_voxels_accel_visit_ex");
+            break;
+        case FramePlan::REFERENCE_LAYOUT:
+            mnv_check(mnv_render_voxels_ex(&dv, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, T.split, T.sample, T.visited, track_visit, I.stream),
+                      "mnv_render_voxels_ex");
+            break;
+    }
+    return track_visit;
+}
+
+// aa_samples > 1: K jittered sub-frames on the frame's slot and stream, then the resolve into the slot's frame
+void VolumeRenderer::issue_aa(const FramePlan &P, const mnv_camera &cv) {
+    Impl &I = *impl_;
+    Impl::Slot &S = I.slots[I.cur];
+    const int K = aa_samples;
     const size_t frame_floats = (size_t)I.width * I.height * 4;
     if (!S.aa_sub) hip_check(hipMalloc((void **)&S.aa_sub, (size_t)K * frame_floats * sizeof(float)), "hipMalloc(sub-frames)");
     const mnv_rect full = {0, 0, I.width, I.height};
@@ -900,82 +978,42 @@ void VolumeRenderer::render_aa(const mnv_camera &cv, bool grid) {
         cams[k].cx = cv.cx - I.aa_offsets[2 * k];
         cams[k].cy = cv.cy - I.aa_offsets[2 * k + 1];
     }
-    if (grid) {  // the batch call has no per-pixel inputs: grid pass + march per camera, in stream order (the slot's two grid images are reused)
+    if (P.draws_inputs) {  // the batch call has no per-pixel inputs: grid pass + march per camera, in stream order (the slot's two grid images are reused)
         for (int k = 0; k < K; ++k) {
             const mnv_frame_inputs in = I.grid_inputs(S, S.stream, cams[k], options);
-            mnv_check(mnv_render_voxels_accel_ex(tree.device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub + (size_t)k * frame_floats, nullptr, S.stream),
+            mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub + (size_t)k * frame_floats, nullptr, S.stream),
                       "mnv_render_voxels_accel_ex");
         }
     } else {
         const mnv_partition whole = {0, 1, 0, 0, 0};
-        mnv_check(mnv_render_voxels_accel_batch(tree.device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub, nullptr, S.stream),
+        mnv_check(mnv_render_voxels_accel_batch(I.tree->device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub, nullptr, S.stream),
                   "mnv_render_voxels_accel_batch");
     }
     mnv_check(mnv_resolve_samples(S.aa_sub, K, I.width, I.height, I.aa_weights_dev, I.aa_radius, I.rgba, I.rgba8, S.stream), "mnv_resolve_samples");
     stats.used_accel = true;
-    stats.capacity = tree.capacity;
-    ++I.frame;
 }
 
-// render() with an orthographic or equirectangular projection (the combinations it cannot serve were refused by render()): the frame's
-// rays on the frame's slot and stream, then the ray march into the slot's frame
-void VolumeRenderer::render_projected(const mnv_camera &cv) {
+// an orthographic or equirectangular projection: the frame's rays on the frame's slot and stream, then the ray march into the slot's frame
+void VolumeRenderer::issue_projected(const mnv_camera &cv) {
     Impl &I = *impl_;
-    N3Tree &tree = *I.tree;
-    if (I.accel_stale) {  // (left behind by refinement frames that were switched off since)
-        if (I.overlapped) I.sync_all();
-        tree.rebuild_accel(I.stream);
-        I.accel_stale = false;
-        I.tree_stream_dirty = true;
-    }
-    if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
-        I.sync_all();  // frames in flight read the old table
-        if (I.equirect_dev) (void)hipFree(I.equirect_dev);
-        I.equirect_dev = nullptr;
-        std::vector<float> table(((size_t)I.width + I.height) * 2);
-        mnv_check(mnv_equirect_tables(I.width, I.height, table.data()), "mnv_equirect_tables");
-        hip_check(hipMalloc((void **)&I.equirect_dev, table.size() * sizeof(float)), "hipMalloc(equirectangular table)");
-        hip_check(hipMemcpy(I.equirect_dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice), "upload equirectangular table");
-        I.equirect_w = I.width;
-        I.equirect_h = I.height;
-    }
-    // the slot, as for a plain frame
-    if (overlaps_next()) {
-        if (I.tree_stream_dirty) {
-            hip_check(hipStreamSynchronize(I.stream), "hipStreamSynchronize");
-            I.tree_stream_dirty = false;
-        }
-        I.ensure_slots(frames_in_flight);
-        I.use_slot((I.cur + 1) % frames_in_flight);
-        I.overlapped = true;
-    } else {
-        if (I.overlapped) I.sync_all();
-        I.use_slot(0);
-    }
     Impl::Slot &S = I.slots[I.cur];
-    S.counted = false;
     const size_t ray_bytes = (size_t)I.width * I.height * 3 * sizeof(float);
     if (!S.ray_origins) {
         hip_check(hipMalloc((void **)&S.ray_origins, ray_bytes), "hipMalloc(ray origins)");
         hip_check(hipMalloc((void **)&S.ray_dirs, ray_bytes), "hipMalloc(ray directions)");
     }
-    const mnv_rect full = {0, 0, I.width, I.height};
-    mnv_check(mnv_generate_rays(projection, &cv, full, projection == MNV_PROJ_EQUIRECT ? I.equirect_dev : nullptr, S.ray_origins, S.ray_dirs, S.stream),
+    mnv_check(mnv_generate_rays(projection, &cv, {0, 0, I.width, I.height}, projection == MNV_PROJ_EQUIRECT ? I.equirect_dev : nullptr, S.ray_origins,
+                                S.ray_dirs, S.stream),
               "mnv_generate_rays");
-    mnv_check(mnv_render_rays_accel(tree.device.accel, S.ray_origins, S.ray_dirs, I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
+    mnv_check(mnv_render_rays_accel(I.tree->device.accel, S.ray_origins, S.ray_dirs, I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
               "mnv_render_rays_accel");
     stats.used_accel = true;
-    stats.capacity = tree.capacity;
-    ++I.frame;
 }
 
-// render() of one rank of several (set_ranks)
-void VolumeRenderer::render_ranks() {
+// one rank of several (set_ranks); returns whether the frame took visit marks
+bool VolumeRenderer::issue_ranks(const FramePlan &P, const mnv_camera &cv) {
     Impl &I = *impl_;
-    if (I.tree == nullptr || I.tree->N <= 0 || !I.tree->device.accel)
-        throw std::runtime_error("several ranks need a tree with the packed accel (N == 2, RGBA or SH1/4/9/16/25 rows)");
     N3Tree &tree = *I.tree;
-    const mnv_camera cv = camera.c_abi();
     const mnv_rect full = {0, 0, I.width, I.height};
     const int world = I.part.world, rank = I.part.rank;
     int32_t j_max = 0;
@@ -985,49 +1023,26 @@ void VolumeRenderer::render_ranks() {
     }
     I.rank_px = (int64_t)j_max * I.part.tile_w * I.part.tile_h;
     const int64_t rows = I.rank_px * world;
-    const bool refine = I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling);
-    if (refine && I.mlp_desc.out_dim != tree.data_dim + 1)
-        throw std::runtime_error("the model's out_dim must be the tree's data_dim + 1 (cuda_renderer.cpp:255-257)");
-    if (options.render_depth && refine) throw std::runtime_error("several ranks: no depth mode while refining");
-
-    // cuda_renderer.cpp:98-107 -- the same decisions on every rank: they depend on the camera and on the (replicated) tree only
-    const bool camera_has_changed = camera.has_changed();
-    const bool track_visit = refine && ((camera_has_changed && tree.capacity > I.max_tree_capacity * 3 / 4) || I.prune_happened || I.want_marks);
-    if (camera_has_changed) I.can_reuse_results = false;
-    stats.track_visit = track_visit;
     float *local = I.local.get<float>((size_t)I.rank_px * 4);
     uint8_t *local8 = I.local8.get<uint8_t>((size_t)I.rank_px * 4);
-    float *split = nullptr, *sample = nullptr;  // [world][rank_px][3]: block r holds rank r's rows
-    int32_t *visited = I.visit_tracker.get<int32_t>((size_t)std::max<long>(I.max_tree_capacity, 1));
-    if (refine && options.use_splitting) {
-        split = I.split_tracker.get<float>(rows * 3);
-        sample = I.sample_tracker.get<float>(rows * 3);
-        I.fill_f32(split, rows * 3, -1.f);
-        I.fill_f32(sample, rows * 3, -1.f);
-    }
-    float *my_split = split ? split + (size_t)rank * I.rank_px * 3 : nullptr, *my_sample = sample ? sample + (size_t)rank * I.rank_px * 3 : nullptr;
-    if (I.accel_stale) {  // every frame of a rank runs on the packed layout
-        tree.rebuild_accel(I.stream);
-        I.accel_stale = false;
-    }
-    if (track_visit && !tree.device.parent) throw std::runtime_error("several ranks: visit marks need the tree's parent array");
+    // the same decisions on every rank: they depend on the camera and on the (replicated) tree only
+    const Impl::Trackers T = I.begin_refinement(P, camera, options, stats, (int64_t)rank * I.rank_px);
+    const bool track_visit = T.track_visit;
+    // (not a row of plan()'s table: it takes the camera latch to know; every tree VolumeRenderer::set uploads has the array)
+    if (track_visit && !P.has_parent) throw std::runtime_error("several ranks: visit marks need the tree's parent array");
     stats.used_accel = true;
-    if (refine && options.use_guided_sampling) {
-        const bool fits = I.mlp_desc.hidden_width == 64 && I.fused_inputs_ok &&
-                          (tree.data_format.format != DataFormat::SH || tree.data_format.basis_dim == 1 || tree.data_format.basis_dim == 4 ||
-                           tree.data_format.basis_dim == 9 || tree.data_format.basis_dim == 16);
-        if (!fits) throw std::runtime_error("several ranks: guided sampling needs a network the fused kernel covers (64 wide, at most 64 encoded inputs)");
+    if (P.guided) {
         unsigned long long *counter = I.fused_counter.get<unsigned long long>(1);
         hip_check(hipMemsetAsync(counter, 0, sizeof(unsigned long long), I.stream), "clear sample counter");
-        mnv_check(mnv_render_guided_fused_track_part(tree.device.accel, &cv, options.c_abi(), full, I.part, I.mlp, &I.grid, local, local8, my_split, my_sample,
-                                                     split ? tree.device.sample_counts : nullptr, track_visit ? visited : nullptr, tree.device.parent, counter,
-                                                     I.stream),
+        mnv_check(mnv_render_guided_fused_track_part(tree.device.accel, &cv, options.c_abi(), full, I.part, I.mlp, &I.grid, local, local8, T.my_split,
+                                                     T.my_sample, T.split ? tree.device.sample_counts : nullptr, track_visit ? T.visited : nullptr,
+                                                     tree.device.parent, counter, I.stream),
                   "mnv_render_guided_fused_track_part");
         I.read_count_later(counter);  // (this rank's share)
         stats.fused = true;
     } else {
-        mnv_check(mnv_render_voxels_accel_visit_part(tree.device.accel, &cv, options.c_abi(), full, I.part, local, local8, my_split, my_sample,
-                                                     tree.device.sample_counts, track_visit ? visited : nullptr, tree.device.parent, I.stream),
+        mnv_check(mnv_render_voxels_accel_visit_part(tree.device.accel, &cv, options.c_abi(), full, I.part, local, local8, T.my_split, T.my_sample,
+                                                     tree.device.sample_counts, track_visit ? T.visited : nullptr, tree.device.parent, I.stream),
                   "mnv_render_voxels_accel_visit_part");
     }
     // the picture: tiles to rank 0, un-permuted there
@@ -1040,23 +1055,20 @@ void VolumeRenderer::render_ranks() {
         mnv_check(mnv_assemble_tiles(table8, I.rgba8, I.width, I.height, I.part, 1, 4, I.stream), "mnv_assemble_tiles");
     }
     // the votes need every rank's tracker rows, a prune every rank's marks
-    if (split) {
-        mnv_check(mnv_allgather(I.comm, split, (size_t)I.rank_px * 12, I.stream), "mnv_allgather");
-        mnv_check(mnv_allgather(I.comm, sample, (size_t)I.rank_px * 12, I.stream), "mnv_allgather");
+    if (T.split) {
+        mnv_check(mnv_allgather(I.comm, T.split, (size_t)I.rank_px * 12, I.stream), "mnv_allgather");
+        mnv_check(mnv_allgather(I.comm, T.sample, (size_t)I.rank_px * 12, I.stream), "mnv_allgather");
     }
     if (track_visit && world > 1) {
         // the marks of the chunks that exist: the replicas agree on tree.capacity, and a chunk beyond it cannot be marked (the table is
         // sized once for the largest tree -- reallocation would stall the frame -- but only cap words per rank travel and merge)
         const size_t cap = (size_t)tree.capacity;
         int32_t *marks = I.marks_table.get<int32_t>((size_t)I.max_tree_capacity * world);
-        hip_check(hipMemcpyAsync(marks + cap * rank, visited, cap * 4, hipMemcpyDeviceToDevice, I.stream), "copy marks");
+        hip_check(hipMemcpyAsync(marks + cap * rank, T.visited, cap * 4, hipMemcpyDeviceToDevice, I.stream), "copy marks");
         mnv_check(mnv_allgather(I.comm, marks, cap * 4, I.stream), "mnv_allgather");
-        mnv_check(mnv_merge_visit_marks(marks, world, (int32_t)cap, visited, I.stream), "mnv_merge_visit_marks");
+        mnv_check(mnv_merge_visit_marks(marks, world, (int32_t)cap, T.visited, I.stream), "mnv_merge_visit_marks");
     }
-    if (refine) I.refine_after_frame(options, stats, seed, track_visit);
-    I.finish_count(stats);
-    ++I.frame;
-    stats.capacity = tree.capacity;
+    return track_visit;
 }
 
 const char *VolumeRenderer::get_backend() { return "HIP gfx950"; }
@@ -1067,21 +1079,6 @@ void VolumeRenderer::download(std::vector<float> *rgba, std::vector<uint8_t> *rg
 
 int VolumeRenderer::last_slot() const { return impl_->cur; }
 
-bool VolumeRenderer::overlaps_next() const {
-    const Impl &I = *impl_;
-    if (I.comm || frames_in_flight <= 1 || I.tree == nullptr || I.tree->N <= 0 || !I.tree->device.accel || I.accel_stale) return false;
-    const bool refine_now = I.mlp != nullptr && (options.use_splitting || options.use_guided_sampling);
-    if (!refine_now) return true;  // a plain frame on the packed accel
-    // a guided-sampling frame that changes nothing and wants nothing but the picture: the fused kernel, no splitting, no visit marks (a tree
-    // below 3/4 of its capacity and no prune pending: render()'s track_visit is then false whatever the camera did)
-    const N3Tree &tree = *I.tree;
-    const bool covered = I.mlp_desc.hidden_width == 64 && I.fused_inputs_ok && I.mlp_desc.out_dim == tree.data_dim + 1 &&
-                         (tree.data_format.format != DataFormat::SH || tree.data_format.basis_dim == 1 || tree.data_format.basis_dim == 4 ||
-                          tree.data_format.basis_dim == 9 || tree.data_format.basis_dim == 16);
-    return guided_in_flight && use_fused_guided && options.use_guided_sampling && !options.use_splitting && !options.render_depth && covered &&
-           !I.prune_happened && !I.want_marks && tree.capacity <= I.max_tree_capacity * 3 / 4;
-}
-
 long VolumeRenderer::slot_guided_samples(int slot) {
     Impl &I = *impl_;
     if (slot < 0 || slot >= (int)I.slots.size()) throw std::runtime_error("slot_guided_samples: no such frame slot");
@@ -1090,8 +1087,6 @@ long VolumeRenderer::slot_guided_samples(int slot) {
     hip_check(hipStreamSynchronize(S.stream), "slot_guided_samples");
     return (long)*S.count_host;
 }
-
-int VolumeRenderer::next_slot() const { return overlaps_next() ? (impl_->cur + 1) % frames_in_flight : 0; }
 
 void VolumeRenderer::download_slot(int slot, std::vector<float> *rgba, std::vector<uint8_t> *rgba8) {
     if (slot < 0 || slot >= (int)impl_->slots.size() || !impl_->slots[slot].rgba) throw std::runtime_error("download_slot: no such frame slot");

@@ -51,7 +51,7 @@ struct VolumeRenderer {
 
     // Wait for the last render() and copy the frame to the host ([height][width][4]).
     void download(std::vector<float> *rgba, std::vector<uint8_t> *rgba8);
-    // Frames in flight: plain frames (no refinement, accel current) rotate over this many slots, each with its own HIP stream
+    // Frames in flight: plain frames (no refinement, a tree with the packed accel) rotate over this many slots, each with its own HIP stream
     // and frame buffers, so that the tail of one launch overlaps the next launches (1 = the reference's one-stream behaviour).
     // render() returns at once; last_slot() names the slot it used and download_slot() waits for that slot's frame only --
     // a caller that wants overlap downloads frame k after it has issued frames k+1 .. k+frames_in_flight-1.
@@ -166,7 +166,7 @@ struct VolumeRenderer {
     // Guided-sampling frames run as one fused kernel when nothing but the picture is wanted from them (false: always the
     // four-step path of the reference, cuda_renderer.cpp:107-139).
     bool use_fused_guided = true;
-    // Frames without a tree change after which the packed accel is rebuilt and used again.
+    // No longer read: the packed accel follows every tree edit in place (splits, resampled leaves, prunes).  Kept for the C ABI.
     int accel_rebuild_after = 4;
 
     // Camera instance
@@ -175,10 +175,25 @@ struct VolumeRenderer {
     RenderOptions options;
 
 private:
-    void render_frame();  // render() but for the score
-    void render_ranks();
-    void render_aa(const mnv_camera &cv, bool grid);
-    void render_projected(const mnv_camera &cv);
+    // A frame is decided once, then issued.  plan() reads the renderer's state and options -- it makes no HIP call and changes nothing --
+    // and answers: the kind of frame (background only; plain or guided beside the frames in flight; a tree frame alone on slot 0 that
+    // may refine, with its march: fused guided, four-step guided, tracked on the accel, reference layout; ranks; anti-aliased;
+    // projected), whether it takes the next slot, whether it draws its own inputs (grid, visible meshes), whether it refines, and
+    // whether it is refused, by the one table of the combinations render() cannot serve.  overlaps_next() and next_slot() read the
+    // same function, so what they predict is what render() does.  Which refusal is reported when several hold is not part of the contract.
+    // render_frame() (render() but for the score): prepare the camera, plan, refuse, bring what the slots share up to date
+    // (update_shared), take the slot, issue the kind's entry points, then the refinement epilogue.
+    struct FramePlan;
+    FramePlan plan() const;
+    void render_frame();
+    void update_shared(const FramePlan &P);
+    void issue_background(const FramePlan &P, const mnv_camera &cv);
+    void issue_plain(const FramePlan &P, const mnv_camera &cv);
+    void issue_guided_in_flight(const FramePlan &P, const mnv_camera &cv);
+    bool issue_tree(const FramePlan &P, const mnv_camera &cv);
+    bool issue_ranks(const FramePlan &P, const mnv_camera &cv);
+    void issue_aa(const FramePlan &P, const mnv_camera &cv);
+    void issue_projected(const mnv_camera &cv);
     struct Impl;
     std::unique_ptr<Impl> impl_;
 };
