@@ -455,6 +455,7 @@ class ProbeFrame(C.Structure):
 _PROBE_SIGNATURES = {
     "mnv_hook_probe_frame_size": (C.c_int, []),
     "mnv_hook_probe_cam_size": (C.c_int, []),
+    "mnv_hook_live_bytes": (C.c_int64, [C.c_int]),
     "mnv_hook_probe_expf": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_expf_digest": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_expf_variants_differ": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),

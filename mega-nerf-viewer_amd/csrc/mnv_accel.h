@@ -52,6 +52,7 @@
 
 #include "../../include/mnv.h"
 #include "mnv_device.h"
+#include "mnv_devmem.h"
 
 namespace mnv {
 
@@ -128,45 +129,56 @@ struct AccelView {
 }  // namespace mnv
 
 struct mnv_accel {
-    mnv::AccelView view;
-    uint32_t *nodes = nullptr;
-    uint8_t *rows = nullptr;
-    uint32_t *grid = nullptr;
-    uint32_t *grid_vox = nullptr;
-    uint32_t *grid2 = nullptr;
-    uint32_t *grid2_vox = nullptr;
-    uint32_t *grid2i = nullptr;           // [2^L2]^3
-    uint2 *recs = nullptr;                // [reserved][8]
-    uint32_t *shadow_nodes = nullptr;     // MNV_ABLATE shadow loads (test-hook build, diagnostics instantiation): copies of nodes / rows at other
-    uint8_t *shadow_rows = nullptr;       // addresses, read with the same access pattern to attribute the HBM traffic by array
-    uint32_t *nodes_spare = nullptr;      // second set of nodes / rows / depth, allocated by the first prune (accel_apply_prune writes the
-    uint8_t *rows_spare = nullptr;        // survivors out of place, then the sets swap)
-    int32_t *depth_spare = nullptr;
-    int32_t *depth = nullptr;             // [reserved] depth of the voxels of each chunk (root chunk: 1); kept for mnv_accel_refresh
-    int32_t *flags = nullptr;             // [8] device scratch of refresh: changed, deepest depth, grids dirty, shallowest voxel, patch items (appended / changed)
-    uint32_t *patch_prefix = nullptr;     // refresh: first patch item of every affected voxel (grow-only)
-    size_t patch_prefix_words = 0;
-    int64_t reserved = 0;                 // chunks the nodes / rows / depth arrays have room for
-    unsigned long long *stats = nullptr;  // MNV_STATS=1 diagnostics
-    uint32_t *fault_dev = nullptr;        // [1] guided_fused2_kernel: spin-waits abandoned by the watchdog since creation (always counted, with or without
-    uint32_t *fault_host = nullptr;       // mnv_set_fused_diag); pinned mirror, refreshed behind every fused launch -- mnv_accel_fused_faults
-    uint32_t fault_reported = 0;          // faults already answered with MNV_E_FAULT
-    uint32_t *line_bits = nullptr;        // MNV_FOOTPRINT=<file> diagnostics: one bit per 128-byte line of grid2i / grid2, recs, nodes, rows, grid2_vox, grid_vox
-    uint32_t line_base[7] = {};           // first line of each of those regions in the bitmap; [6] = all lines
-    unsigned long long *timeline = nullptr;  // MNV_TIMELINE=<file> diagnostics: tile / wavefront time stamps of the last launch
-    size_t timeline_bytes = 0, timeline_tiles = 0, timeline_waves = 0, timeline_tiles_per_frame = 0;
+    mnv::AccelView view;                       // what frames read: pointers into the owners below, set by publish_view() alone
+    mnv::Buffer<uint32_t> nodes;
+    mnv::Buffer<uint8_t> rows;
+    mnv::Buffer<uint32_t> grid, grid_vox, grid2, grid2_vox;
+    mnv::Buffer<uint32_t> grid2i;              // [2^L2]^3
+    mnv::Buffer<uint2> recs;                   // [reserved][8]
+    mnv::Buffer<uint8_t> shadow_nodes;         // MNV_ABLATE shadow loads (test-hook build, diagnostics instantiation): copies of nodes (or recs) / rows at
+    mnv::Buffer<uint8_t> shadow_rows;          // other addresses, read with the same access pattern to attribute the HBM traffic by array
+    mnv::Buffer<uint32_t> nodes_spare;         // second set of nodes / rows / depth, allocated by the first prune (accel_apply_prune writes the
+    mnv::Buffer<uint8_t> rows_spare;           // survivors out of place, then the sets swap)
+    mnv::Buffer<int32_t> depth_spare;
+    mnv::Buffer<int32_t> depth;                // [reserved] depth of the voxels of each chunk (root chunk: 1); kept for mnv_accel_refresh
+    mnv::Buffer<int32_t> flags;                // [8] device scratch of refresh: changed, deepest depth, grids dirty, shallowest voxel, patch items (appended / changed)
+    mnv::Buffer<uint32_t> patch_prefix;        // refresh: first patch item of every affected voxel (grow-only)
+    int64_t reserved = 0;                      // chunks the nodes / rows / depth arrays have room for
+    mnv::Buffer<unsigned long long> stats;     // MNV_STATS=1 diagnostics
+    mnv::Mirrored<uint32_t> fault;             // [1] guided_fused2_kernel: spin-waits abandoned by the watchdog since creation (always counted, with or without
+                                               // mnv_set_fused_diag); the pinned mirror is refreshed behind every fused launch -- mnv_accel_fused_faults
+    uint32_t fault_reported = 0;               // faults already answered with MNV_E_FAULT
+    mnv::Buffer<uint32_t> line_bits;           // MNV_FOOTPRINT=<file> diagnostics: one bit per 128-byte line of grid2i / grid2, recs, nodes, rows, grid2_vox, grid_vox
+    uint32_t line_base[7] = {};                // first line of each of those regions in the bitmap; [6] = all lines
+    mnv::Buffer<unsigned long long> timeline;  // MNV_TIMELINE=<file> diagnostics: tile / wavefront time stamps of the last launch
+    size_t timeline_tiles = 0, timeline_waves = 0, timeline_tiles_per_frame = 0;
     // per-launch slots: [kNumQueues] ray-queue heads (64 B apart; a queue spans the frames of a batch) + [n_frames] camera blocks,
     // written on the launch stream by stage_launch_kernel; kSlots launches may be in flight
-    uint8_t *slots_dev = nullptr;
+    mnv::Buffer<uint8_t> slots_dev;
     std::mutex launch_mutex;              // guards the three slot fields below (launch_accel)
     std::atomic<uint32_t> slot_counter{0};
-    hipEvent_t slot_done[mnv::kSlots] = {};  // recorded after the launch that used the slot
+    mnv::Event slot_done[mnv::kSlots];    // recorded after the launch that used the slot
     bool slot_used[mnv::kSlots] = {};
     std::atomic<int> colour_math{0};      // mnv_accel_set_colour_math: 0 exact (bit-identical to the oracle), 1 hardware exp2 / rcp in the colour sigmoid
     std::atomic<int> fused_kernel{0};     // mnv_accel_set_fused_kernel: 0 = the first that fits, 2 = producer / consumer wavefronts, 1 = one role
     std::atomic<unsigned long long *> fused_diag{nullptr};  // mnv_accel_set_fused_diag: 32 device words the fused kernels add their clocks / counts to
-    size_t bytes = 0;
+    size_t bytes = 0;            // mnv_accel_device_bytes: frame_bytes() at the last build, or at the refresh that allocated the records
+    int64_t built_capacity = 0;  // chunks of the tree at the last build: what frame_bytes() counts of nodes / rows (not the reserve, not appended chunks)
     int device = 0;
     int num_cus = 0;     // units the persistent launch fills (mnv_accel_set_cu_budget)
     int device_cus = 0;  // units of the device
+
+    // The one place that points the view at the owners.  `inline_words` / `records`: whether frames may read grid2i / recs (a build's
+    // want_inline / want_recs; refresh and prune pass what the view showed before).
+    void publish_view(bool inline_words, bool records) {
+        view.nodes = nodes.get(), view.rows = rows.get();
+        view.grid = grid.get(), view.grid_vox = grid_vox.get();
+        view.grid2 = grid2.get(), view.grid2_vox = grid2_vox.get();
+        view.grid2i = inline_words ? grid2i.get() : nullptr;
+        view.recs = records ? recs.get() : nullptr;
+    }
+    // the arrays a frame reads, as they exist (spares, depths, flags, slots and diagnostics are not counted)
+    size_t frame_bytes() const {
+        return (size_t)built_capacity * 8 * (4 + (size_t)view.row_bytes) + grid.bytes() + grid_vox.bytes() + grid2.bytes() + grid2_vox.bytes() + grid2i.bytes() + recs.bytes();
+    }
 };

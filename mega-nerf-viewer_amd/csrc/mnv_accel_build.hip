@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #include "mnv_accel_launch.h"
@@ -180,38 +181,36 @@ int accel_build(mnv_accel *a, const mnv_tree_view *t, hipStream_t stream) {
     const int b = (t->format == MNV_FORMAT_SH && t->basis_dim >= 0) ? t->basis_dim : -1;
     const int64_t cap = t->capacity, nvox = cap * 8, max_capacity = a->reserved;
     const int row_bytes = row_bytes_for(b);
-    int32_t *depth = a->depth, *changed = a->flags;
-    auto fail = [&](int code) { return code; };
+    int32_t *depth = a->depth.get(), *changed = a->flags.get();
     // chunk depths: root chunk holds depth-1 voxels
-    if ((rc = check_hip(hipMemsetAsync(depth, 0, max_capacity * 4, stream), "memset depth"))) return fail(rc);
+    if ((rc = check_hip(hipMemsetAsync(depth, 0, max_capacity * 4, stream), "memset depth"))) return rc;
     const int32_t one = 1;
-    if ((rc = check_hip(hipMemcpyAsync(depth, &one, 4, hipMemcpyHostToDevice, stream), "seed depth"))) return fail(rc);
+    if ((rc = check_hip(hipMemcpyAsync(depth, &one, 4, hipMemcpyHostToDevice, stream), "seed depth"))) return rc;
     const unsigned nb = (unsigned)((nvox + 255) / 256);
     int max_depth = 1;
     for (int level = 1; level < 25; ++level) {
         int32_t flag = 0;
-        if ((rc = check_hip(hipMemsetAsync(changed, 0, 4, stream), "memset flag"))) return fail(rc);
+        if ((rc = check_hip(hipMemsetAsync(changed, 0, 4, stream), "memset flag"))) return rc;
         hipLaunchKernelGGL(accel_depth_pass, dim3(nb), dim3(256), 0, stream, t->child, depth, t->capacity, level, changed);
-        if ((rc = check_hip(hipMemcpyAsync(&flag, changed, 4, hipMemcpyDeviceToHost, stream), "read flag"))) return fail(rc);
-        if ((rc = check_hip(hipStreamSynchronize(stream), "accel_depth_pass"))) return fail(rc);
+        if ((rc = check_hip(hipMemcpyAsync(&flag, changed, 4, hipMemcpyDeviceToHost, stream), "read flag"))) return rc;
+        if ((rc = check_hip(hipStreamSynchronize(stream), "accel_depth_pass"))) return rc;
         if (!flag) break;
         max_depth = level + 1;
     }
-    if (max_depth > 23) return fail(set_error(MNV_E_UNSUPPORTED, "accel supports trees up to depth 23; use mnv_render_voxels"));
-    hipLaunchKernelGGL(accel_pack_nodes, dim3(nb), dim3(256), 0, stream, t->child, t->data, depth, a->nodes, t->capacity, t->data_dim);
+    if (max_depth > 23) return set_error(MNV_E_UNSUPPORTED, "accel supports trees up to depth 23; use mnv_render_voxels");
+    hipLaunchKernelGGL(accel_pack_nodes, dim3(nb), dim3(256), 0, stream, t->child, t->data, depth, a->nodes.get(), t->capacity, t->data_dim);
     hipLaunchKernelGGL(accel_pack_rows, dim3((unsigned)((nvox * 3 + 255) / 256)), dim3(256), 0, stream, t->data,
-                       reinterpret_cast<uint16_t *>(a->rows), nvox, t->data_dim, b > 0 ? b : 1, chan_bytes_for(b) / 2,
+                       reinterpret_cast<uint16_t *>(a->rows.get()), nvox, t->data_dim, b > 0 ? b : 1, chan_bytes_for(b) / 2,
                        row_bytes / 2);
     int L = max_depth < kMaxGridLevel ? max_depth : kMaxGridLevel;
     const int64_t gcells = (int64_t)1 << (3 * L);
     if (!a->grid || a->view.grid_level != L) {
-        if (a->grid) (void)hipFree(a->grid);
-        if (a->grid_vox) (void)hipFree(a->grid_vox);
-        a->grid = a->grid_vox = nullptr;
-        if ((rc = check_hip(hipMalloc((void **)&a->grid, gcells * 4), "hipMalloc(grid)"))) return fail(rc);
-        if ((rc = check_hip(hipMalloc((void **)&a->grid_vox, gcells * 4), "hipMalloc(grid_vox)"))) return fail(rc);
+        a->grid.reset();
+        a->grid_vox.reset();
+        if ((rc = check_hip(a->grid.alloc(gcells), "hipMalloc(grid)"))) return rc;
+        if ((rc = check_hip(a->grid_vox.alloc(gcells), "hipMalloc(grid_vox)"))) return rc;
     }
-    hipLaunchKernelGGL(accel_build_grid, dim3((unsigned)((gcells + 255) / 256)), dim3(256), 0, stream, a->nodes, a->grid, a->grid_vox, L);
+    hipLaunchKernelGGL(accel_build_grid, dim3((unsigned)((gcells + 255) / 256)), dim3(256), 0, stream, a->nodes.get(), a->grid.get(), a->grid_vox.get(), L);
     // second lookup grid at level L2 <= min(max_depth - 1, 9): 8^L2 words per array (64 MiB at level 8,
     // 512 MiB at level 9).  Pick the deepest level whose two arrays stay below max(128 MiB, 2 x the packed
     // tree): HBM is 288 GB, and every level moved into the grid removes a dependent load from deep steps
@@ -224,19 +223,17 @@ int accel_build(mnv_accel *a, const mnv_tree_view *t, hipStream_t stream) {
     if (L2 <= L || L2 < 2) L2 = 0;
     int64_t g2cells = 0;
     if (a->grid2 && a->view.grid2_level != L2) {
-        (void)hipFree(a->grid2);
-        (void)hipFree(a->grid2_vox);
-        a->grid2 = a->grid2_vox = nullptr;
-        if (a->grid2i) (void)hipFree(a->grid2i);
-        a->grid2i = nullptr;
+        a->grid2.reset();
+        a->grid2_vox.reset();
+        a->grid2i.reset();
     }
     if (L2 > 0) {
         g2cells = (int64_t)1 << (3 * L2);
         if (!a->grid2) {
-            if ((rc = check_hip(hipMalloc((void **)&a->grid2, g2cells * 4), "hipMalloc(grid2)"))) return fail(rc);
-            if ((rc = check_hip(hipMalloc((void **)&a->grid2_vox, g2cells * 4), "hipMalloc(grid2_vox)"))) return fail(rc);
+            if ((rc = check_hip(a->grid2.alloc(g2cells), "hipMalloc(grid2)"))) return rc;
+            if ((rc = check_hip(a->grid2_vox.alloc(g2cells), "hipMalloc(grid2_vox)"))) return rc;
         }
-        hipLaunchKernelGGL(accel_build_grid2, dim3((unsigned)((g2cells + 255) / 256)), dim3(256), 0, stream, a->nodes, a->grid2, a->grid2_vox, L2);
+        hipLaunchKernelGGL(accel_build_grid2, dim3((unsigned)((g2cells + 255) / 256)), dim3(256), 0, stream, a->nodes.get(), a->grid2.get(), a->grid2_vox.get(), L2);
     }
     // What frames read instead of node words (mnv_accel_refresh patches both with the tree edit, a prune derives them again):
     //  * grid2i: grid2 with the last level folded into the words of the cells whose chunk holds eight leaves -- a depth-10 tree (cfg2, L2 = 9)
@@ -246,34 +243,24 @@ int accel_build(mnv_accel *a, const mnv_tree_view *t, hipStream_t stream) {
     static const int env_bricks = knob_int(KNOB_BRICK_LEVELS, 3);  // bit 0: inline cell words, bit 1: records
     const bool want_inline = (env_bricks & 1) && L2 > 0, want_recs = (env_bricks & 2) && want_inline && max_depth >= L2 + 2;
     if (want_inline) {
-        if (!a->grid2i && (rc = check_hip(hipMalloc((void **)&a->grid2i, g2cells * 4), "hipMalloc(grid2i)"))) return fail(rc);
+        if (!a->grid2i && (rc = check_hip(a->grid2i.alloc(g2cells), "hipMalloc(grid2i)"))) return rc;
         uint32_t base = 0;
-        if ((rc = min_chunk_of_depth(depth, t->capacity, L2 + 1, a->flags + 6, stream, &base))) return fail(rc);
+        if ((rc = min_chunk_of_depth(depth, t->capacity, L2 + 1, a->flags.get() + 6, stream, &base))) return rc;
         a->view.inline_base = base;
-        launch_build_grid2i(a->nodes, a->grid2, a->grid2i, L2, base, stream);
-    } else if (a->grid2i) {
-        (void)hipFree(a->grid2i);
-        a->grid2i = nullptr;
+        launch_build_grid2i(a->nodes.get(), a->grid2.get(), a->grid2i.get(), L2, base, stream);
+    } else {
+        a->grid2i.reset();
     }
     if (want_recs) {
-        if (!a->recs && (rc = check_hip(hipMalloc((void **)&a->recs, (size_t)max_capacity * kRecWords * 4), "hipMalloc(brick records)"))) return fail(rc);
-        launch_build_recs(a->nodes, depth, a->recs, t->capacity, L2, stream);
-    } else if (a->recs) {
-        (void)hipFree(a->recs);
-        a->recs = nullptr;
+        if (!a->recs && (rc = check_hip(a->recs.alloc((size_t)max_capacity * 8), "hipMalloc(brick records)"))) return rc;
+        launch_build_recs(a->nodes.get(), depth, a->recs.get(), t->capacity, L2, stream);
+    } else {
+        a->recs.reset();
     }
-    if ((rc = check_hip(hipGetLastError(), "accel build launch"))) return fail(rc);
-    if ((rc = check_hip(hipStreamSynchronize(stream), "accel build"))) return fail(rc);
-    a->view.grid2i = want_inline ? a->grid2i : nullptr;
-    a->view.recs = want_recs ? a->recs : nullptr;
-
-    a->view.nodes = a->nodes;
-    a->view.rows = a->rows;
-    a->view.grid = a->grid;
-    a->view.grid_vox = a->grid_vox;
+    if ((rc = check_hip(hipGetLastError(), "accel build launch"))) return rc;
+    if ((rc = check_hip(hipStreamSynchronize(stream), "accel build"))) return rc;
+    a->publish_view(want_inline, want_recs);
     a->view.grid_level = L;
-    a->view.grid2 = a->grid2;
-    a->view.grid2_vox = a->grid2_vox;
     a->view.grid2_level = L2;
     a->view.max_depth = max_depth;
     a->view.row_bytes = row_bytes;
@@ -286,7 +273,8 @@ int accel_build(mnv_accel *a, const mnv_tree_view *t, hipStream_t stream) {
     a->view.basis_dim = t->basis_dim;
     a->view.format = t->format;
     a->view.capacity = t->capacity;
-    a->bytes = (size_t)(nvox * 4 + nvox * row_bytes + gcells * 8 + g2cells * 8) + (a->recs ? (size_t)max_capacity * kRecWords * 4 : 0) + (a->grid2i ? (size_t)g2cells * 4 : 0);
+    a->built_capacity = cap;
+    a->bytes = a->frame_bytes();
     return MNV_OK;
 }
 
@@ -311,36 +299,31 @@ int mnv_accel_create_reserved(const mnv_tree_view *t, int64_t max_capacity, void
     if (b >= 0 && t->data_dim != 3 * b + 1) return set_error(MNV_E_UNSUPPORTED, "accel needs data_dim == 3 * basis_dim + 1");
     if (b < 0 && t->data_dim != 4) return set_error(MNV_E_UNSUPPORTED, "accel needs data_dim == 4 for RGBA rows");
     hipStream_t stream = (hipStream_t)hip_stream;
-    mnv_accel *a = new mnv_accel();
+    std::unique_ptr<mnv_accel> a(new mnv_accel());
     int rc = MNV_OK;
-    auto fail = [&](int code) {
-        mnv_accel_destroy(a);
-        return code;
-    };
-    if ((rc = check_hip(hipGetDevice(&a->device), "hipGetDevice"))) return fail(rc);
+    if ((rc = check_hip(hipGetDevice(&a->device), "hipGetDevice"))) return rc;
     hipDeviceProp_t prop;
-    if ((rc = check_hip(hipGetDeviceProperties(&prop, a->device), "hipGetDeviceProperties"))) return fail(rc);
+    if ((rc = check_hip(hipGetDeviceProperties(&prop, a->device), "hipGetDeviceProperties"))) return rc;
     a->num_cus = a->device_cus = prop.multiProcessorCount;
 
     const int row_bytes = row_bytes_for(b);
     a->reserved = max_capacity;
-    if ((rc = check_hip(hipMalloc((void **)&a->nodes, max_capacity * 8 * 4), "hipMalloc(nodes)"))) return fail(rc);
-    if ((rc = check_hip(hipMalloc((void **)&a->rows, max_capacity * 8 * row_bytes), "hipMalloc(rows)"))) return fail(rc);
-    if ((rc = check_hip(hipMalloc((void **)&a->depth, max_capacity * 4), "hipMalloc(depth)"))) return fail(rc);
-    if ((rc = check_hip(hipMalloc((void **)&a->flags, 32), "hipMalloc(flag)"))) return fail(rc);
-    if ((rc = check_hip(hipMalloc((void **)&a->fault_dev, 4), "hipMalloc(fault)"))) return fail(rc);
-    if ((rc = check_hip(hipMemsetAsync(a->fault_dev, 0, 4, stream), "memset fault"))) return fail(rc);
-    if ((rc = check_hip(hipHostMalloc((void **)&a->fault_host, 4, hipHostMallocDefault), "hipHostMalloc(fault)"))) return fail(rc);
-    *a->fault_host = 0u;
-    if ((rc = check_hip(hipMalloc((void **)&a->slots_dev, (size_t)kSlots * kSlotBytes), "hipMalloc(slots)"))) return fail(rc);
+    if ((rc = check_hip(a->nodes.alloc((size_t)max_capacity * 8), "hipMalloc(nodes)"))) return rc;
+    if ((rc = check_hip(a->rows.alloc((size_t)max_capacity * 8 * row_bytes), "hipMalloc(rows)"))) return rc;
+    if ((rc = check_hip(a->depth.alloc((size_t)max_capacity), "hipMalloc(depth)"))) return rc;
+    if ((rc = check_hip(a->flags.alloc(8), "hipMalloc(flag)"))) return rc;
+    if ((rc = alloc_pair(a->fault, 1, "hipMalloc(fault)", "hipHostMalloc(fault)"))) return rc;
+    if ((rc = check_hip(hipMemsetAsync(a->fault.dev.get(), 0, 4, stream), "memset fault"))) return rc;
+    *a->fault.host.get() = 0u;
+    if ((rc = check_hip(a->slots_dev.alloc((size_t)kSlots * kSlotBytes), "hipMalloc(slots)"))) return rc;
     for (int i = 0; i < kSlots; ++i)
-        if ((rc = check_hip(hipEventCreateWithFlags(&a->slot_done[i], hipEventDisableTiming), "hipEventCreate(slot)"))) return fail(rc);
+        if ((rc = check_hip(a->slot_done[i].create(hipEventDisableTiming), "hipEventCreate(slot)"))) return rc;
 
-    if ((rc = check_hip(hipMalloc((void **)&a->stats, 32 * sizeof(unsigned long long)), "hipMalloc(stats)"))) return fail(rc);
-    if ((rc = check_hip(hipMemsetAsync(a->stats, 0, 32 * sizeof(unsigned long long), stream), "memset stats"))) return fail(rc);
+    if ((rc = check_hip(a->stats.alloc(32), "hipMalloc(stats)"))) return rc;
+    if ((rc = check_hip(hipMemsetAsync(a->stats.get(), 0, a->stats.bytes(), stream), "memset stats"))) return rc;
 
-    if ((rc = accel_build(a, t, stream))) return fail(rc);
-    *out = a;
+    if ((rc = accel_build(a.get(), t, stream))) return rc;
+    *out = a.release();
     return MNV_OK;
 }
 
@@ -358,9 +341,9 @@ void mnv_accel_destroy(mnv_accel *a) {
     if (!a) return;
     if (a->stats && knob_set(KNOB_STATS)) {
         unsigned long long h[16];
-        if (hipMemcpy(h, a->stats, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(h, a->stats.get(), sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
             unsigned long long ph[8] = {};
-            if (hipMemcpy(ph, a->stats + 16, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess && ph[4] > 0)
+            if (hipMemcpy(ph, a->stats.get() + 16, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess && ph[4] > 0)
                 fprintf(stderr, "[mnv phases] share of the wavefronts' time (serialised by the stamps): lookup %.3f, step arithmetic + opacity %.3f, row wait %.3f, "
                                 "colour arithmetic %.3f, other (refill, ray set-up, flush, loop) %.3f; wave-steps %llu\n",
                         (double)ph[0] / ph[4], (double)ph[1] / ph[4], (double)ph[2] / ph[4], (double)ph[3] / ph[4], 1.0 - (double)(ph[0] + ph[1] + ph[2] + ph[3]) / ph[4], ph[5]);
@@ -376,7 +359,7 @@ void mnv_accel_destroy(mnv_accel *a) {
         h[0] = a->timeline_tiles;
         h[1] = a->timeline_waves;
         h[2] = a->timeline_tiles_per_frame;
-        if (hipMemcpy(h.data() + 3, a->timeline, words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(h.data() + 3, a->timeline.get(), words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
             if (FILE *f = fopen(knob_str(KNOB_TIMELINE), "wb")) {
                 fwrite(h.data(), 8, h.size(), f);
                 fclose(f);
@@ -387,7 +370,7 @@ void mnv_accel_destroy(mnv_accel *a) {
         // unique 128-byte lines per array, as JSON (tools/footprint.py reads it)
         const size_t words = ((size_t)a->line_base[6] + 31) / 32;
         std::vector<uint32_t> h(words);
-        if (hipMemcpy(h.data(), a->line_bits, words * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(h.data(), a->line_bits.get(), words * 4, hipMemcpyDeviceToHost) == hipSuccess) {
             static const char *names[6] = {"grid2", "records", "nodes", "rows", "grid2_vox", "grid_vox"};
             unsigned long long lines[6] = {};
             for (int r = 0; r < 6; ++r)
@@ -400,31 +383,6 @@ void mnv_accel_destroy(mnv_accel *a) {
             }
         }
     }
-    if (a->line_bits) (void)hipFree(a->line_bits);
-    if (a->timeline) (void)hipFree(a->timeline);
-    if (a->recs) (void)hipFree(a->recs);
-    if (a->grid2i) (void)hipFree(a->grid2i);
-    if (a->shadow_nodes) (void)hipFree(a->shadow_nodes);
-    if (a->shadow_rows) (void)hipFree(a->shadow_rows);
-    if (a->nodes_spare) (void)hipFree(a->nodes_spare);
-    if (a->rows_spare) (void)hipFree(a->rows_spare);
-    if (a->depth_spare) (void)hipFree(a->depth_spare);
-    if (a->stats) (void)hipFree(a->stats);
-    if (a->depth) (void)hipFree(a->depth);
-    if (a->flags) (void)hipFree(a->flags);
-    if (a->patch_prefix) (void)hipFree(a->patch_prefix);
-    if (a->fault_dev) (void)hipFree(a->fault_dev);
-    if (a->fault_host) (void)hipHostFree(a->fault_host);
-    if (a->nodes) (void)hipFree(a->nodes);
-    if (a->rows) (void)hipFree(a->rows);
-    if (a->grid) (void)hipFree(a->grid);
-    if (a->grid_vox) (void)hipFree(a->grid_vox);
-    if (a->grid2) (void)hipFree(a->grid2);
-    if (a->grid2_vox) (void)hipFree(a->grid2_vox);
-    if (a->slots_dev) (void)hipFree(a->slots_dev);
-    for (int i = 0; i < kSlots; ++i)
-        if (a->slot_done[i]) (void)hipEventDestroy(a->slot_done[i]);
-
     delete a;
 }
 
@@ -438,16 +396,16 @@ int mnv_accel_lookup_coverage(const mnv_accel *a, int64_t out4[4]) {
     if (a->view.grid2_level <= 0) return MNV_OK;
     mnv_accel *mut = const_cast<mnv_accel *>(a);
     std::lock_guard<std::mutex> view_lock(mut->launch_mutex);
-    unsigned long long *dev = nullptr, h[4] = {};
+    Buffer<unsigned long long> dev;
+    unsigned long long h[4] = {};
     int rc;
-    if ((rc = check_hip(hipMalloc((void **)&dev, sizeof(h)), "hipMalloc(coverage)"))) return rc;
-    rc = check_hip(hipMemset(dev, 0, sizeof(h)), "memset coverage");
+    if ((rc = check_hip(dev.alloc(4), "hipMalloc(coverage)"))) return rc;
+    rc = check_hip(hipMemset(dev.get(), 0, sizeof(h)), "memset coverage");
     const int64_t cells = (int64_t)1 << (3 * a->view.grid2_level);
     if (!rc) {
-        hipLaunchKernelGGL(accel_count_coverage, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, a->nodes, a->grid2, a->view.grid2i, cells, dev);
-        rc = check_hip(hipMemcpy(h, dev, sizeof(h), hipMemcpyDeviceToHost), "read coverage");  // (the null stream: behind every launch of the device)
+        hipLaunchKernelGGL(accel_count_coverage, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, a->nodes.get(), a->grid2.get(), a->view.grid2i, cells, dev.get());
+        rc = check_hip(hipMemcpy(h, dev.get(), sizeof(h), hipMemcpyDeviceToHost), "read coverage");  // (the null stream: behind every launch of the device)
     }
-    (void)hipFree(dev);
     if (rc) return rc;
     out4[0] = (int64_t)h[0];
     out4[1] = (int64_t)h[1];

@@ -142,7 +142,7 @@ static int attach_diagnostics(mnv_accel *mut, AccelLaunch &K, bool rays, bool fu
     static const bool env_stats = knob_set(KNOB_STATS);
     static const char *env_timeline = knob_str(KNOB_TIMELINE);
     static const char *env_footprint = knob_str(KNOB_FOOTPRINT);
-    K.stats = (env_stats || env_ablate || env_timeline || env_footprint) && !rays ? accel->stats : nullptr;  // all four run on the diagnostics instantiation (camera frames only)
+    K.stats = (env_stats || env_ablate || env_timeline || env_footprint) && !rays ? accel->stats.get() : nullptr;  // all four run on the diagnostics instantiation (camera frames only)
     static const int env_stats_level = env_stats ? std::max(1, knob_int(KNOB_STATS, 1)) : 0;
     K.count_stats = env_stats ? env_stats_level : 0;
     if (env_footprint && !fused) {
@@ -158,46 +158,41 @@ static int attach_diagnostics(mnv_accel *mut, AccelLaunch &K, bool rays, bool fu
             }
             mut->line_base[6] = (uint32_t)at;
             const size_t words = (size_t)(at + 31) / 32;
-            if (hipMalloc((void **)&mut->line_bits, words * 4) != hipSuccess) return (int)hipErrorOutOfMemory;
-            (void)hipMemsetAsync(mut->line_bits, 0, words * 4, stream);
+            if (mut->line_bits.alloc(words) != hipSuccess) return (int)hipErrorOutOfMemory;
+            (void)hipMemsetAsync(mut->line_bits.get(), 0, words * 4, stream);
         }
-        K.line_bits = mut->line_bits;
+        K.line_bits = mut->line_bits.get();
         for (int i = 0; i < 6; ++i) K.line_base[i] = mut->line_base[i];
     }
     static const int env_shadow = knob_int(KNOB_SHADOW, 0);
     if (env_shadow & (16 | 32 | 64)) {
         // shadow loads (test-hook build + a -DMNV_SHADOW_MASK variant of the march): copies of the arrays at other addresses, made once
         const size_t nvox = (size_t)accel->reserved * 8;
-        auto shadow = [&](void **dst, const void *src, size_t bytes) -> int {
-            if (*dst || !src) return 0;
-            hipError_t es = hipMalloc(dst, bytes);
-            if (es == hipSuccess) es = hipMemcpyAsync(*dst, src, bytes, hipMemcpyDeviceToDevice, stream);
+        auto shadow = [&](Buffer<uint8_t> &dst, const void *src, size_t bytes) -> int {
+            if (dst || !src) return 0;
+            hipError_t es = dst.alloc(bytes);
+            if (es == hipSuccess) es = hipMemcpyAsync(dst.get(), src, bytes, hipMemcpyDeviceToDevice, stream);
             return (int)es;
         };
         int es = 0;
-        if (env_shadow & 16) es = shadow((void **)&mut->shadow_nodes, accel->nodes, nvox * 4);
-        if (!es && (env_shadow & 32)) es = shadow((void **)&mut->shadow_rows, accel->rows, nvox * (size_t)accel->view.row_bytes);
-        if (!es && (env_shadow & 64) && accel->recs) es = shadow((void **)&mut->shadow_nodes, accel->recs, (size_t)accel->reserved * kRecWords * 4);  // (bits 16 and 64 are not combined)
+        if (env_shadow & 16) es = shadow(mut->shadow_nodes, accel->nodes.get(), nvox * 4);
+        if (!es && (env_shadow & 32)) es = shadow(mut->shadow_rows, accel->rows.get(), nvox * (size_t)accel->view.row_bytes);
+        if (!es && (env_shadow & 64) && accel->recs) es = shadow(mut->shadow_nodes, accel->recs.get(), (size_t)accel->reserved * kRecWords * 4);  // (bits 16 and 64 are not combined)
         if (es) return es;
-        K.shadow_nodes = accel->shadow_nodes;
-        K.shadow_rows = accel->shadow_rows;
-        K.shadow_recs = reinterpret_cast<const uint2 *>(accel->shadow_nodes);
+        K.shadow_nodes = reinterpret_cast<const uint32_t *>(accel->shadow_nodes.get());
+        K.shadow_rows = accel->shadow_rows.get();
+        K.shadow_recs = reinterpret_cast<const uint2 *>(accel->shadow_nodes.get());
     }
     if (env_timeline && K.stats) {
         // (re)allocate the record buffer of this launch; mnv_accel_destroy writes the last launch's records to the file
         const size_t tiles = (size_t)K.n_tiles * (size_t)K.n_frames, waves = (size_t)n_blocks * 4;
         const size_t bytes = (tiles * 4 + waves * 2) * 8;
-        if (mut->timeline_bytes < bytes) {
-            if (mut->timeline) (void)hipFree(mut->timeline);
-            mut->timeline = nullptr;
-            if (hipMalloc((void **)&mut->timeline, bytes) != hipSuccess) return (int)hipErrorOutOfMemory;
-            mut->timeline_bytes = bytes;
-        }
-        (void)hipMemsetAsync(mut->timeline, 0, bytes, stream);
+        if (grow(mut->timeline, bytes / 8, bytes / 8, stream, false) != hipSuccess) return (int)hipErrorOutOfMemory;
+        (void)hipMemsetAsync(mut->timeline.get(), 0, bytes, stream);
         mut->timeline_tiles = tiles;
         mut->timeline_waves = waves;
         mut->timeline_tiles_per_frame = K.n_tiles;
-        K.timeline = mut->timeline;
+        K.timeline = mut->timeline.get();
         K.timeline_tiles = (uint32_t)tiles;
     }
     return 0;
@@ -263,10 +258,10 @@ static int launch_accel(const AccelFrame &R, const FrameParams &P, const CamBloc
     const uint32_t slot = mut->slot_counter.fetch_add(1) % kSlots;
     // a caller that runs more than kSlots launches ahead of the device waits here for the launch that last used the slot
     if (mut->slot_used[slot]) {
-        hipError_t es = hipEventSynchronize(mut->slot_done[slot]);
+        hipError_t es = hipEventSynchronize(mut->slot_done[slot].get());
         if (es != hipSuccess) return (int)es;
     }
-    uint8_t *ds = accel->slots_dev + (size_t)slot * kSlotBytes;
+    uint8_t *ds = accel->slots_dev.get() + (size_t)slot * kSlotBytes;
     const size_t heads_bytes = (size_t)kNumQueues * 64;  // one head per queue; a queue spans the frames of the batch
     K.queue = reinterpret_cast<uint32_t *>(ds);
     CamBlock *dcams = reinterpret_cast<CamBlock *>(ds + heads_bytes);
@@ -300,9 +295,9 @@ static int launch_accel(const AccelFrame &R, const FrameParams &P, const CamBloc
         rc = (int)hipGetLastError();
     }
     if (rc == 0 && R.fused)  // the fault word's pinned mirror follows the frame on its stream (render_accel, mnv_accel_fused_faults)
-        rc = (int)hipMemcpyAsync(mut->fault_host, mut->fault_dev, 4, hipMemcpyDeviceToHost, stream);
+        rc = (int)hipMemcpyAsync(mut->fault.host.get(), mut->fault.dev.get(), 4, hipMemcpyDeviceToHost, stream);
     if (rc == 0) {
-        rc = (int)hipEventRecord(mut->slot_done[slot], stream);
+        rc = (int)hipEventRecord(mut->slot_done[slot].get(), stream);
         mut->slot_used[slot] = true;
     }
     return rc;
@@ -313,7 +308,7 @@ static int launch_accel(const AccelFrame &R, const FrameParams &P, const CamBloc
 static int report_fused_fault(const mnv_accel *accel) {
     mnv_accel *mut = const_cast<mnv_accel *>(accel);
     std::lock_guard<std::mutex> g(mut->launch_mutex);
-    const uint32_t seen = *static_cast<volatile uint32_t *>(mut->fault_host);
+    const uint32_t seen = *static_cast<volatile uint32_t *>(mut->fault.host.get());
     if (seen == mut->fault_reported) return MNV_OK;
     const uint32_t n = seen - mut->fault_reported;
     mut->fault_reported = seen;
@@ -359,9 +354,9 @@ static int render_accel(const AccelFrame &request) {
             return set_error(MNV_E_UNSUPPORTED, "the fused guided-sampling frame supports RGBA and SH1/4/9/16 trees; use the four-step path");
         std::memset(static_cast<void *>(&F), 0, sizeof(F));
         F.S = S;
-        F.frags = R.mlp->frags;
-        F.biases = R.mlp->biases;
-        F.embeddings = R.mlp->embeddings;
+        F.frags = R.mlp->frags.get();
+        F.biases = R.mlp->biases.get();
+        F.embeddings = R.mlp->embeddings.get();
         for (int i = 0; i < 2; ++i) F.grid_dim[i] = R.grid->grid_dim[i];
         for (int i = 0; i < 3; ++i) {
             F.min_position[i] = R.grid->min_position[i];
@@ -506,7 +501,7 @@ int mnv_accel_set_fused_diag(mnv_accel *accel, unsigned long long *words32) {
 int mnv_accel_fused_faults(const mnv_accel *accel, uint32_t *count_out) {
     if (!accel || !count_out) return set_error(MNV_E_INVALID, "null argument");
     uint32_t v = 0;
-    const int rc = check_hip(hipMemcpy(&v, accel->fault_dev, 4, hipMemcpyDeviceToHost), "read fault word");  // waits for the device
+    const int rc = check_hip(hipMemcpy(&v, accel->fault.dev.get(), 4, hipMemcpyDeviceToHost), "read fault word");  // waits for the device
     if (rc) return rc;
     *count_out = v;
     return MNV_OK;

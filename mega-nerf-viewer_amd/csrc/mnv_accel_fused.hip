@@ -17,7 +17,7 @@ int launch_fused(const mnv_accel *accel, const AccelLaunch &K, const FusedGuided
     const bool trk = K.split_track || K.sample_track || K.visited;
     // producer / consumer wavefronts when one sub-module's weights fit a workgroup's LDS beside the rings (at least two workgroups per CU)
     FusedGuided F = fused;
-    F.fault = accel->fault_dev;
+    F.fault = accel->fault.dev.get();
     int slots = kF2NS;  // weight slots: as many as fit beside the rings (at least one per two consumers)
     const int f2_per_cu = (4 * kF2WavesPerSimd) / (kF2NP + kF2NC);  // workgroups per CU the kernel is built for
     while (slots > 1 && (size_t)f2_layout(nb, lds_level, F.S, slots).total * 4 > (size_t)160 * 1024 / f2_per_cu) --slots;

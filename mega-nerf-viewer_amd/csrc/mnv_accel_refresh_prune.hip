@@ -252,18 +252,18 @@ __global__ void accel_verify_lookup(const uint32_t *nodes, const int32_t *depth,
 }
 
 int verify_lookup(mnv_accel *a, hipStream_t stream, const char *where) {
-    int32_t *bad = nullptr, h[5] = {};
+    Buffer<int32_t> bad;
+    int32_t h[5] = {};
     int rc;
-    if ((rc = check_hip(hipMalloc((void **)&bad, sizeof(h)), "hipMalloc(verify)"))) return rc;
-    (void)hipMemsetAsync(bad, 0, sizeof(h), stream);
+    if ((rc = check_hip(bad.alloc(5), "hipMalloc(verify)"))) return rc;
+    (void)hipMemsetAsync(bad.get(), 0, sizeof(h), stream);
     const int L2 = a->view.grid2_level;
     int64_t n = std::max<int64_t>((int64_t)1 << (3 * a->view.grid_level), (int64_t)a->view.capacity * 8);
     if (L2 > 0) n = std::max<int64_t>(n, (int64_t)1 << (3 * L2));
-    hipLaunchKernelGGL(accel_verify_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a->nodes, a->depth, a->grid, a->grid_vox, a->view.grid_level,
-                       a->grid2, a->grid2_vox, a->view.grid2i, a->view.recs, L2, a->view.capacity, a->view.inline_base, bad);
-    rc = check_hip(hipMemcpyAsync(h, bad, sizeof(h), hipMemcpyDeviceToHost, stream), "verify read");
+    hipLaunchKernelGGL(accel_verify_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a->nodes.get(), a->depth.get(), a->grid.get(), a->grid_vox.get(),
+                       a->view.grid_level, a->grid2.get(), a->grid2_vox.get(), a->view.grid2i, a->view.recs, L2, a->view.capacity, a->view.inline_base, bad.get());
+    rc = check_hip(hipMemcpyAsync(h, bad.get(), sizeof(h), hipMemcpyDeviceToHost, stream), "verify read");
     if (!rc) rc = check_hip(hipStreamSynchronize(stream), "verify");
-    (void)hipFree(bad);
     if (rc) return rc;
     if (h[0] | h[1] | h[2] | h[3] | h[4]) {
         fprintf(stderr, "[mnv verify] %s: patched lookup words differ from a fresh derivation: grid2 %d, grid2_vox %d, grid2i %d, records %d, grid %d\n", where,
@@ -347,45 +347,44 @@ int accel_apply_prune(mnv_accel *a, const int32_t *parent, const uint16_t *data,
     int rc;
     const int64_t reserved = a->reserved;
     const int row_bytes = a->view.row_bytes;
-    if (!a->nodes_spare) {  // second set of the per-voxel arrays: the survivors are written out of place, then the sets swap
-        if ((rc = check_hip(hipMalloc((void **)&a->nodes_spare, reserved * 8 * 4), "hipMalloc(nodes spare)"))) return rc;
-        if ((rc = check_hip(hipMalloc((void **)&a->rows_spare, reserved * 8 * row_bytes), "hipMalloc(rows spare)"))) return rc;
-        if ((rc = check_hip(hipMalloc((void **)&a->depth_spare, reserved * 4), "hipMalloc(depth spare)"))) return rc;
-    }
-    if ((rc = check_hip(hipMemsetAsync(a->depth_spare, 0, reserved * 4, stream), "memset depth"))) return rc;
-    const int64_t nvox = (int64_t)old_capacity * 8;
-    hipLaunchKernelGGL(accel_prune_nodes, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, stream, a->nodes, a->depth, data, data_dim, to_delete, shifts,
-                       old_capacity, a->nodes_spare, a->depth_spare);
     const int32_t quads = 8 * row_bytes / 16;
     if (8 * row_bytes % 16) return set_error(MNV_E_UNSUPPORTED, "row size");
+    if (!a->nodes_spare || !a->rows_spare || !a->depth_spare) {  // second set of the per-voxel arrays: the survivors are written out of place, then the sets swap
+        if ((rc = check_hip(a->nodes_spare.alloc((size_t)reserved * 8), "hipMalloc(nodes spare)"))) return rc;
+        if ((rc = check_hip(a->rows_spare.alloc((size_t)reserved * 8 * row_bytes), "hipMalloc(rows spare)"))) return rc;
+        if ((rc = check_hip(a->depth_spare.alloc((size_t)reserved), "hipMalloc(depth spare)"))) return rc;
+    }
+    if ((rc = check_hip(hipMemsetAsync(a->depth_spare.get(), 0, reserved * 4, stream), "memset depth"))) return rc;
+    const int64_t nvox = (int64_t)old_capacity * 8;
+    hipLaunchKernelGGL(accel_prune_nodes, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, stream, a->nodes.get(), a->depth.get(), data, data_dim, to_delete,
+                       shifts, old_capacity, a->nodes_spare.get(), a->depth_spare.get());
     const int64_t nq = (int64_t)old_capacity * quads;
-    hipLaunchKernelGGL(accel_prune_rows, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const uint4 *>(a->rows), to_delete, shifts,
-                       old_capacity, quads, reinterpret_cast<uint4 *>(a->rows_spare));
+    hipLaunchKernelGGL(accel_prune_rows, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const uint4 *>(a->rows.get()), to_delete,
+                       shifts, old_capacity, quads, reinterpret_cast<uint4 *>(a->rows_spare.get()));
     const int64_t gcells = (int64_t)1 << (3 * a->view.grid_level);
-    hipLaunchKernelGGL(accel_prune_grid, dim3((unsigned)((gcells + 255) / 256)), dim3(256), 0, stream, a->grid, a->grid_vox, gcells, parent, a->depth, data,
+    hipLaunchKernelGGL(accel_prune_grid, dim3((unsigned)((gcells + 255) / 256)), dim3(256), 0, stream, a->grid.get(), a->grid_vox.get(), gcells, parent, a->depth.get(), data,
                        data_dim, to_delete, shifts);
     if (a->view.grid2_level > 0) {
         const int64_t g2 = (int64_t)1 << (3 * a->view.grid2_level);
-        hipLaunchKernelGGL(accel_prune_grid, dim3((unsigned)((g2 + 255) / 256)), dim3(256), 0, stream, a->grid2, a->grid2_vox, g2, parent, a->depth, data,
+        hipLaunchKernelGGL(accel_prune_grid, dim3((unsigned)((g2 + 255) / 256)), dim3(256), 0, stream, a->grid2.get(), a->grid2_vox.get(), g2, parent, a->depth.get(), data,
                            data_dim, to_delete, shifts);
     }
     if ((rc = check_hip(hipGetLastError(), "accel prune launch"))) return rc;
-    std::swap(a->nodes, a->nodes_spare);
-    std::swap(a->rows, a->rows_spare);
-    std::swap(a->depth, a->depth_spare);
-    a->view.nodes = a->nodes;
-    a->view.rows = a->rows;
+    a->nodes.swap(a->nodes_spare);
+    a->rows.swap(a->rows_spare);
+    a->depth.swap(a->depth_spare);
+    a->publish_view(a->view.grid2i != nullptr, a->view.recs != nullptr);
     a->view.capacity = old_capacity - n_deleted;  // max_depth stays an upper bound (the march only needs pos * 2^max_depth < 2^24)
     // inline cell words and brick records: derived again from the renumbered node words and the patched grid, on the same stream (a pass over
     // the grid like accel_prune_grid's own; prunes are rare)
     if (a->view.grid2i) {
         // (the chunks were renumbered: the 22-bit chunk field is re-based on the smallest number of depth L2 + 1 there is now)
         uint32_t base = 0;
-        if ((rc = min_chunk_of_depth(a->depth, a->view.capacity, a->view.grid2_level + 1, a->flags + 6, stream, &base))) return rc;
+        if ((rc = min_chunk_of_depth(a->depth.get(), a->view.capacity, a->view.grid2_level + 1, a->flags.get() + 6, stream, &base))) return rc;
         a->view.inline_base = base;
-        launch_build_grid2i(a->nodes, a->grid2, a->grid2i, a->view.grid2_level, base, stream);
+        launch_build_grid2i(a->nodes.get(), a->grid2.get(), a->grid2i.get(), a->view.grid2_level, base, stream);
     }
-    if (a->view.recs) launch_build_recs(a->nodes, a->depth, a->recs, a->view.capacity, a->view.grid2_level, stream);
+    if (a->view.recs) launch_build_recs(a->nodes.get(), a->depth.get(), a->recs.get(), a->view.capacity, a->view.grid2_level, stream);
     if ((rc = check_hip(hipGetLastError(), "accel prune launch"))) return rc;
     static const int dbg = knob_int(KNOB_REFRESH_DEBUG, 0);
     if (dbg >= 2) return verify_lookup(a, stream, "prune");
@@ -417,7 +416,7 @@ int mnv_accel_refresh(mnv_accel *a, const mnv_tree_view *t, int32_t old_capacity
     const int grid_depth = a->view.grid_level;  // leaves this shallow sit in the small (LDS-staged) lookup grid
     // [1] deepest depth, [2] the small lookup grid is affected, [3] shallowest affected voxel, [4] / [5] patch items of the appended / changed voxels
     int32_t h[8] = {0, a->view.max_depth, 0, 127, 0, 0, 0, 0};
-    if ((rc = check_hip(hipMemcpyAsync(a->flags, h, sizeof(h), hipMemcpyHostToDevice, stream), "refresh flags"))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(a->flags.get(), h, sizeof(h), hipMemcpyHostToDevice, stream), "refresh flags"))) return rc;
     const int32_t n_new = t->capacity - old_capacity;
     // the level-L2 grid: only the cells the affected voxels cover, cut into items (accel_patch_grid2).  The refresh kernels count every
     // voxel's items, accel_patch_plan scans the counts, the totals come back with the flags.
@@ -427,35 +426,26 @@ int mnv_accel_refresh(mnv_accel *a, const mnv_tree_view *t, int32_t old_capacity
     uint32_t *prefix_new = nullptr, *prefix_changed = nullptr;
     if (patch_new || patch_changed) {
         const size_t words = (size_t)n_new + 1 + (size_t)(patch_changed ? n_changed : 0) + 1;
-        if (a->patch_prefix_words < words) {
-            if (a->patch_prefix) {
-                if ((rc = check_hip(hipStreamSynchronize(stream), "accel refresh"))) return rc;
-                (void)hipFree(a->patch_prefix);
-                a->patch_prefix = nullptr;
-                a->patch_prefix_words = 0;
-            }
-            if ((rc = check_hip(hipMalloc((void **)&a->patch_prefix, (words + words / 4) * 4), "hipMalloc(patch items)"))) return rc;
-            a->patch_prefix_words = words + words / 4;
-        }
-        if (patch_new) prefix_new = a->patch_prefix;
-        if (patch_changed) prefix_changed = a->patch_prefix + n_new + 1;
+        if ((rc = check_hip(grow(a->patch_prefix, words, words + words / 4, stream, true), "hipMalloc(patch items)"))) return rc;
+        if (patch_new) prefix_new = a->patch_prefix.get();
+        if (patch_changed) prefix_changed = a->patch_prefix.get() + n_new + 1;
     }
     if (n_new > 0) {
-        hipLaunchKernelGGL(accel_refresh_depth, dim3((n_new + 255) / 256), dim3(256), 0, stream, t->parent, a->depth, old_capacity, t->capacity, a->flags);
+        hipLaunchKernelGGL(accel_refresh_depth, dim3((n_new + 255) / 256), dim3(256), 0, stream, t->parent, a->depth.get(), old_capacity, t->capacity, a->flags.get());
         const int64_t nv = (int64_t)n_new * 8;
-        hipLaunchKernelGGL(accel_refresh_nodes, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, t->child, t->parent, t->data, a->depth, a->nodes,
-                           old_capacity, t->capacity, t->data_dim, grid_depth, a->flags, prefix_new, L2, L2i);
-        launch_pack_rows(t->data + (int64_t)old_capacity * 8 * t->data_dim, reinterpret_cast<uint16_t *>(a->rows) + (int64_t)old_capacity * 8 * row_halfs, nv,
+        hipLaunchKernelGGL(accel_refresh_nodes, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, t->child, t->parent, t->data, a->depth.get(), a->nodes.get(),
+                           old_capacity, t->capacity, t->data_dim, grid_depth, a->flags.get(), prefix_new, L2, L2i);
+        launch_pack_rows(t->data + (int64_t)old_capacity * 8 * t->data_dim, reinterpret_cast<uint16_t *>(a->rows.get()) + (int64_t)old_capacity * 8 * row_halfs, nv,
                          t->data_dim, per_chan, chan_halfs, row_halfs, stream);
-        if (patch_new) hipLaunchKernelGGL(accel_patch_plan, dim3(1), dim3(1024), 0, stream, n_new, prefix_new, a->flags + 4);
+        if (patch_new) hipLaunchKernelGGL(accel_patch_plan, dim3(1), dim3(1024), 0, stream, n_new, prefix_new, a->flags.get() + 4);
     }
     if (n_changed > 0) {
-        hipLaunchKernelGGL(accel_refresh_changed, dim3((n_changed + 255) / 256), dim3(256), 0, stream, changed_nodes, n_changed, t->child, t->data, a->depth,
-                           a->nodes, reinterpret_cast<uint16_t *>(a->rows), t->data_dim, per_chan, chan_halfs, row_halfs, grid_depth, a->flags, prefix_changed,
+        hipLaunchKernelGGL(accel_refresh_changed, dim3((n_changed + 255) / 256), dim3(256), 0, stream, changed_nodes, n_changed, t->child, t->data, a->depth.get(),
+                           a->nodes.get(), reinterpret_cast<uint16_t *>(a->rows.get()), t->data_dim, per_chan, chan_halfs, row_halfs, grid_depth, a->flags.get(), prefix_changed,
                            L2, L2i);
-        if (patch_changed) hipLaunchKernelGGL(accel_patch_plan, dim3(1), dim3(1024), 0, stream, n_changed, prefix_changed, a->flags + 5);
+        if (patch_changed) hipLaunchKernelGGL(accel_patch_plan, dim3(1), dim3(1024), 0, stream, n_changed, prefix_changed, a->flags.get() + 5);
     }
-    if ((rc = check_hip(hipMemcpyAsync(h, a->flags, sizeof(h), hipMemcpyDeviceToHost, stream), "read flags"))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(h, a->flags.get(), sizeof(h), hipMemcpyDeviceToHost, stream), "read flags"))) return rc;
     if ((rc = check_hip(hipStreamSynchronize(stream), "accel refresh"))) return rc;
     if (h[1] > 23) {
         // nodes, rows and depths are patched, the lookup grids are not: no frame may read them as they are (mnv_accel_rebuild refuses the tree too)
@@ -465,7 +455,7 @@ int mnv_accel_refresh(mnv_accel *a, const mnv_tree_view *t, int32_t old_capacity
         return set_error(MNV_E_UNSUPPORTED, "accel supports trees up to depth 23; use mnv_render_voxels");
     }
     if (h[2]) {  // an affected voxel is held by the small lookup grid: 32^3 cells at most, rebuilt whole
-        launch_build_grid(a->nodes, a->grid, a->grid_vox, a->view.grid_level, stream);
+        launch_build_grid(a->nodes.get(), a->grid.get(), a->grid_vox.get(), a->view.grid_level, stream);
     }
     if (a->view.grid2_level > 0) {
         static const int dbg = knob_int(KNOB_REFRESH_DEBUG, 0);
@@ -473,13 +463,13 @@ int mnv_accel_refresh(mnv_accel *a, const mnv_tree_view *t, int32_t old_capacity
             fprintf(stderr, "[mnv refresh] n_new %d n_changed %d shallowest %d grid2_level %d patch items %d + %d\n", n_new, n_changed, h[3], a->view.grid2_level, h[4], h[5]);
         if (h[4] > 0)
             hipLaunchKernelGGL(accel_patch_grid2, dim3((unsigned)h[4]), dim3(256), 0, stream, (const int32_t *)nullptr, old_capacity, n_new, prefix_new, t->parent,
-                               a->depth, a->nodes, a->grid2, a->grid2_vox, const_cast<uint32_t *>(a->view.grid2i), a->view.grid2_level, a->view.inline_base);
+                               a->depth.get(), a->nodes.get(), a->grid2.get(), a->grid2_vox.get(), const_cast<uint32_t *>(a->view.grid2i), a->view.grid2_level, a->view.inline_base);
         if (h[5] > 0)
-            hipLaunchKernelGGL(accel_patch_grid2, dim3((unsigned)h[5]), dim3(256), 0, stream, changed_nodes, 0, n_changed, prefix_changed, t->parent, a->depth,
-                               a->nodes, a->grid2, a->grid2_vox, const_cast<uint32_t *>(a->view.grid2i), a->view.grid2_level, a->view.inline_base);
+            hipLaunchKernelGGL(accel_patch_grid2, dim3((unsigned)h[5]), dim3(256), 0, stream, changed_nodes, 0, n_changed, prefix_changed, t->parent, a->depth.get(),
+                               a->nodes.get(), a->grid2.get(), a->grid2_vox.get(), const_cast<uint32_t *>(a->view.grid2i), a->view.grid2_level, a->view.inline_base);
         if (n_changed > 0 && !t->parent && h[3] <= L2i) {  // no parent array to walk up: the whole grid
-            if (h[3] <= L2) launch_build_grid2(a->nodes, a->grid2, a->grid2_vox, a->view.grid2_level, stream);
-            if (a->view.grid2i) launch_build_grid2i(a->nodes, a->grid2, a->grid2i, a->view.grid2_level, a->view.inline_base, stream);
+            if (h[3] <= L2) launch_build_grid2(a->nodes.get(), a->grid2.get(), a->grid2_vox.get(), a->view.grid2_level, stream);
+            if (a->view.grid2i) launch_build_grid2i(a->nodes.get(), a->grid2.get(), a->grid2i.get(), a->view.grid2_level, a->view.inline_base, stream);
         }
     }
     a->view.max_depth = std::max(a->view.max_depth, h[1]);
@@ -489,20 +479,20 @@ int mnv_accel_refresh(mnv_accel *a, const mnv_tree_view *t, int32_t old_capacity
     if (a->view.grid2i && (env_bricks & 2) && a->view.max_depth >= L2 + 2) {
         if (!a->view.recs) {
             if (!a->recs) {
-                if ((rc = check_hip(hipMalloc((void **)&a->recs, (size_t)a->reserved * kRecWords * 4), "hipMalloc(brick records)"))) return rc;
-                a->bytes += (size_t)a->reserved * kRecWords * 4;
+                if ((rc = check_hip(a->recs.alloc((size_t)a->reserved * 8), "hipMalloc(brick records)"))) return rc;
+                a->bytes = a->frame_bytes();
             }
-            launch_build_recs(a->nodes, a->depth, a->recs, t->capacity, L2, stream);
-            a->view.recs = a->recs;
+            launch_build_recs(a->nodes.get(), a->depth.get(), a->recs.get(), t->capacity, L2, stream);
+            a->publish_view(true, true);
         } else if (n_changed > 0 && !t->parent) {
-            launch_build_recs(a->nodes, a->depth, a->recs, t->capacity, L2, stream);
+            launch_build_recs(a->nodes.get(), a->depth.get(), a->recs.get(), t->capacity, L2, stream);
         } else {
             if (n_new > 0)
-                hipLaunchKernelGGL(accel_patch_recs, dim3((n_new + 255) / 256), dim3(256), 0, stream, (const int32_t *)nullptr, old_capacity, n_new, t->parent, a->depth,
-                                   a->nodes, a->recs, L2);
+                hipLaunchKernelGGL(accel_patch_recs, dim3((n_new + 255) / 256), dim3(256), 0, stream, (const int32_t *)nullptr, old_capacity, n_new, t->parent, a->depth.get(),
+                                   a->nodes.get(), a->recs.get(), L2);
             if (n_changed > 0)
-                hipLaunchKernelGGL(accel_patch_recs, dim3((n_changed + 255) / 256), dim3(256), 0, stream, changed_nodes, 0, n_changed, t->parent, a->depth, a->nodes,
-                                   a->recs, L2);
+                hipLaunchKernelGGL(accel_patch_recs, dim3((n_changed + 255) / 256), dim3(256), 0, stream, changed_nodes, 0, n_changed, t->parent, a->depth.get(), a->nodes.get(),
+                                   a->recs.get(), L2);
         }
     }
     if ((rc = check_hip(hipGetLastError(), "accel refresh launch"))) return rc;

@@ -31,7 +31,9 @@
 
 #include "mnv_accel_launch.h"
 
+using mnv::Buffer;
 using mnv::check_hip;
+using mnv::Event;
 using mnv::set_error;
 
 namespace {
@@ -458,15 +460,13 @@ int require_device() {
 }  // namespace
 
 struct mnv_surface {
-    float *vert = nullptr;      // device [n_verts][9]
-    uint32_t *faces = nullptr;  // device [n_indices]
+    Buffer<float> vert;      // device [n_verts][9]
+    Buffer<uint32_t> faces;  // device [n_indices]
     int64_t n_verts = 0, n_indices = 0;
     mnv_surface_stats stats{};
 
     ~mnv_surface() {
         if (vert || faces) (void)hipDeviceSynchronize();
-        if (vert) (void)hipFree(vert);
-        if (faces) (void)hipFree(faces);
     }
 };
 
@@ -474,17 +474,10 @@ namespace {
 
 // the per-call scratch and the events that time the passes; freed whatever way extract() leaves
 struct Scratch {
-    uint32_t *flag = nullptr, *pos = nullptr, *list = nullptr, *vcnt = nullptr, *qcnt = nullptr, *fault = nullptr;
-    unsigned long long *mask = nullptr, *voff = nullptr, *qoff = nullptr, *totals = nullptr;
-    void *tmp = nullptr;
-    hipEvent_t ev[6] = {};
-    ~Scratch() {
-        for (void *p : {(void *)flag, (void *)pos, (void *)list, (void *)vcnt, (void *)qcnt, (void *)fault, (void *)mask, (void *)voff, (void *)qoff,
-                        (void *)totals, tmp})
-            if (p) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    Buffer<uint32_t> flag, pos, list, vcnt, qcnt, fault;
+    Buffer<unsigned long long> mask, voff, qoff, totals;
+    Buffer<uint8_t> tmp;
+    Event ev[6];
 };
 
 int extract(const mnv_accel *accel, const mnv_extract_params *prm, hipStream_t stream, mnv_surface *out) {
@@ -495,65 +488,65 @@ int extract(const mnv_accel *accel, const mnv_extract_params *prm, hipStream_t s
     const int64_t n_bricks = (int64_t)1 << (3 * (level - 3));
     Scratch W;
     int rc;
-    for (hipEvent_t &e : W.ev)
-        if ((rc = check_hip(hipEventCreate(&e), "hipEventCreate"))) return rc;
+    for (Event &e : W.ev)
+        if ((rc = check_hip(e.create(hipEventDefault), "hipEventCreate"))) return rc;
     size_t tmp32 = 0, tmp64 = 0;
     auto in64 = rocprim::make_transform_iterator((const uint32_t *)nullptr, U32ToU64());
     (void)rocprim::exclusive_scan(nullptr, tmp32, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)n_bricks, rocprim::plus<uint32_t>(), stream);
     (void)rocprim::exclusive_scan(nullptr, tmp64, in64, (unsigned long long *)nullptr, 0ull, (size_t)n_bricks, rocprim::plus<unsigned long long>(), stream);
     const size_t tmp_bytes = std::max(tmp32, tmp64) + 256;
-    if ((rc = check_hip(hipMalloc((void **)&W.flag, (size_t)n_bricks * 4), "hipMalloc(extract flags)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.pos, (size_t)n_bricks * 4), "hipMalloc(extract positions)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.list, (size_t)n_bricks * 4), "hipMalloc(extract list)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.vcnt, (size_t)n_bricks * 4), "hipMalloc(extract counts)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.qcnt, (size_t)n_bricks * 4), "hipMalloc(extract counts)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.mask, (size_t)n_bricks * 64), "hipMalloc(extract masks)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.voff, (size_t)n_bricks * 8), "hipMalloc(extract offsets)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.qoff, (size_t)n_bricks * 8), "hipMalloc(extract offsets)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.totals, 3 * 8), "hipMalloc(extract totals)")) ||
-        (rc = check_hip(hipMalloc((void **)&W.fault, 4), "hipMalloc(extract fault)")) ||
-        (rc = check_hip(hipMalloc(&W.tmp, tmp_bytes), "hipMalloc(extract scan scratch)")))
+    if ((rc = check_hip(W.flag.alloc((size_t)n_bricks), "hipMalloc(extract flags)")) ||
+        (rc = check_hip(W.pos.alloc((size_t)n_bricks), "hipMalloc(extract positions)")) ||
+        (rc = check_hip(W.list.alloc((size_t)n_bricks), "hipMalloc(extract list)")) ||
+        (rc = check_hip(W.vcnt.alloc((size_t)n_bricks), "hipMalloc(extract counts)")) ||
+        (rc = check_hip(W.qcnt.alloc((size_t)n_bricks), "hipMalloc(extract counts)")) ||
+        (rc = check_hip(W.mask.alloc((size_t)n_bricks * 8), "hipMalloc(extract masks)")) ||
+        (rc = check_hip(W.voff.alloc((size_t)n_bricks), "hipMalloc(extract offsets)")) ||
+        (rc = check_hip(W.qoff.alloc((size_t)n_bricks), "hipMalloc(extract offsets)")) ||
+        (rc = check_hip(W.totals.alloc(3), "hipMalloc(extract totals)")) ||
+        (rc = check_hip(W.fault.alloc(1), "hipMalloc(extract fault)")) ||
+        (rc = check_hip(W.tmp.alloc(tmp_bytes), "hipMalloc(extract scan scratch)")))
         return rc;
-    if ((rc = check_hip(hipMemsetAsync(W.fault, 0, 4, stream), "extract memset")) ||
-        (rc = check_hip(hipMemsetAsync(W.vcnt, 0, (size_t)n_bricks * 4, stream), "extract memset")) ||
-        (rc = check_hip(hipMemsetAsync(W.qcnt, 0, (size_t)n_bricks * 4, stream), "extract memset")) ||
-        (rc = check_hip(hipMemsetAsync(W.mask, 0, (size_t)n_bricks * 64, stream), "extract memset")))
+    if ((rc = check_hip(hipMemsetAsync(W.fault.get(), 0, 4, stream), "extract memset")) ||
+        (rc = check_hip(hipMemsetAsync(W.vcnt.get(), 0, (size_t)n_bricks * 4, stream), "extract memset")) ||
+        (rc = check_hip(hipMemsetAsync(W.qcnt.get(), 0, (size_t)n_bricks * 4, stream), "extract memset")) ||
+        (rc = check_hip(hipMemsetAsync(W.mask.get(), 0, (size_t)n_bricks * 64, stream), "extract memset")))
         return rc;
     // (a) candidates, compacted in ascending brick order
-    (void)hipEventRecord(W.ev[0], stream);
-    hipLaunchKernelGGL(candidate_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, stream, T, level, prm->iso, all ? 1 : 0, n_bricks, W.flag, W.fault);
+    (void)hipEventRecord(W.ev[0].get(), stream);
+    hipLaunchKernelGGL(candidate_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, stream, T, level, prm->iso, all ? 1 : 0, n_bricks, W.flag.get(), W.fault.get());
     size_t t = tmp_bytes;
-    if ((rc = check_hip(rocprim::exclusive_scan(W.tmp, t, (const uint32_t *)W.flag, W.pos, 0u, (size_t)n_bricks, rocprim::plus<uint32_t>(), stream),
+    if ((rc = check_hip(rocprim::exclusive_scan(W.tmp.get(), t, (const uint32_t *)W.flag.get(), W.pos.get(), 0u, (size_t)n_bricks, rocprim::plus<uint32_t>(), stream),
                         "exclusive_scan(candidates)")))
         return rc;
-    hipLaunchKernelGGL(candidate_list_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, stream, W.flag, W.pos, n_bricks, W.list, W.totals);
-    (void)hipEventRecord(W.ev[1], stream);
+    hipLaunchKernelGGL(candidate_list_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, stream, W.flag.get(), W.pos.get(), n_bricks, W.list.get(), W.totals.get());
+    (void)hipEventRecord(W.ev[1].get(), stream);
     unsigned long long totals[3] = {0, 0, 0};
     uint32_t fault = 0;
     if ((rc = check_hip(hipGetLastError(), "extract candidate pass")) ||
-        (rc = check_hip(hipMemcpyAsync(totals, W.totals, 8, hipMemcpyDeviceToHost, stream), "read candidate count")) ||
+        (rc = check_hip(hipMemcpyAsync(totals, W.totals.get(), 8, hipMemcpyDeviceToHost, stream), "read candidate count")) ||
         (rc = check_hip(hipStreamSynchronize(stream), "extract candidate pass")))
         return rc;
     const int64_t n_cand = (int64_t)totals[0];
     if (n_cand < 0 || n_cand > n_bricks) return set_error(MNV_E_INVALID, "mnv_extract_surface: candidate count out of range");
     // (b) count, (c) scans
-    if (n_cand > 0) hipLaunchKernelGGL(count_kernel, dim3((unsigned)n_cand), dim3(256), 0, stream, T, level, prm->iso, W.list, W.mask, W.vcnt, W.qcnt, W.fault);
-    (void)hipEventRecord(W.ev[2], stream);
+    if (n_cand > 0) hipLaunchKernelGGL(count_kernel, dim3((unsigned)n_cand), dim3(256), 0, stream, T, level, prm->iso, W.list.get(), W.mask.get(), W.vcnt.get(), W.qcnt.get(), W.fault.get());
+    (void)hipEventRecord(W.ev[2].get(), stream);
     t = tmp_bytes;
-    if ((rc = check_hip(rocprim::exclusive_scan(W.tmp, t, rocprim::make_transform_iterator((const uint32_t *)W.vcnt, U32ToU64()), W.voff, 0ull, (size_t)n_bricks,
+    if ((rc = check_hip(rocprim::exclusive_scan(W.tmp.get(), t, rocprim::make_transform_iterator((const uint32_t *)W.vcnt.get(), U32ToU64()), W.voff.get(), 0ull, (size_t)n_bricks,
                                                 rocprim::plus<unsigned long long>(), stream),
                         "exclusive_scan(vertices)")))
         return rc;
     t = tmp_bytes;
-    if ((rc = check_hip(rocprim::exclusive_scan(W.tmp, t, rocprim::make_transform_iterator((const uint32_t *)W.qcnt, U32ToU64()), W.qoff, 0ull, (size_t)n_bricks,
+    if ((rc = check_hip(rocprim::exclusive_scan(W.tmp.get(), t, rocprim::make_transform_iterator((const uint32_t *)W.qcnt.get(), U32ToU64()), W.qoff.get(), 0ull, (size_t)n_bricks,
                                                 rocprim::plus<unsigned long long>(), stream),
                         "exclusive_scan(quads)")))
         return rc;
-    hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(1), 0, stream, W.voff, W.vcnt, W.qoff, W.qcnt, n_bricks, W.totals);
-    (void)hipEventRecord(W.ev[3], stream);
+    hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(1), 0, stream, W.voff.get(), W.vcnt.get(), W.qoff.get(), W.qcnt.get(), n_bricks, W.totals.get());
+    (void)hipEventRecord(W.ev[3].get(), stream);
     if ((rc = check_hip(hipGetLastError(), "extract count pass")) ||
-        (rc = check_hip(hipMemcpyAsync(totals, W.totals, 3 * 8, hipMemcpyDeviceToHost, stream), "read extract totals")) ||
-        (rc = check_hip(hipMemcpyAsync(&fault, W.fault, 4, hipMemcpyDeviceToHost, stream), "read extract fault")) ||
+        (rc = check_hip(hipMemcpyAsync(totals, W.totals.get(), 3 * 8, hipMemcpyDeviceToHost, stream), "read extract totals")) ||
+        (rc = check_hip(hipMemcpyAsync(&fault, W.fault.get(), 4, hipMemcpyDeviceToHost, stream), "read extract fault")) ||
         (rc = check_hip(hipStreamSynchronize(stream), "extract count pass")))
         return rc;
     if (fault) return set_error(MNV_E_INVALID, "mnv_extract_surface: a child link leaves the tree (not a valid N3Tree)");
@@ -561,21 +554,17 @@ int extract(const mnv_accel *accel, const mnv_extract_params *prm, hipStream_t s
     if (n_verts > (unsigned long long)INT32_MAX || n_quads * 6ull > (unsigned long long)INT32_MAX)
         return set_error(MNV_E_UNSUPPORTED, "mnv_extract_surface: more than 2^31 - 1 vertices or indices (lower the level)");
     // (d) emit, (e) colour
-    float *vert = nullptr;
-    uint32_t *faces = nullptr;
-    if (n_verts > 0 && (rc = check_hip(hipMalloc((void **)&vert, (size_t)n_verts * 9 * sizeof(float)), "hipMalloc(surface vertices)"))) return rc;
-    if (n_quads > 0 && (rc = check_hip(hipMalloc((void **)&faces, (size_t)n_quads * 6 * sizeof(uint32_t)), "hipMalloc(surface indices)"))) {
-        if (vert) (void)hipFree(vert);
-        return rc;
-    }
-    out->vert = vert, out->faces = faces;  // (the surface frees them from here on)
+    if (n_verts > 0 && (rc = check_hip(out->vert.alloc((size_t)n_verts * 9), "hipMalloc(surface vertices)"))) return rc;
+    if (n_quads > 0 && (rc = check_hip(out->faces.alloc((size_t)n_quads * 6), "hipMalloc(surface indices)"))) return rc;
+    float *vert = out->vert.get();
+    uint32_t *faces = out->faces.get();
     out->n_verts = (int64_t)n_verts, out->n_indices = (int64_t)n_quads * 6;
     if (n_verts > 0) {
         const EmitParams P = {level, prm->iso, std::ldexp(1.f, -level), colour ? 1 : 0};
-        hipLaunchKernelGGL(emit_kernel, dim3((unsigned)n_cand), dim3(256), 0, stream, T, P, W.list, W.mask, W.voff, W.qoff, vert, (int64_t)n_verts, faces,
-                           (int64_t)n_quads, W.fault);
+        hipLaunchKernelGGL(emit_kernel, dim3((unsigned)n_cand), dim3(256), 0, stream, T, P, W.list.get(), W.mask.get(), W.voff.get(), W.qoff.get(), vert, (int64_t)n_verts, faces,
+                           (int64_t)n_quads, W.fault.get());
     }
-    (void)hipEventRecord(W.ev[4], stream);
+    (void)hipEventRecord(W.ev[4].get(), stream);
     if (n_verts > 0 && colour) {
         const dim3 grid(blocks_for((int64_t)n_verts)), block(256);
         switch (basis) {
@@ -587,20 +576,20 @@ int extract(const mnv_accel *accel, const mnv_extract_params *prm, hipStream_t s
             default: hipLaunchKernelGGL(colour_kernel<25>, grid, block, 0, stream, T, vert, (int64_t)n_verts); break;
         }
     }
-    (void)hipEventRecord(W.ev[5], stream);
+    (void)hipEventRecord(W.ev[5].get(), stream);
     if ((rc = check_hip(hipGetLastError(), "extract emit pass")) ||
-        (rc = check_hip(hipMemcpyAsync(&fault, W.fault, 4, hipMemcpyDeviceToHost, stream), "read extract fault")) ||
+        (rc = check_hip(hipMemcpyAsync(&fault, W.fault.get(), 4, hipMemcpyDeviceToHost, stream), "read extract fault")) ||
         (rc = check_hip(hipStreamSynchronize(stream), "extract emit pass")))
         return rc;
     if (fault) return set_error(MNV_E_INVALID, "mnv_extract_surface: the tree changed during the call (the passes disagree)");
     mnv_surface_stats &st = out->stats;
     st.bricks = n_bricks, st.candidate_bricks = n_cand;
-    (void)hipEventElapsedTime(&st.ms_candidates, W.ev[0], W.ev[1]);
-    (void)hipEventElapsedTime(&st.ms_count, W.ev[1], W.ev[2]);
-    (void)hipEventElapsedTime(&st.ms_scan, W.ev[2], W.ev[3]);
-    (void)hipEventElapsedTime(&st.ms_emit, W.ev[3], W.ev[4]);
-    (void)hipEventElapsedTime(&st.ms_colour, W.ev[4], W.ev[5]);
-    (void)hipEventElapsedTime(&st.ms_total, W.ev[0], W.ev[5]);
+    (void)hipEventElapsedTime(&st.ms_candidates, W.ev[0].get(), W.ev[1].get());
+    (void)hipEventElapsedTime(&st.ms_count, W.ev[1].get(), W.ev[2].get());
+    (void)hipEventElapsedTime(&st.ms_scan, W.ev[2].get(), W.ev[3].get());
+    (void)hipEventElapsedTime(&st.ms_emit, W.ev[3].get(), W.ev[4].get());
+    (void)hipEventElapsedTime(&st.ms_colour, W.ev[4].get(), W.ev[5].get());
+    (void)hipEventElapsedTime(&st.ms_total, W.ev[0].get(), W.ev[5].get());
     return MNV_OK;
 }
 
@@ -663,17 +652,17 @@ int mnv_surface_download(const mnv_surface *s, float *vert, int64_t cap_floats, 
     if ((vert && cap_floats < s->n_verts * 9) || (faces && cap_indices < s->n_indices))
         return set_error(MNV_E_INVALID, "mnv_surface_download: buffer too small (mnv_surface_counts holds the sizes)");
     int rc;
-    if (vert && s->n_verts > 0 && (rc = check_hip(hipMemcpy(vert, s->vert, (size_t)s->n_verts * 9 * sizeof(float), hipMemcpyDeviceToHost), "download vertices")))
+    if (vert && s->n_verts > 0 && (rc = check_hip(hipMemcpy(vert, s->vert.get(), (size_t)s->n_verts * 9 * sizeof(float), hipMemcpyDeviceToHost), "download vertices")))
         return rc;
-    if (faces && s->n_indices > 0 && (rc = check_hip(hipMemcpy(faces, s->faces, (size_t)s->n_indices * sizeof(uint32_t), hipMemcpyDeviceToHost), "download indices")))
+    if (faces && s->n_indices > 0 && (rc = check_hip(hipMemcpy(faces, s->faces.get(), (size_t)s->n_indices * sizeof(uint32_t), hipMemcpyDeviceToHost), "download indices")))
         return rc;
     return MNV_OK;
 }
 
 int mnv_surface_device(const mnv_surface *s, const float **vert, const uint32_t **faces) {
     if (!s) return set_error(MNV_E_INVALID, "null surface");
-    if (vert) *vert = s->vert;
-    if (faces) *faces = s->faces;
+    if (vert) *vert = s->vert.get();
+    if (faces) *faces = s->faces.get();
     return MNV_OK;
 }
 
@@ -682,18 +671,16 @@ int mnv_surface_to_mesh(const mnv_surface *s, int unlit, mnv_mesh **out) {
     *out = nullptr;
     if (!s) return set_error(MNV_E_INVALID, "null surface");
     if (s->n_verts == 0 || s->n_indices == 0) return set_error(MNV_E_INVALID, "mnv_surface_to_mesh: the surface is empty");
-    float *dv = nullptr;
-    uint32_t *df = nullptr;
+    Buffer<float> dv;
+    Buffer<uint32_t> df;
     int rc;
-    if ((rc = check_hip(hipMalloc((void **)&dv, (size_t)s->n_verts * 9 * sizeof(float)), "hipMalloc(mesh vertices)")) ||
-        (rc = check_hip(hipMalloc((void **)&df, (size_t)s->n_indices * sizeof(uint32_t)), "hipMalloc(mesh indices)")) ||
-        (rc = check_hip(hipMemcpy(dv, s->vert, (size_t)s->n_verts * 9 * sizeof(float), hipMemcpyDeviceToDevice), "copy mesh vertices")) ||
-        (rc = check_hip(hipMemcpy(df, s->faces, (size_t)s->n_indices * sizeof(uint32_t), hipMemcpyDeviceToDevice), "copy mesh indices")) ||
-        (rc = mnv::mesh_adopt_device(dv, s->n_verts, df, s->n_indices, 3, unlit, out))) {
-        if (dv) (void)hipFree(dv);
-        if (df) (void)hipFree(df);
+    if ((rc = check_hip(dv.alloc((size_t)s->n_verts * 9), "hipMalloc(mesh vertices)")) ||
+        (rc = check_hip(df.alloc((size_t)s->n_indices), "hipMalloc(mesh indices)")) ||
+        (rc = check_hip(hipMemcpy(dv.get(), s->vert.get(), dv.bytes(), hipMemcpyDeviceToDevice), "copy mesh vertices")) ||
+        (rc = check_hip(hipMemcpy(df.get(), s->faces.get(), df.bytes(), hipMemcpyDeviceToDevice), "copy mesh indices")) ||
+        (rc = mnv::mesh_adopt_device(dv.get(), s->n_verts, df.get(), s->n_indices, 3, unlit, out)))
         return rc;
-    }
+    (void)dv.release(), (void)df.release();  // (the mesh owns them now)
     return MNV_OK;
 }
 

@@ -8,11 +8,19 @@
 
 #include "../../include/mnv.h"
 #include "mnv_device.h"
+#include "mnv_devmem.h"
 #include "mnv_error.h"
 
 namespace mnv {
 
 int check_hip(hipError_t e, const char *what);
+// allocates a device / pinned pair; a failure carries the text of the half that failed
+template <typename T>
+int alloc_pair(Mirrored<T> &m, size_t count, const char *dev_text, const char *pinned_text) {
+    bool pinned = false;
+    const hipError_t e = m.alloc(count, &pinned);
+    return check_hip(e, pinned ? pinned_text : dev_text);
+}
 
 // Fill the camera / option / rodrigues part of the kernel argument block.
 int fill_params(FrameParams &P, const mnv_camera *cam, const mnv_render_options *opt, mnv_rect tile);
@@ -31,7 +39,7 @@ int render_accel_for_tree(const mnv_accel *accel, const mnv_tree_view *tree, con
                           const mnv_frame_inputs *inputs, float *rgba_out, uint8_t *rgba8_out, float *split_track, float *sample_track,
                           hipStream_t stream);
 
-// a mesh handle over device arrays the caller allocated (hipMalloc) and hands over (mnv_mesh.hip)
+// a mesh handle over device arrays the caller allocated (mnv::Buffer) and releases to it after MNV_OK (mnv_mesh.hip)
 int mesh_adopt_device(float *vert, int64_t n_verts, uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit, mnv_mesh **out);
 
 }  // namespace mnv

@@ -29,8 +29,8 @@ using mnv::set_error;
 using namespace mnv_raster;
 
 struct mnv_mesh {
-    float *vert = nullptr;      // device [n_verts][9]
-    uint32_t *faces = nullptr;  // device [n_prims][face_size] or null
+    mnv::Buffer<float> vert;      // device [n_verts][9]
+    mnv::Buffer<uint32_t> faces;  // device [n_prims][face_size] or empty
     int64_t n_verts = 0, n_prims = 0;
     int32_t face_size = 3;
     bool unlit = false, visible = true;
@@ -38,8 +38,6 @@ struct mnv_mesh {
 
     ~mnv_mesh() {
         if (vert || faces) (void)hipDeviceSynchronize();
-        if (vert) (void)hipFree(vert);
-        if (faces) (void)hipFree(faces);
     }
 };
 
@@ -379,34 +377,14 @@ unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 struct Scratch {
     int device = -1;
     hipStream_t stream = nullptr;
-    MeshDesc *descs = nullptr;
-    int64_t cap_descs = 0;
-    PrimRec *recs = nullptr;
-    int64_t cap_recs = 0;
-    unsigned *count = nullptr, *cursor = nullptr;
-    unsigned long long *offset = nullptr, *total = nullptr, *total_host = nullptr;
-    int64_t n_tiles = 0;
-    uint32_t *list = nullptr;
-    int64_t cap_list = 0;
+    mnv::Buffer<MeshDesc> descs;
+    mnv::Buffer<PrimRec> recs;
+    TileBins bins;
 };
 std::mutex g_mu;
-std::vector<Scratch *> g_scratch;
+std::vector<Scratch *> g_scratch;  // (heap objects that live as long as the process: never freed, so no hipFree after the runtime is gone)
 
-template <typename T>
-int regrow(T **p, int64_t *cap, int64_t need, hipStream_t stream, const char *what) {
-    if (need <= *cap) return MNV_OK;
-    int rc;
-    if (*p) {
-        if ((rc = check_hip(hipStreamSynchronize(stream), what))) return rc;  // the old array may be in use by this stream
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    const int64_t n = need + need / 4 + 64;
-    if ((rc = check_hip(hipMalloc((void **)p, (size_t)n * sizeof(T)), what))) return rc;
-    *cap = n;
-    return MNV_OK;
-}
+size_t with_slack(int64_t need) { return (size_t)(need + need / 4 + 64); }
 
 int validate_mesh_arrays(const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_faces, int32_t face_size) {
     if (face_size < 1 || face_size > 3) return set_error(MNV_E_INVALID, "mnv_mesh: face_size must be 1 (points), 2 (lines) or 3 (triangles)");
@@ -423,14 +401,15 @@ int validate_mesh_arrays(const float *vert, int64_t n_verts, const uint32_t *fac
 
 }  // namespace
 
-// A triangle / line / point mesh over device arrays the caller allocated with hipMalloc and hands over (mnv_surface_to_mesh): the handle
-// owns them from a MNV_OK on.  The indices are the producer's and are not read back for validation.
+// A triangle / line / point mesh over device arrays the caller allocated and hands over (mnv_surface_to_mesh): the handle
+// owns them from a MNV_OK on, and the caller releases its owners.  The indices are the producer's and are not read back for validation.
 int mnv::mesh_adopt_device(float *vert, int64_t n_verts, uint32_t *faces, int64_t n_indices, int32_t face_size, int unlit, mnv_mesh **out) {
     if (!out || !vert || n_verts <= 0 || face_size < 1 || face_size > 3 || (faces ? n_indices <= 0 || n_indices % face_size != 0 : n_indices != 0) ||
         n_verts > (int64_t)UINT32_MAX)
         return set_error(MNV_E_INVALID, "mnv_mesh: bad device arrays");
     mnv_mesh *m = new mnv_mesh();
-    m->vert = vert, m->faces = faces;
+    m->vert.adopt(vert, (size_t)n_verts * 9);
+    m->faces.adopt(faces, (size_t)n_indices);
     m->n_verts = n_verts;
     m->n_prims = faces ? n_indices / face_size : n_verts / face_size;
     m->face_size = face_size;
@@ -451,21 +430,17 @@ static int upload_mesh(mnv_mesh *m, const float *vert, int64_t n_verts, const ui
         (void)hipGetLastError();
         return set_error(MNV_E_NO_DEVICE, "no current HIP device");
     }
-    float *dv = nullptr;
-    uint32_t *df = nullptr;
-    if ((rc = check_hip(hipMalloc((void **)&dv, (size_t)n_verts * 9 * sizeof(float)), "hipMalloc(mesh vertices)")) ||
-        (rc = check_hip(hipMemcpy(dv, vert, (size_t)n_verts * 9 * sizeof(float), hipMemcpyHostToDevice), "upload mesh vertices")) ||
-        (faces && ((rc = check_hip(hipMalloc((void **)&df, (size_t)n_indices * sizeof(uint32_t)), "hipMalloc(mesh indices)")) ||
-                   (rc = check_hip(hipMemcpy(df, faces, (size_t)n_indices * sizeof(uint32_t), hipMemcpyHostToDevice), "upload mesh indices"))))) {
-        if (dv) (void)hipFree(dv);
-        if (df) (void)hipFree(df);
+    mnv::Buffer<float> dv;
+    mnv::Buffer<uint32_t> df;
+    if ((rc = check_hip(dv.alloc((size_t)n_verts * 9), "hipMalloc(mesh vertices)")) ||
+        (rc = check_hip(hipMemcpy(dv.get(), vert, dv.bytes(), hipMemcpyHostToDevice), "upload mesh vertices")) ||
+        (faces && ((rc = check_hip(df.alloc((size_t)n_indices), "hipMalloc(mesh indices)")) ||
+                   (rc = check_hip(hipMemcpy(df.get(), faces, df.bytes(), hipMemcpyHostToDevice), "upload mesh indices")))))
         return rc;
-    }
     std::lock_guard<std::mutex> lock(g_mu);
     if (m->vert || m->faces) (void)hipDeviceSynchronize();  // (frames that drew the old arrays)
-    if (m->vert) (void)hipFree(m->vert);
-    if (m->faces) (void)hipFree(m->faces);
-    m->vert = dv, m->faces = df;
+    m->vert = std::move(dv);
+    m->faces = std::move(df);
     m->n_verts = n_verts;
     m->n_prims = faces ? n_indices / face_size : n_verts / face_size;
     m->face_size = face_size;
@@ -549,7 +524,7 @@ int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv
         const mnv_mesh *m = meshes[i];
         if (!m->visible || m->n_prims == 0) continue;
         MeshDesc d;
-        d.vert = m->vert, d.faces = m->faces, d.first = n_prims, d.n_prims = m->n_prims;
+        d.vert = m->vert.get(), d.faces = m->faces.get(), d.first = n_prims, d.n_prims = m->n_prims;
         std::memcpy(d.M, m->M, sizeof(d.M));
         d.face_size = m->face_size, d.unlit = m->unlit ? 1 : 0;
         descs.push_back(d);
@@ -577,47 +552,31 @@ int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv
                            (uint32_t *)rgba8_out);
         return check_hip(hipGetLastError(), "mesh_tile_kernel");
     }
-    if ((rc = regrow(&S->descs, &S->cap_descs, (int64_t)descs.size(), stream, "mesh descriptors")) ||
-        (rc = regrow(&S->recs, &S->cap_recs, n_prims, stream, "primitive records")))
+    // (the stream may still use the old arrays: grow waits for it before they go)
+    if ((rc = check_hip(mnv::grow(S->descs, descs.size(), with_slack((int64_t)descs.size()), stream, true), "mesh descriptors")) ||
+        (rc = check_hip(mnv::grow(S->recs, (size_t)n_prims, with_slack(n_prims), stream, true), "primitive records")))
         return rc;
     // (`descs` outlives the copy: this call waits for the stream below, for the pair total)
-    if ((rc = check_hip(hipMemcpyAsync(S->descs, descs.data(), descs.size() * sizeof(MeshDesc), hipMemcpyHostToDevice, stream), "upload mesh descriptors")))
+    if ((rc = check_hip(hipMemcpyAsync(S->descs.get(), descs.data(), descs.size() * sizeof(MeshDesc), hipMemcpyHostToDevice, stream), "upload mesh descriptors")))
         return rc;
-    P.descs = S->descs;
-    if (S->n_tiles < n_tiles) {
-        if ((rc = check_hip(hipStreamSynchronize(stream), "mesh scratch"))) return rc;
-        for (void *p : {(void *)S->count, (void *)S->cursor, (void *)S->offset})
-            if (p) (void)hipFree(p);
-        S->count = S->cursor = nullptr;
-        S->offset = nullptr;
-        S->n_tiles = 0;
-        if ((rc = check_hip(hipMalloc((void **)&S->count, (size_t)n_tiles * 4), "hipMalloc(tile counts)")) ||
-            (rc = check_hip(hipMalloc((void **)&S->cursor, (size_t)n_tiles * 4), "hipMalloc(tile cursors)")) ||
-            (rc = check_hip(hipMalloc((void **)&S->offset, (size_t)n_tiles * 8), "hipMalloc(tile offsets)")) ||
-            (rc = check_hip(hipMemsetAsync(S->count, 0, (size_t)n_tiles * 4, stream), "clear tile counts")))
-            return rc;
-        S->n_tiles = n_tiles;
-    }
-    if (!S->total) {
-        if ((rc = check_hip(hipMalloc((void **)&S->total, 8), "hipMalloc(pair total)")) ||
-            (rc = check_hip(hipHostMalloc((void **)&S->total_host, 8, hipHostMallocDefault), "hipHostMalloc(pair total)")))
-            return rc;
-    }
-    hipLaunchKernelGGL(mesh_setup_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, P, S->recs);
-    hipLaunchKernelGGL(mesh_bin_count_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, S->recs, n_prims, P.V, G, S->count);
-    hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, S->count, (int)n_tiles, S->offset, S->cursor, S->total);
+    P.descs = S->descs.get();
+    TileBins &B = S->bins;
+    if ((rc = B.ensure(n_tiles, stream, "mesh scratch"))) return rc;
+    hipLaunchKernelGGL(mesh_setup_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, P, S->recs.get());
+    hipLaunchKernelGGL(mesh_bin_count_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, S->recs.get(), n_prims, P.V, G, B.count.get());
+    hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, B.count.get(), (int)n_tiles, B.offset.get(), B.cursor.get(), B.total.dev.get());
     if ((rc = check_hip(hipGetLastError(), "mesh setup / count / scan")) ||
-        (rc = check_hip(hipMemcpyAsync(S->total_host, S->total, 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
+        (rc = check_hip(hipMemcpyAsync(B.total.host.get(), B.total.dev.get(), 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
         (rc = check_hip(hipStreamSynchronize(stream), "mesh setup / count / scan")))
         return rc;
-    const int64_t pairs = (int64_t)*S->total_host;
-    if ((rc = regrow(&S->list, &S->cap_list, std::max<int64_t>(pairs, 1), stream, "pair list"))) return rc;
+    const int64_t pairs = (int64_t)*B.total.host.get(), list_need = std::max<int64_t>(pairs, 1);
+    if ((rc = B.grow_list(list_need, (int64_t)with_slack(list_need), "pair list"))) return rc;
     if (pairs > 0) {
-        hipLaunchKernelGGL(mesh_bin_fill_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, S->recs, n_prims, P.V, G, S->offset, S->cursor, S->list);
+        hipLaunchKernelGGL(mesh_bin_fill_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, S->recs.get(), n_prims, P.V, G, B.offset.get(), B.cursor.get(), B.list.get());
         if ((rc = check_hip(hipGetLastError(), "mesh_bin_fill_kernel"))) return rc;
     }
-    hipLaunchKernelGGL(mesh_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, (const PrimRec *)S->recs, G, S->count,
-                       (const unsigned long long *)S->offset, (const uint32_t *)S->list, bg, u_tmax, u_rgba8, under ? 1 : 0, tmax_px_out,
+    hipLaunchKernelGGL(mesh_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, (const PrimRec *)S->recs.get(), G, B.count.get(),
+                       (const unsigned long long *)B.offset.get(), (const uint32_t *)B.list.get(), bg, u_tmax, u_rgba8, under ? 1 : 0, tmax_px_out,
                        (uint32_t *)rgba8_out);
     return check_hip(hipGetLastError(), "mesh_tile_kernel");
 }

@@ -9,6 +9,7 @@
 
 #include "../../include/mnv.h"
 #include "mnv_device.h"
+#include "mnv_devmem.h"
 
 namespace mnv {
 
@@ -38,11 +39,10 @@ struct MlpShape {
 
 struct mnv_mlp {
     mnv::MlpShape shape;
-    uint16_t *frags = nullptr;      // [n_clusters][frag_halfs] binary16, fragment order
-    float *biases = nullptr;        // [n_clusters][bias_floats]
-    uint16_t *embeddings = nullptr; // [n_clusters][n_embeddings][embedding_dim] binary16
-    uint8_t *scratch = nullptr;     // grow-only: order, tiles, counters
-    size_t scratch_bytes = 0;
+    mnv::Buffer<uint16_t> frags;       // [n_clusters][frag_halfs] binary16, fragment order
+    mnv::Buffer<float> biases;         // [n_clusters][bias_floats]
+    mnv::Buffer<uint16_t> embeddings;  // [n_clusters][n_embeddings][embedding_dim] binary16
+    mnv::Buffer<uint8_t> scratch;      // grow-only: order, tiles, counters
     int num_cus = 0;
     int blocks_per_cu = 0;          // workgroups of this network's forward kernel a compute unit holds (asked once)
 };

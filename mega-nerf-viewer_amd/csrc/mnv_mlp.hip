@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -813,38 +814,27 @@ int mnv_mlp_create(const mnv_mlp_desc *desc, const uint16_t *params, size_t n_ha
         if (!emb.empty()) std::memcpy(emb.data() + (size_t)c * S.n_embeddings * S.embedding_dim, src, (size_t)S.n_embeddings * S.embedding_dim * 2);
     }
 
-    mnv_mlp *m = new mnv_mlp();
+    std::unique_ptr<mnv_mlp> m(new mnv_mlp());
     m->shape = S;
     m->num_cus = prop.multiProcessorCount;
     hipStream_t stream = (hipStream_t)hip_stream;
-    auto fail = [&](int code) {
-        mnv_mlp_destroy(m);
-        return code;
-    };
     // + 8 fragments / 64 floats of slack: the fused guided kernel fetches every layer as 8 fragments and 4 bias tiles
-    if ((rc = check_hip(hipMalloc((void **)&m->frags, frags.size() * 2 + 8 * 1024), "hipMalloc(mlp fragments)"))) return fail(rc);
-    if ((rc = check_hip(hipMalloc((void **)&m->biases, biases.size() * 4 + 256), "hipMalloc(mlp biases)"))) return fail(rc);
-    if ((rc = check_hip(hipMemsetAsync(m->frags, 0, frags.size() * 2 + 8 * 1024, stream), "clear"))) return fail(rc);
-    if ((rc = check_hip(hipMemsetAsync(m->biases, 0, biases.size() * 4 + 256, stream), "clear"))) return fail(rc);
-    if ((rc = check_hip(hipMemcpyAsync(m->frags, frags.data(), frags.size() * 2, hipMemcpyHostToDevice, stream), "upload"))) return fail(rc);
-    if ((rc = check_hip(hipMemcpyAsync(m->biases, biases.data(), biases.size() * 4, hipMemcpyHostToDevice, stream), "upload"))) return fail(rc);
+    if ((rc = check_hip(m->frags.alloc(frags.size() + 8 * 512), "hipMalloc(mlp fragments)"))) return rc;
+    if ((rc = check_hip(m->biases.alloc(biases.size() + 64), "hipMalloc(mlp biases)"))) return rc;
+    if ((rc = check_hip(hipMemsetAsync(m->frags.get(), 0, m->frags.bytes(), stream), "clear"))) return rc;
+    if ((rc = check_hip(hipMemsetAsync(m->biases.get(), 0, m->biases.bytes(), stream), "clear"))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(m->frags.get(), frags.data(), frags.size() * 2, hipMemcpyHostToDevice, stream), "upload"))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(m->biases.get(), biases.data(), biases.size() * 4, hipMemcpyHostToDevice, stream), "upload"))) return rc;
     if (!emb.empty()) {
-        if ((rc = check_hip(hipMalloc((void **)&m->embeddings, emb.size() * 2), "hipMalloc(mlp embeddings)"))) return fail(rc);
-        if ((rc = check_hip(hipMemcpyAsync(m->embeddings, emb.data(), emb.size() * 2, hipMemcpyHostToDevice, stream), "upload"))) return fail(rc);
+        if ((rc = check_hip(m->embeddings.alloc(emb.size()), "hipMalloc(mlp embeddings)"))) return rc;
+        if ((rc = check_hip(hipMemcpyAsync(m->embeddings.get(), emb.data(), emb.size() * 2, hipMemcpyHostToDevice, stream), "upload"))) return rc;
     }
-    if ((rc = check_hip(hipStreamSynchronize(stream), "mlp upload"))) return fail(rc);  // the staging vectors die here
-    *out = m;
+    if ((rc = check_hip(hipStreamSynchronize(stream), "mlp upload"))) return rc;  // the staging vectors die here
+    *out = m.release();
     return MNV_OK;
 }
 
-void mnv_mlp_destroy(mnv_mlp *m) {
-    if (!m) return;
-    if (m->frags) (void)hipFree(m->frags);
-    if (m->biases) (void)hipFree(m->biases);
-    if (m->embeddings) (void)hipFree(m->embeddings);
-    if (m->scratch) (void)hipFree(m->scratch);
-    delete m;
-}
+void mnv_mlp_destroy(mnv_mlp *m) { delete m; }
 
 int mnv_query_submodules(mnv_mlp *m, const int16_t *cluster_indices, const float *samples, int32_t samples_stride,
                          int64_t n, float *results, int32_t result_stride, void *hip_stream) {
@@ -863,19 +853,12 @@ int mnv_query_submodules(mnv_mlp *m, const int16_t *cluster_indices, const float
     const size_t o_counts = 0, o_start = o_counts + table, o_cursor = o_start + table, o_tiles = o_cursor + table, o_order = o_tiles + table;
     const size_t need = o_order + (size_t)n * 4;
     int rc;
-    if (m->scratch_bytes < need) {
-        if (m->scratch) {
-            if ((rc = check_hip(hipStreamSynchronize(stream), "mlp scratch"))) return rc;
-            (void)hipFree(m->scratch);
-            m->scratch = nullptr;
-            m->scratch_bytes = 0;
-        }
-        if ((rc = check_hip(hipMalloc((void **)&m->scratch, need + need / 4), "hipMalloc(mlp scratch)"))) return rc;
-        m->scratch_bytes = need + need / 4;
-    }
-    int32_t *counts = reinterpret_cast<int32_t *>(m->scratch + o_counts), *seg_start = reinterpret_cast<int32_t *>(m->scratch + o_start);
-    int32_t *cursor = reinterpret_cast<int32_t *>(m->scratch + o_cursor);
-    int32_t *tile_start = reinterpret_cast<int32_t *>(m->scratch + o_tiles), *order = reinterpret_cast<int32_t *>(m->scratch + o_order);
+    // (queries in flight on the stream read the old scratch: grow waits for them before it goes)
+    if ((rc = check_hip(mnv::grow(m->scratch, need, need + need / 4, stream, true), "hipMalloc(mlp scratch)"))) return rc;
+    uint8_t *scratch = m->scratch.get();
+    int32_t *counts = reinterpret_cast<int32_t *>(scratch + o_counts), *seg_start = reinterpret_cast<int32_t *>(scratch + o_start);
+    int32_t *cursor = reinterpret_cast<int32_t *>(scratch + o_cursor);
+    int32_t *tile_start = reinterpret_cast<int32_t *>(scratch + o_tiles), *order = reinterpret_cast<int32_t *>(scratch + o_order);
 
     if ((rc = check_hip(hipMemsetAsync(counts, 0, kMaxClusters * 4, stream), "memset"))) return rc;
     // sort blocks: as many chunks of 2048 rows each as leaves about two blocks per compute unit (at most 16 chunks)
@@ -888,9 +871,9 @@ int mnv_query_submodules(mnv_mlp *m, const int16_t *cluster_indices, const float
 
     MlpLaunch L;
     L.S = S;
-    L.frags = m->frags;
-    L.biases = m->biases;
-    L.embeddings = m->embeddings;
+    L.frags = m->frags.get();
+    L.biases = m->biases.get();
+    L.embeddings = m->embeddings.get();
     L.samples = samples;
     L.samples_stride = samples_stride;
     L.results = results;

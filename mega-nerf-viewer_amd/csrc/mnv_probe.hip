@@ -176,6 +176,11 @@ extern "C" {
 int mnv_hook_probe_frame_size(void) { return (int)sizeof(mnv::FrameParams); }
 int mnv_hook_probe_cam_size(void) { return (int)sizeof(mnv::CamBlock); }
 
+// bytes the library's owners hold right now (csrc/mnv_devmem.h): which 0 device memory, 1 pinned host memory
+int64_t mnv_hook_live_bytes(int which) {
+    return which == 1 ? mnv::live_bytes<mnv::Mem::pinned>().load(std::memory_order_relaxed) : mnv::live_bytes<mnv::Mem::device>().load(std::memory_order_relaxed);
+}
+
 int mnv_hook_probe_expf(const float *x, int64_t n, int which, float *out, void *hip_stream) {
     if (n < 0 || (n > 0 && (!x || !out)) || which < 0 || which > 1) return set_error(MNV_E_INVALID, "mnv_hook_probe_expf: bad arguments");
     if (n == 0) return MNV_OK;

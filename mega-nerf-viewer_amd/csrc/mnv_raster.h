@@ -1,6 +1,6 @@
 // mnv_raster.h -- device code shared by the two rasterisers that write the frame's inputs (mnv_wireframe.hip: the octree grid;
 // mnv_mesh.hip: triangle / line / point meshes): steps 1-5 of the raster contract of include/mnv.h (mnv_render_wireframe) for one segment,
-// the 32 x 32 screen tiles and the scan of the per-tile pair counts.  Every float operation is float32 in the order the contract
+// the 32 x 32 screen tiles and the scan of the per-tile pair counts -- and, host side, the tile-bin scratch that both passes keep per stream.  Every float operation is float32 in the order the contract
 // states, under the Makefile's -ffp-contract=off.  Included by .hip units only; everything has internal linkage.
 #pragma once
 
@@ -8,6 +8,8 @@
 
 #include <cmath>
 #include <cstdint>
+
+#include "mnv_internal.h"
 
 namespace mnv_raster {
 
@@ -176,5 +178,34 @@ __host__ __device__ __forceinline__ uint32_t pack_unit(float c) {
     const float k = fminf(fmaxf(c, 0.f), 1.f);
     return (uint32_t)floorf(k * 255.f + 0.5f);
 }
+
+// Host side: the scratch of a binned pass.  Each pass keeps one per stream under its own lock, and every call leaves the counts zero.
+struct TileBins {
+    mnv::Buffer<unsigned> count, cursor;      // [tiles] each
+    mnv::Buffer<unsigned long long> offset;   // [tiles]
+    mnv::Mirrored<unsigned long long> total;  // [1] pairs of the call, read back through the pinned word
+    mnv::Buffer<uint32_t> list;               // the pair list (grow-only)
+
+    // room for n_tiles tiles (a new set waits for the stream, which may use the old one, and starts with cleared counts) and the pair total
+    int ensure(int64_t n_tiles, hipStream_t stream, const char *what) {
+        int rc;
+        if ((int64_t)count.count() < n_tiles) {
+            if ((rc = mnv::check_hip(hipStreamSynchronize(stream), what))) return rc;
+            cursor.reset();
+            offset.reset();
+            if ((rc = mnv::check_hip(count.alloc((size_t)n_tiles), "hipMalloc(tile counts)")) ||
+                (rc = mnv::check_hip(cursor.alloc((size_t)n_tiles), "hipMalloc(tile cursors)")) ||
+                (rc = mnv::check_hip(offset.alloc((size_t)n_tiles), "hipMalloc(tile offsets)")) ||
+                (rc = mnv::check_hip(hipMemsetAsync(count.get(), 0, count.bytes(), stream), "clear tile counts"))) {
+                count.reset();  // (the next call starts over)
+                return rc;
+            }
+        }
+        if (!total && (rc = mnv::alloc_pair(total, 1, "hipMalloc(pair total)", "hipHostMalloc(pair total)"))) return rc;
+        return MNV_OK;
+    }
+    // room for `need` pairs.  The caller has just waited for the stream to read the pair total, so nothing uses the old list.
+    int grow_list(int64_t need, int64_t slack, const char *what) { return mnv::check_hip(mnv::grow(list, (size_t)need, (size_t)slack, nullptr, false), what); }
+};
 
 }  // namespace mnv_raster

@@ -30,28 +30,17 @@ namespace mnv {
 
 namespace {
 
-// ---------------------------------------------------------------- grow-only device workspace, per device
-struct Workspace {
-    void *ptr = nullptr;
-    size_t cap = 0;
-};
+// ---------------------------------------------------------------- grow-only device workspace, per device: heap objects that live as long as
+// the process and are never destroyed (a hipFree after the runtime has torn down would crash at exit)
 std::mutex g_ws_mutex;
-Workspace g_ws[16];
+Buffer<uint8_t> *const g_ws = new Buffer<uint8_t>[16];
 
 int ws_reserve(size_t bytes, uint8_t **out) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    Workspace &w = g_ws[dev];
-    if (w.cap < bytes) {
-        if (w.ptr) (void)hipFree(w.ptr);
-        w.ptr = nullptr;
-        w.cap = 0;
-        const size_t want = bytes + bytes / 4;
-        int rc = check_hip(hipMalloc(&w.ptr, want), "hipMalloc(refine workspace)");
-        if (rc) return rc;
-        w.cap = want;
-    }
-    *out = static_cast<uint8_t *>(w.ptr);
+    const int rc = check_hip(grow(g_ws[dev], bytes, bytes + bytes / 4, nullptr, false), "hipMalloc(refine workspace)");
+    if (rc) return rc;
+    *out = g_ws[dev].get();
     return MNV_OK;
 }
 

@@ -266,65 +266,27 @@ unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 struct mnv_wireframe {
     int32_t max_depth = 0;
     WireTransform T{};
-    uint4 *cubes = nullptr;
-    int64_t n_cubes = 0, cap_cubes = 0;
-    int4 *front[2] = {nullptr, nullptr};
-    int64_t cap_front[2] = {0, 0};
-    unsigned long long *ctr = nullptr;       // device [3]
-    unsigned long long *ctr_host = nullptr;  // pinned [3]
+    mnv::Buffer<uint4> cubes;
+    int64_t n_cubes = 0;
+    mnv::Buffer<int4> front[2];
+    mnv::Mirrored<unsigned long long> ctr;  // [3]: device counters and their pinned mirror
     int32_t method = MNV_WIREFRAME_AUTO;
     // raster scratch, one set per HIP stream (left reset by every call: key image all ones, tile counts zero).  mnv_render_wireframe holds
     // `mu` from its first launch to its last, so calls from several host threads on one stream do not interleave their passes.
     struct Scratch {
         hipStream_t stream = nullptr;
-        unsigned long long *keys = nullptr;  // MNV_WIREFRAME_GLOBAL: [pixels]
-        int64_t key_px = 0;
-        unsigned *count = nullptr, *cursor = nullptr;  // MNV_WIREFRAME_BINNED: [tiles] each, offsets [tiles], pair list [cap_list]
-        unsigned long long *offset = nullptr, *total = nullptr, *total_host = nullptr;
-        int64_t n_tiles = 0;
-        uint32_t *list = nullptr;
-        int64_t cap_list = 0;
+        mnv::Buffer<unsigned long long> keys;  // MNV_WIREFRAME_GLOBAL: [pixels]
+        TileBins bins;                         // MNV_WIREFRAME_BINNED
     };
     mutable std::mutex mu;
     mutable std::vector<Scratch> scratch;
 
-    ~mnv_wireframe() {
-        (void)hipDeviceSynchronize();
-        if (cubes) (void)hipFree(cubes);
-        for (int i = 0; i < 2; ++i)
-            if (front[i]) (void)hipFree(front[i]);
-        if (ctr) (void)hipFree(ctr);
-        if (ctr_host) (void)hipHostFree(ctr_host);
-        for (Scratch &s : scratch) {
-            for (void *p : {(void *)s.keys, (void *)s.count, (void *)s.cursor, (void *)s.offset, (void *)s.total, (void *)s.list})
-                if (p) (void)hipFree(p);
-            if (s.total_host) (void)hipHostFree(s.total_host);
-        }
-    }
+    ~mnv_wireframe() { (void)hipDeviceSynchronize(); }
 };
 
 namespace {
 
-// grow a device array to hold `need` elements, keeping the first `keep` (stream-ordered copy, then a wait before the old one goes)
-template <typename T>
-int grow(T **p, int64_t *cap, int64_t need, int64_t keep, hipStream_t stream) {
-    if (need <= *cap) return MNV_OK;
-    const int64_t n = need + need / 4 + 64;
-    T *q = nullptr;
-    int rc = check_hip(hipMalloc((void **)&q, (size_t)n * sizeof(T)), "hipMalloc(wireframe)");
-    if (rc) return rc;
-    if (*p && keep > 0) {
-        if ((rc = check_hip(hipMemcpyAsync(q, *p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice, stream), "copy wireframe")) ||
-            (rc = check_hip(hipStreamSynchronize(stream), "copy wireframe"))) {
-            (void)hipFree(q);
-            return rc;
-        }
-    }
-    if (*p) (void)hipFree(*p);
-    *p = q;
-    *cap = n;
-    return MNV_OK;
-}
+size_t with_slack(int64_t need) { return (size_t)(need + need / 4 + 64); }
 
 int generate(mnv_wireframe *w, const mnv_tree_view *tree, int32_t max_depth, hipStream_t stream) {
     if (!tree || (tree->capacity > 0 && !tree->child)) return set_error(MNV_E_INVALID, "mnv_wireframe: null tree view / child array");
@@ -343,35 +305,35 @@ int generate(mnv_wireframe *w, const mnv_tree_view *tree, int32_t max_depth, hip
     w->n_cubes = 0;
     if (tree->capacity == 0) return MNV_OK;
     int rc;
-    if (!w->ctr) {
-        if ((rc = check_hip(hipMalloc((void **)&w->ctr, 3 * sizeof(unsigned long long)), "hipMalloc(wireframe counters)"))) return rc;
-        if ((rc = check_hip(hipHostMalloc((void **)&w->ctr_host, 3 * sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc"))) return rc;
-    }
-    if ((rc = grow(&w->front[0], &w->cap_front[0], 1, 0, stream))) return rc;
+    if (!w->ctr && (rc = mnv::alloc_pair(w->ctr, 3, "hipMalloc(wireframe counters)", "hipHostMalloc"))) return rc;
+    unsigned long long *ctr = w->ctr.dev.get(), *ctr_host = w->ctr.host.get();
+    if ((rc = check_hip(mnv::grow(w->front[0], 1, with_slack(1), stream, false), "hipMalloc(wireframe)"))) return rc;
     const int4 root = make_int4(0, 0, 0, 0);
-    if ((rc = check_hip(hipMemcpyAsync(w->front[0], &root, sizeof(root), hipMemcpyHostToDevice, stream), "wireframe root"))) return rc;
-    if ((rc = check_hip(hipMemsetAsync(w->ctr, 0, 3 * sizeof(unsigned long long), stream), "wireframe counters"))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(w->front[0].get(), &root, sizeof(root), hipMemcpyHostToDevice, stream), "wireframe root"))) return rc;
+    if ((rc = check_hip(hipMemsetAsync(ctr, 0, 3 * sizeof(unsigned long long), stream), "wireframe counters"))) return rc;
     int64_t n_front = 1;
     int cur = 0;
     for (int depth = 0; n_front > 0; ++depth) {
         if (depth > kMaxLevel) return set_error(MNV_E_UNSUPPORTED, "mnv_wireframe: tree deeper than 31 levels (or a cycle)");
         // a level emits at most 8 cubes per frontier chunk; a tree visits each chunk once, so no frontier exceeds the capacity
-        if ((rc = grow(&w->cubes, &w->cap_cubes, w->n_cubes + 8 * n_front, w->n_cubes, stream))) return rc;
+        // (the cubes found so far move to the new array; a frontier's contents are not kept)
+        const int64_t need_cubes = w->n_cubes + 8 * n_front;
+        if ((rc = check_hip(mnv::grow(w->cubes, (size_t)need_cubes, with_slack(need_cubes), stream, false, (size_t)w->n_cubes), "hipMalloc(wireframe)"))) return rc;
         const int64_t cap_next = std::min<int64_t>(8 * n_front, tree->capacity);
-        if ((rc = grow(&w->front[cur ^ 1], &w->cap_front[cur ^ 1], cap_next, 0, stream))) return rc;
-        if ((rc = check_hip(hipMemsetAsync(w->ctr, 0, sizeof(unsigned long long), stream), "wireframe counters"))) return rc;
-        hipLaunchKernelGGL(wire_level_kernel, dim3(blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, tree->capacity, w->front[cur], n_front, depth,
-                           max_depth, w->front[cur ^ 1], cap_next, w->cubes, w->cap_cubes, w->ctr);
+        if ((rc = check_hip(mnv::grow(w->front[cur ^ 1], (size_t)cap_next, with_slack(cap_next), stream, false), "hipMalloc(wireframe)"))) return rc;
+        if ((rc = check_hip(hipMemsetAsync(ctr, 0, sizeof(unsigned long long), stream), "wireframe counters"))) return rc;
+        hipLaunchKernelGGL(wire_level_kernel, dim3(blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, tree->capacity, w->front[cur].get(), n_front,
+                           depth, max_depth, w->front[cur ^ 1].get(), cap_next, w->cubes.get(), (int64_t)w->cubes.count(), ctr);
         if ((rc = check_hip(hipGetLastError(), "wire_level_kernel"))) return rc;
-        if ((rc = check_hip(hipMemcpyAsync(w->ctr_host, w->ctr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "wireframe counters")) ||
+        if ((rc = check_hip(hipMemcpyAsync(ctr_host, ctr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "wireframe counters")) ||
             (rc = check_hip(hipStreamSynchronize(stream), "wire_level_kernel")))
             return rc;
-        if (w->ctr_host[2]) {
+        if (ctr_host[2]) {
             w->n_cubes = 0;
             return set_error(MNV_E_INVALID, "mnv_wireframe: a child link leaves the tree (not a valid N3Tree)");
         }
-        n_front = (int64_t)w->ctr_host[0];
-        w->n_cubes = (int64_t)w->ctr_host[1];
+        n_front = (int64_t)ctr_host[0];
+        w->n_cubes = (int64_t)ctr_host[1];
         cur ^= 1;
     }
     return MNV_OK;
@@ -413,7 +375,7 @@ int mnv_wireframe_segments(const mnv_wireframe *w, float *segments_out, int64_t 
     if (!segments_out) return cap_segments == 0 ? MNV_OK : set_error(MNV_E_INVALID, "null segment buffer");
     if (cap_segments < n) return set_error(MNV_E_INVALID, "segment buffer too small (n_segments holds the count)");
     if (n == 0) return MNV_OK;
-    hipLaunchKernelGGL(wire_segments_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)hip_stream, w->cubes, n, w->T, segments_out);
+    hipLaunchKernelGGL(wire_segments_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)hip_stream, w->cubes.get(), n, w->T, segments_out);
     return check_hip(hipGetLastError(), "wire_segments_kernel");
 }
 
@@ -451,65 +413,40 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
     if (n_edges > (int64_t)UINT32_MAX) method = MNV_WIREFRAME_GLOBAL;  // the pair list names edges in 32 bits
     int rc;
     if (method == MNV_WIREFRAME_GLOBAL) {
-        if (S->key_px < n_px) {
+        if ((int64_t)S->keys.count() < n_px) {
             if ((rc = check_hip(hipStreamSynchronize(stream), "wireframe scratch"))) return rc;  // the old image may be in use by this stream
-            if (S->keys) (void)hipFree(S->keys);
-            S->keys = nullptr;
-            S->key_px = 0;
-            if ((rc = check_hip(hipMalloc((void **)&S->keys, (size_t)n_px * sizeof(unsigned long long)), "hipMalloc(wireframe key image)"))) return rc;
-            S->key_px = n_px;
-            if ((rc = check_hip(hipMemsetAsync(S->keys, 0xff, (size_t)n_px * sizeof(unsigned long long), stream), "clear key image"))) return rc;
+            if ((rc = check_hip(S->keys.alloc((size_t)n_px), "hipMalloc(wireframe key image)"))) return rc;
+            if ((rc = check_hip(hipMemsetAsync(S->keys.get(), 0xff, S->keys.bytes(), stream), "clear key image"))) {
+                S->keys.reset();  // (every call relies on an image it finds being all ones)
+                return rc;
+            }
         }
         if (n_edges > 0) {
-            hipLaunchKernelGGL(wire_raster_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes, n_edges, P, S->keys);
+            hipLaunchKernelGGL(wire_raster_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, S->keys.get());
             if ((rc = check_hip(hipGetLastError(), "wire_raster_kernel"))) return rc;
         }
-        hipLaunchKernelGGL(wire_resolve_kernel, dim3(blocks_for(n_px)), dim3(256), 0, stream, S->keys, n_px, bg, tmax_px_out, (uint32_t *)rgba8_out);
+        hipLaunchKernelGGL(wire_resolve_kernel, dim3(blocks_for(n_px)), dim3(256), 0, stream, S->keys.get(), n_px, bg, tmax_px_out, (uint32_t *)rgba8_out);
         return check_hip(hipGetLastError(), "wire_resolve_kernel");
     }
     const TileGrid G = {(tile.w + kTile - 1) / kTile, (tile.h + kTile - 1) / kTile};
     const int64_t n_tiles = (int64_t)G.ntx * G.nty;
-    if (S->n_tiles < n_tiles) {
-        if ((rc = check_hip(hipStreamSynchronize(stream), "wireframe scratch"))) return rc;
-        for (void *p : {(void *)S->count, (void *)S->cursor, (void *)S->offset})
-            if (p) (void)hipFree(p);
-        S->count = S->cursor = nullptr;
-        S->offset = nullptr;
-        S->n_tiles = 0;
-        if ((rc = check_hip(hipMalloc((void **)&S->count, (size_t)n_tiles * 4), "hipMalloc(tile counts)")) ||
-            (rc = check_hip(hipMalloc((void **)&S->cursor, (size_t)n_tiles * 4), "hipMalloc(tile cursors)")) ||
-            (rc = check_hip(hipMalloc((void **)&S->offset, (size_t)n_tiles * 8), "hipMalloc(tile offsets)")) ||
-            (rc = check_hip(hipMemsetAsync(S->count, 0, (size_t)n_tiles * 4, stream), "clear tile counts")))
-            return rc;
-        S->n_tiles = n_tiles;
-    }
-    if (!S->total) {
-        if ((rc = check_hip(hipMalloc((void **)&S->total, 8), "hipMalloc(pair total)")) ||
-            (rc = check_hip(hipHostMalloc((void **)&S->total_host, 8, hipHostMallocDefault), "hipHostMalloc(pair total)")))
-            return rc;
-    }
+    TileBins &B = S->bins;
+    if ((rc = B.ensure(n_tiles, stream, "wireframe scratch"))) return rc;
     if (n_edges > 0) {
-        hipLaunchKernelGGL(wire_bin_count_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes, n_edges, P, G, S->count);
-        hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, S->count, (int)n_tiles, S->offset, S->cursor, S->total);
+        hipLaunchKernelGGL(wire_bin_count_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, G, B.count.get());
+        hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, B.count.get(), (int)n_tiles, B.offset.get(), B.cursor.get(), B.total.dev.get());
         if ((rc = check_hip(hipGetLastError(), "wire_bin_count / scan")) ||
-            (rc = check_hip(hipMemcpyAsync(S->total_host, S->total, 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
+            (rc = check_hip(hipMemcpyAsync(B.total.host.get(), B.total.dev.get(), 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
             (rc = check_hip(hipStreamSynchronize(stream), "wire_bin_count / scan")))
             return rc;
-        const int64_t pairs = (int64_t)*S->total_host;
-        if (pairs > S->cap_list) {
-            if (S->list) (void)hipFree(S->list);
-            S->list = nullptr;
-            S->cap_list = 0;
-            const int64_t cap = pairs + pairs / 4 + 1024;
-            if ((rc = check_hip(hipMalloc((void **)&S->list, (size_t)cap * 4), "hipMalloc(pair list)"))) return rc;
-            S->cap_list = cap;
-        }
+        const int64_t pairs = (int64_t)*B.total.host.get();
+        if ((rc = B.grow_list(pairs, pairs + pairs / 4 + 1024, "hipMalloc(pair list)"))) return rc;
         if (pairs > 0) {
-            hipLaunchKernelGGL(wire_bin_fill_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes, n_edges, P, G, S->offset, S->cursor, S->list);
+            hipLaunchKernelGGL(wire_bin_fill_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, G, B.offset.get(), B.cursor.get(), B.list.get());
             if ((rc = check_hip(hipGetLastError(), "wire_bin_fill_kernel"))) return rc;
         }
     }
-    hipLaunchKernelGGL(wire_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, w->cubes, P, G, S->count, S->offset, S->list, bg, tmax_px_out,
+    hipLaunchKernelGGL(wire_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, w->cubes.get(), P, G, B.count.get(), B.offset.get(), B.list.get(), bg, tmax_px_out,
                        (uint32_t *)rgba8_out);
     return check_hip(hipGetLastError(), "wire_tile_kernel");
 }

@@ -462,38 +462,38 @@ int run_rank(const Args &args, int rank, int world, Rendezvous *rv) {
 
     constexpr int RING = 2;
     struct Slot {
-        uint8_t *local8 = nullptr, *gathered8 = nullptr, *frames8 = nullptr;
-        float *local = nullptr, *gathered = nullptr, *framesf = nullptr;
-        hipEvent_t rendered = nullptr, sent = nullptr, assembled = nullptr;
+        mnv::Buffer<uint8_t> local8, gathered8, frames8;
+        mnv::Buffer<float> local, gathered, framesf;
+        mnv::Event rendered, sent, assembled;
         long first = -1;
         int count = 0;
     } slots[RING];
     for (Slot &s : slots) {
-        hip_ok(hipMalloc((void **)&s.local8, local_px * 4), "hipMalloc(local tiles)");
-        if (raw) hip_ok(hipMalloc((void **)&s.local, local_px * 16), "hipMalloc(local tiles f32)");
+        hip_ok(s.local8.alloc(local_px * 4), "hipMalloc(local tiles)");
+        if (raw) hip_ok(s.local.alloc(local_px * 4), "hipMalloc(local tiles f32)");
         if (rank == 0) {
-            hip_ok(hipMalloc((void **)&s.gathered8, local_px * 4 * world), "hipMalloc(gather table)");
-            hip_ok(hipMalloc((void **)&s.frames8, frame_px * 4 * batch), "hipMalloc(frames)");
+            hip_ok(s.gathered8.alloc(local_px * 4 * world), "hipMalloc(gather table)");
+            hip_ok(s.frames8.alloc(frame_px * 4 * batch), "hipMalloc(frames)");
             if (raw) {
-                hip_ok(hipMalloc((void **)&s.gathered, local_px * 16 * world), "hipMalloc(gather table f32)");
-                hip_ok(hipMalloc((void **)&s.framesf, frame_px * 16 * batch), "hipMalloc(frames f32)");
+                hip_ok(s.gathered.alloc(local_px * 4 * world), "hipMalloc(gather table f32)");
+                hip_ok(s.framesf.alloc(frame_px * 4 * batch), "hipMalloc(frames f32)");
             }
         }
-        hip_ok(hipEventCreateWithFlags(&s.rendered, hipEventDisableTiming), "hipEventCreate");
-        hip_ok(hipEventCreateWithFlags(&s.sent, hipEventDisableTiming), "hipEventCreate");
-        hip_ok(hipEventCreateWithFlags(&s.assembled, hipEventDisableTiming), "hipEventCreate");
+        hip_ok(s.rendered.create(hipEventDisableTiming), "hipEventCreate");
+        hip_ok(s.sent.create(hipEventDisableTiming), "hipEventCreate");
+        hip_ok(s.assembled.create(hipEventDisableTiming), "hipEventCreate");
     }
     std::vector<uint8_t> host8;
     std::vector<float> hostf;
     auto flush = [&](Slot &s) {  // rank 0: wait for the slot's assembled frames and write them
         if (s.first < 0) return;
-        hip_ok(hipEventSynchronize(s.assembled), "assemble");
+        hip_ok(hipEventSynchronize(s.assembled.get()), "assemble");
         if (rank == 0 && !out.empty()) {
             host8.resize(frame_px * 4 * s.count);
-            hip_ok(hipMemcpy(host8.data(), s.frames8, host8.size(), hipMemcpyDeviceToHost), "download frames");
+            hip_ok(hipMemcpy(host8.data(), s.frames8.get(), host8.size(), hipMemcpyDeviceToHost), "download frames");
             if (raw) {
                 hostf.resize(frame_px * 4 * s.count);
-                hip_ok(hipMemcpy(hostf.data(), s.framesf, hostf.size() * 4, hipMemcpyDeviceToHost), "download frames f32");
+                hip_ok(hipMemcpy(hostf.data(), s.framesf.get(), hostf.size() * 4, hipMemcpyDeviceToHost), "download frames f32");
             }
             for (int i = 0; i < s.count; ++i)
                 write_frame(out, s.first + i, width, height, host8.data() + frame_px * 4 * i, raw ? hostf.data() + frame_px * 4 * i : nullptr);
@@ -510,29 +510,29 @@ int run_rank(const Args &args, int rank, int world, Rendezvous *rv) {
         s.first = f0;
         s.count = n;
         // one launch per rank and batch; the buffer is reused only after the gather that last read it
-        hip_ok(hipStreamWaitEvent((hipStream_t)march_stream, s.sent, 0), "wait(sent)");
+        hip_ok(hipStreamWaitEvent((hipStream_t)march_stream, s.sent.get(), 0), "wait(sent)");
         if (!guided) {
-            mnv_ok(mnv_render_voxels_accel_batch(tree.device.accel, cams.data() + f0, n, rend.options.c_abi(), full, part, s.local, s.local8, march_stream),
+            mnv_ok(mnv_render_voxels_accel_batch(tree.device.accel, cams.data() + f0, n, rend.options.c_abi(), full, part, s.local.get(), s.local8.get(), march_stream),
                    "mnv_render_voxels_accel_batch");
         } else {
             // guided sampling: one fused launch (march + networks + composite) per frame, into the frame's place in the batch buffer
             for (int i = 0; i < n; ++i)
                 mnv_ok(mnv_render_guided_fused_part(tree.device.accel, &cams[f0 + i], rend.options.c_abi(), full, part, rend.model(), &rend.cluster_grid(),
-                                                    s.local ? s.local + (size_t)i * tile_px * 4 : nullptr, s.local8 + (size_t)i * tile_px * 4, nullptr,
+                                                    s.local ? s.local.get() + (size_t)i * tile_px * 4 : nullptr, s.local8.get() + (size_t)i * tile_px * 4, nullptr,
                                                     march_stream),
                        "mnv_render_guided_fused_part");
         }
-        hip_ok(hipEventRecord(s.rendered, (hipStream_t)march_stream), "record(rendered)");
+        hip_ok(hipEventRecord(s.rendered.get(), (hipStream_t)march_stream), "record(rendered)");
         // gather + un-permute on the side stream, overlapping the next batch's march
-        hip_ok(hipStreamWaitEvent(side, s.rendered, 0), "wait(rendered)");
-        mnv_ok(mnv_gather_tiles(comm, s.local8, s.gathered8, tile_px * 4 * n, 0, side), "mnv_gather_tiles");
-        if (raw) mnv_ok(mnv_gather_tiles(comm, s.local, s.gathered, tile_px * 16 * n, 0, side), "mnv_gather_tiles(f32)");
-        hip_ok(hipEventRecord(s.sent, side), "record(sent)");
+        hip_ok(hipStreamWaitEvent(side, s.rendered.get(), 0), "wait(rendered)");
+        mnv_ok(mnv_gather_tiles(comm, s.local8.get(), s.gathered8.get(), tile_px * 4 * n, 0, side), "mnv_gather_tiles");
+        if (raw) mnv_ok(mnv_gather_tiles(comm, s.local.get(), s.gathered.get(), tile_px * 16 * n, 0, side), "mnv_gather_tiles(f32)");
+        hip_ok(hipEventRecord(s.sent.get(), side), "record(sent)");
         if (rank == 0) {
-            mnv_ok(mnv_assemble_tiles(s.gathered8, s.frames8, width, height, part, n, 4, side), "mnv_assemble_tiles");
-            if (raw) mnv_ok(mnv_assemble_tiles(s.gathered, s.framesf, width, height, part, n, 16, side), "mnv_assemble_tiles(f32)");
+            mnv_ok(mnv_assemble_tiles(s.gathered8.get(), s.frames8.get(), width, height, part, n, 4, side), "mnv_assemble_tiles");
+            if (raw) mnv_ok(mnv_assemble_tiles(s.gathered.get(), s.framesf.get(), width, height, part, n, 16, side), "mnv_assemble_tiles(f32)");
         }
-        hip_ok(hipEventRecord(s.assembled, side), "record(assembled)");
+        hip_ok(hipEventRecord(s.assembled.get(), side), "record(assembled)");
     }
     for (int k = 0; k < RING; ++k) flush(slots[(b + k) % RING]);
     hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
@@ -541,13 +541,6 @@ int run_rank(const Args &args, int rank, int world, Rendezvous *rv) {
         std::printf("%s x %d (RCCL %d): %ld frame(s) %dx%d, interleaved %dx%d macro tiles, %.3f ms/frame wall%s, %.1f Mrays/s\n", rend.get_backend(), world,
                     (int)mnv_comm_rccl_version(), frames, width, height, kMacroW, kMacroH, wall_ms / std::max<long>(frames, 1),
                     out.empty() ? "" : " incl. download + file output", wall_ms > 0 ? (double)width * height * frames / wall_ms / 1e3 : 0.0);
-    for (Slot &s : slots) {
-        for (void *p : {(void *)s.local8, (void *)s.gathered8, (void *)s.frames8, (void *)s.local, (void *)s.gathered, (void *)s.framesf})
-            if (p) (void)hipFree(p);
-        (void)hipEventDestroy(s.rendered);
-        (void)hipEventDestroy(s.sent);
-        (void)hipEventDestroy(s.assembled);
-    }
     (void)hipStreamDestroy(side);
     mnv_comm_destroy(comm);
     (void)mnv_stream_destroy(march_stream);
@@ -680,7 +673,7 @@ int main(int argc, char **argv) {
         const bool score = !target.empty(), ssim = args.has("ssim");
         const int score_flags = MNV_METRIC_QUANTISED | (target_mask.empty() ? 0 : MNV_METRIC_MASK_ALPHA) | (ssim ? MNV_METRIC_SSIM : 0);
         const size_t frame_px = (size_t)width * height;
-        std::vector<uint8_t *> target_dev(score ? (size_t)rend.frames_in_flight : 0, nullptr);
+        std::vector<mnv::Buffer<uint8_t>> target_dev(score ? (size_t)rend.frames_in_flight : 0);
         std::vector<uint8_t> target_rgb, target_alpha, target_rgba;
         auto load_target = [&](long f, int slot) {
             char name[4096];
@@ -702,9 +695,9 @@ int main(int argc, char **argv) {
                 target_rgba[p * 4 + 2] = target_rgb[p * 3 + 2];
                 target_rgba[p * 4 + 3] = target_alpha[p];
             }
-            if (!target_dev[slot]) hip_ok(hipMalloc((void **)&target_dev[slot], frame_px * 4), "hipMalloc(target image)");
-            hip_ok(hipMemcpy(target_dev[slot], target_rgba.data(), frame_px * 4, hipMemcpyHostToDevice), "upload target image");
-            rend.set_target(target_dev[slot], score_flags);
+            if (!target_dev[slot]) hip_ok(target_dev[slot].alloc(frame_px * 4), "hipMalloc(target image)");
+            hip_ok(hipMemcpy(target_dev[slot].get(), target_rgba.data(), frame_px * 4, hipMemcpyHostToDevice), "upload target image");
+            rend.set_target(target_dev[slot].get(), score_flags);
         };
         double psnr_sum = 0.0, ssim_sum = 0.0;
         long scored = 0;
@@ -748,8 +741,7 @@ int main(int argc, char **argv) {
         rend.sync_tree_streams();
         if (score) {
             rend.set_target(nullptr);
-            for (uint8_t *p : target_dev)
-                if (p) (void)hipFree(p);
+            target_dev.clear();
             if (ssim)
                 std::printf("mean over %ld frame(s): psnr %.4f ssim %.6f\n", scored, psnr_sum / std::max<long>(scored, 1), ssim_sum / std::max<long>(scored, 1));
             else

@@ -199,10 +199,6 @@ void hip_check(hipError_t e, const char *what) {
 
 void N3Tree::free_device() {
     if (device.accel) mnv_accel_destroy(device.accel);
-    if (device.data) (void)hipFree(device.data);
-    if (device.child) (void)hipFree(device.child);
-    if (device.parent) (void)hipFree(device.parent);
-    if (device.sample_counts) (void)hipFree(device.sample_counts);
     device = Device();
 }
 
@@ -212,19 +208,19 @@ void N3Tree::move_to_device(long max_capacity, bool need_parent, bool need_sampl
     free_device();
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t row = (size_t)N3_ * data_dim * sizeof(uint16_t);
-    hip_check(hipMalloc((void **)&device.data, (size_t)max_capacity * row), "hipMalloc(data)");
-    hip_check(hipMemcpyAsync(device.data, data.data(), (size_t)capacity * row, hipMemcpyHostToDevice, stream), "copy data");
-    hip_check(hipMalloc((void **)&device.child, (size_t)max_capacity * N3_ * sizeof(int32_t)), "hipMalloc(child)");
-    hip_check(hipMemcpyAsync(device.child, child.data(), (size_t)capacity * N3_ * sizeof(int32_t), hipMemcpyHostToDevice, stream), "copy child");
+    hip_check(device.data.alloc((size_t)max_capacity * N3_ * data_dim), "hipMalloc(data)");
+    hip_check(hipMemcpyAsync(device.data.get(), data.data(), (size_t)capacity * row, hipMemcpyHostToDevice, stream), "copy data");
+    hip_check(device.child.alloc((size_t)max_capacity * N3_), "hipMalloc(child)");
+    hip_check(hipMemcpyAsync(device.child.get(), child.data(), (size_t)capacity * N3_ * sizeof(int32_t), hipMemcpyHostToDevice, stream), "copy child");
     if (need_parent) {
-        hip_check(hipMalloc((void **)&device.parent, (size_t)max_capacity * sizeof(int32_t)), "hipMalloc(parent)");
-        hip_check(hipMemcpyAsync(device.parent, parent.data(), (size_t)capacity * sizeof(int32_t), hipMemcpyHostToDevice, stream), "copy parent");
+        hip_check(device.parent.alloc((size_t)max_capacity), "hipMalloc(parent)");
+        hip_check(hipMemcpyAsync(device.parent.get(), parent.data(), (size_t)capacity * sizeof(int32_t), hipMemcpyHostToDevice, stream), "copy parent");
     }
     if (need_sample_counts) {
         // The reference allocates this array without initialising it (n3tree.cpp:235-241);
         // here the host's 8s are uploaded so that the sample tracker is deterministic.
-        hip_check(hipMalloc((void **)&device.sample_counts, (size_t)max_capacity * N3_ * sizeof(int16_t)), "hipMalloc(sample_counts)");
-        hip_check(hipMemcpyAsync(device.sample_counts, sample_counts.data(), (size_t)capacity * N3_ * sizeof(int16_t), hipMemcpyHostToDevice, stream), "copy sample_counts");
+        hip_check(device.sample_counts.alloc((size_t)max_capacity * N3_), "hipMalloc(sample_counts)");
+        hip_check(hipMemcpyAsync(device.sample_counts.get(), sample_counts.data(), (size_t)capacity * N3_ * sizeof(int16_t), hipMemcpyHostToDevice, stream), "copy sample_counts");
     }
     device.max_capacity = max_capacity;
     hip_check(hipStreamSynchronize(stream), "upload");
@@ -258,15 +254,15 @@ void N3Tree::copy_from_device(void *hip_stream) {
     const size_t cap = (size_t)capacity;
     data.resize(cap * N3_ * data_dim);
     child.resize(cap * N3_);
-    hip_check(hipMemcpyAsync(data.data(), device.data, data.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, stream), "download data");
-    hip_check(hipMemcpyAsync(child.data(), device.child, child.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream), "download child");
+    hip_check(hipMemcpyAsync(data.data(), device.data.get(), data.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, stream), "download data");
+    hip_check(hipMemcpyAsync(child.data(), device.child.get(), child.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream), "download child");
     if (device.parent) {
         parent.resize(cap);
-        hip_check(hipMemcpyAsync(parent.data(), device.parent, cap * sizeof(int32_t), hipMemcpyDeviceToHost, stream), "download parent");
+        hip_check(hipMemcpyAsync(parent.data(), device.parent.get(), cap * sizeof(int32_t), hipMemcpyDeviceToHost, stream), "download parent");
     }
     if (device.sample_counts) {
         sample_counts.resize(cap * N3_);
-        hip_check(hipMemcpyAsync(sample_counts.data(), device.sample_counts, sample_counts.size() * sizeof(int16_t), hipMemcpyDeviceToHost, stream),
+        hip_check(hipMemcpyAsync(sample_counts.data(), device.sample_counts.get(), sample_counts.size() * sizeof(int16_t), hipMemcpyDeviceToHost, stream),
                   "download sample_counts");
     }
     hip_check(hipStreamSynchronize(stream), "download tree");
@@ -290,10 +286,10 @@ mnv_tree_view N3Tree::host_view() const {
 
 mnv_tree_view N3Tree::device_view() const {
     mnv_tree_view v = host_view();
-    v.data = device.data;
-    v.child = device.child;
-    v.parent = device.parent;
-    v.sample_counts = device.sample_counts;
+    v.data = device.data.get();
+    v.child = device.child.get();
+    v.parent = device.parent.get();
+    v.sample_counts = device.sample_counts.get();
     return v;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mnv.h"
+#include "../csrc/mnv_devmem.h"
 #include "data_format.hpp"
 #include "mesh.hpp"
 
@@ -75,17 +76,17 @@ struct N3Tree {
     int capacity = 0;
 
     struct Device {
-        uint16_t *data = nullptr;
-        int32_t *child = nullptr;
-        int32_t *parent = nullptr;
-        int16_t *sample_counts = nullptr;
+        mnv::Buffer<uint16_t> data;
+        mnv::Buffer<int32_t> child;
+        mnv::Buffer<int32_t> parent;          // empty unless asked for
+        mnv::Buffer<int16_t> sample_counts;   // empty unless asked for
         long max_capacity = 0;
         mnv_accel *accel = nullptr;
     } device;
 
     mnv_tree_view host_view() const;
     mnv_tree_view device_view() const;  // pointers are null before move_to_device
-    bool on_device() const { return device.data != nullptr; }
+    bool on_device() const { return (bool)device.data; }
 
     // Vertices of the grid overlay (n3tree.cpp:249-329): every voxel with child == 0 || depth >= max_depth as a cube of
     // 12 edges = 24 vertices of 9 floats (position, colour 0,0,0, normal 0,0,1), in the reference's order and float arithmetic.

@@ -58,27 +58,22 @@ void aa_weights(int filter, int n_samples, const float *offsets_xy, float *weigh
             }
 }
 
-// grow-only device buffer
-struct DeviceBuffer {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    ~DeviceBuffer() { release(); }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-    template <typename T>
-    T *get(size_t count) {
-        const size_t need = count * sizeof(T);
-        if (need > bytes) {
-            release();
-            hip_check(hipMalloc(&ptr, need + need / 8), "hipMalloc(refinement buffer)");
-            bytes = need + need / 8;
-        }
-        return static_cast<T *>(ptr);
-    }
-};
+// a grow-only refinement buffer as `count` elements of T
+using Bytes = mnv::Buffer<uint8_t>;
+template <typename T>
+T *sized(Bytes &b, size_t count) {
+    const size_t need = count * sizeof(T);
+    hip_check(mnv::grow(b, need, need + need / 8, nullptr, false), "hipMalloc(refinement buffer)");
+    return reinterpret_cast<T *>(b.get());
+}
+
+// a device / pinned pair; a failure carries the text of the half that failed
+template <typename T>
+void alloc_pair(mnv::Mirrored<T> &m, const char *dev_text, const char *pinned_text) {
+    bool pinned = false;
+    const hipError_t e = m.alloc(1, &pinned);
+    hip_check(e, pinned ? pinned_text : dev_text);
+}
 
 // What the next render() does, decided from the renderer's state and options alone (VolumeRenderer::plan()).  render() issues exactly
 // this; overlaps_next() / next_slot() report it.
@@ -121,16 +116,16 @@ struct VolumeRenderer::Impl {
     // overlaps frames k+1, k+2.  Frames that refine the tree run one at a time on slot 0 (they mutate what the next one reads).
     struct Slot {
         hipStream_t stream = nullptr;
-        float *rgba = nullptr;
-        uint8_t *rgba8 = nullptr;
-        unsigned long long *count_dev = nullptr, *count_host = nullptr;  // guided frames in flight: this slot's sample counter and its pinned copy
-        bool counted = false;                                             // ... which a frame on this slot has written (or is about to)
-        float *grid_tmax = nullptr;                                       // show_grid: this slot's depth image and image under the volume
-        uint8_t *grid_rgba8 = nullptr;
-        float *aa_sub = nullptr;  // aa_samples > 1: this slot's K float sub-frames
-        float *ray_origins = nullptr, *ray_dirs = nullptr;  // projection != pinhole: this slot's rays, [height][width][3] each
-        mnv_metric_sums *sums_dev = nullptr, *sums_host = nullptr;  // set_target: this slot's sums and their pinned copy
-        bool scored = false;                                         // ... which the last frame on this slot has written (or is about to)
+        mnv::Buffer<float> rgba;
+        mnv::Buffer<uint8_t> rgba8;
+        mnv::Mirrored<unsigned long long> count;  // guided frames in flight: this slot's sample counter and its pinned copy
+        bool counted = false;                     // ... which a frame on this slot has written (or is about to)
+        mnv::Buffer<float> grid_tmax;             // show_grid: this slot's depth image and image under the volume
+        mnv::Buffer<uint8_t> grid_rgba8;
+        mnv::Buffer<float> aa_sub;                // aa_samples > 1: this slot's K float sub-frames
+        mnv::Buffer<float> ray_origins, ray_dirs;  // projection != pinhole: this slot's rays, [height][width][3] each
+        mnv::Mirrored<mnv_metric_sums> sums;      // set_target: this slot's sums and their pinned copy
+        bool scored = false;                      // ... which the last frame on this slot has written (or is about to)
     };
     std::vector<Slot> slots;
     int cur = 0;            // slot of the most recent render()
@@ -152,14 +147,14 @@ struct VolumeRenderer::Impl {
     mnv_mlp *mlp = nullptr;
     mnv_mlp_desc mlp_desc{};
     mnv_cluster_grid grid{};
-    DeviceBuffer split_tracker, sample_tracker, visit_tracker, num_samples, cluster_indices, guided_samples;
-    DeviceBuffer offsets, z_vals, sample_rows, sample_clusters, nerf_results;
-    DeviceBuffer nodes, rand_sample, rand_clusters, results, fused_counter;
+    Bytes split_tracker, sample_tracker, visit_tracker, num_samples, cluster_indices, guided_samples;
+    Bytes offsets, z_vals, sample_rows, sample_clusters, nerf_results;
+    Bytes nodes, rand_sample, rand_clusters, results, fused_counter;
     // several ranks (set_ranks): this rank's share of the frame in compact tile-major order, the gather table on rank 0, the marks table
     mnv_comm *comm = nullptr;
     mnv_partition part = {0, 1, 0, 0, 0};
     int64_t rank_px = 0;  // pixels per rank in the compact layout: j_max macro tiles
-    DeviceBuffer local, local8, table, table8, marks_table;
+    Bytes local, local8, table, table8, marks_table;
     int64_t tracker_rows() const { return comm ? rank_px * part.world : (int64_t)width * height; }
     bool fused_inputs_ok = false;  // the model's encoded input fits the fused guided kernel (<= 64 features)
     bool prune_happened = false, can_reuse_results = false;
@@ -173,20 +168,16 @@ struct VolumeRenderer::Impl {
     uint64_t tree_version = 0, wire_version = 0;
     // anti-aliasing: what the device weight table (shared by the slots) and the slots' sub-frame buffers were made for
     int aa_k = 1, aa_filter = -1, aa_radius = 0;
-    float *aa_weights_dev = nullptr;
+    mnv::Buffer<float> aa_weights_dev;
     std::vector<float> aa_offsets;
     void free_aa() {  // (the streams are idle)
-        for (Slot &s : slots) {
-            if (s.aa_sub) (void)hipFree(s.aa_sub);
-            s.aa_sub = nullptr;
-        }
-        if (aa_weights_dev) (void)hipFree(aa_weights_dev);
-        aa_weights_dev = nullptr;
+        for (Slot &s : slots) s.aa_sub.reset();
+        aa_weights_dev.reset();
         aa_k = 1;
         aa_filter = -1;
     }
     // projection == MNV_PROJ_EQUIRECT: the device table of mnv_equirect_tables (shared by the slots) and the size it was made for
-    float *equirect_dev = nullptr;
+    mnv::Buffer<float> equirect_dev;
     int equirect_w = 0, equirect_h = 0;
     // what draws this frame's inputs (set by render()): the grid, the visible meshes of VolumeRenderer::meshes, or both
     bool pass_grid = false;
@@ -194,15 +185,15 @@ struct VolumeRenderer::Impl {
     // the grid pass and / or the mesh pass of this frame into slot S's images on `st`, returned as the frame's inputs (the edge list is
     // current); the meshes are drawn over the grid, in place
     mnv_frame_inputs grid_inputs(Slot &S, hipStream_t st, const mnv_camera &cv, const RenderOptions &o) {
-        if (!S.grid_tmax) {
-            hip_check(hipMalloc((void **)&S.grid_tmax, (size_t)width * height * sizeof(float)), "hipMalloc(grid depth image)");
-            hip_check(hipMalloc((void **)&S.grid_rgba8, (size_t)width * height * 4), "hipMalloc(grid image)");
+        if (!S.grid_tmax || !S.grid_rgba8) {
+            hip_check(S.grid_tmax.alloc((size_t)width * height), "hipMalloc(grid depth image)");
+            hip_check(S.grid_rgba8.alloc((size_t)width * height * 4), "hipMalloc(grid image)");
         }
-        const mnv_frame_inputs in = {S.grid_tmax, S.grid_rgba8};
-        if (pass_grid) mnv_check(mnv_render_wireframe(wire, &cv, o.c_abi(), {0, 0, width, height}, S.grid_tmax, S.grid_rgba8, st), "mnv_render_wireframe");
+        const mnv_frame_inputs in = {S.grid_tmax.get(), S.grid_rgba8.get()};
+        if (pass_grid) mnv_check(mnv_render_wireframe(wire, &cv, o.c_abi(), {0, 0, width, height}, S.grid_tmax.get(), S.grid_rgba8.get(), st), "mnv_render_wireframe");
         if (!pass_meshes.empty())
             mnv_check(mnv_render_meshes(pass_meshes.data(), (int32_t)pass_meshes.size(), &cv, o.c_abi(), {0, 0, width, height}, pass_grid ? &in : nullptr,
-                                        S.grid_tmax, S.grid_rgba8, st),
+                                        S.grid_tmax.get(), S.grid_rgba8.get(), st),
                       "mnv_render_meshes");
         return in;
     }
@@ -212,17 +203,17 @@ struct VolumeRenderer::Impl {
     }
     // the fused guided kernel's sample count: copied to pinned memory behind the kernel and read at the frame's LAST wait (the vote's,
     // the tree edit's) instead of at a wait of its own right behind the march -- 20-40 us of a refinement frame
-    unsigned long long *count_host = nullptr;
+    mnv::PinnedBuffer<unsigned long long> count_host;
     bool count_pending = false;
     void read_count_later(const unsigned long long *counter) {
-        if (!count_host) hip_check(hipHostMalloc((void **)&count_host, sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc(sample count)");
-        hip_check(hipMemcpyAsync(count_host, counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "read sample counter");
+        if (!count_host) hip_check(count_host.alloc(1), "hipHostMalloc(sample count)");
+        hip_check(hipMemcpyAsync(count_host.get(), counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "read sample counter");
         count_pending = true;
     }
     void finish_count(FrameStats &st) {
         if (!count_pending) return;
         hip_check(hipStreamSynchronize(stream), "guided frame");
-        st.guided_samples = (long)*count_host;
+        st.guided_samples = (long)*count_host.get();
         count_pending = false;
     }
 
@@ -232,19 +223,11 @@ struct VolumeRenderer::Impl {
         stream = slots[0].stream;
     }
     ~Impl() {
-        free_frame();
-        if (aa_weights_dev) (void)hipFree(aa_weights_dev);
-        if (equirect_dev) (void)hipFree(equirect_dev);
+        free_frame();  // (waits for every stream)
         if (wire) mnv_wireframe_destroy(wire);
-        if (count_host) (void)hipHostFree(count_host);
         if (mlp) mnv_mlp_destroy(mlp);
-        for (Slot &s : slots) {
-            if (s.count_dev) (void)hipFree(s.count_dev);
-            if (s.count_host) (void)hipHostFree(s.count_host);
-            if (s.sums_dev) (void)hipFree(s.sums_dev);
-            if (s.sums_host) (void)hipHostFree(s.sums_host);
+        for (Slot &s : slots)
             if (s.stream) (void)hipStreamDestroy(s.stream);
-        }
     }
     void sync_all() {
         for (Slot &s : slots) hip_check(hipStreamSynchronize(s.stream), "hipStreamSynchronize");
@@ -253,19 +236,13 @@ struct VolumeRenderer::Impl {
     void free_frame() {
         for (Slot &s : slots) {
             if (s.stream) (void)hipStreamSynchronize(s.stream);
-            if (s.rgba) (void)hipFree(s.rgba);
-            if (s.rgba8) (void)hipFree(s.rgba8);
-            if (s.grid_tmax) (void)hipFree(s.grid_tmax);
-            if (s.grid_rgba8) (void)hipFree(s.grid_rgba8);
-            if (s.aa_sub) (void)hipFree(s.aa_sub);
-            s.aa_sub = nullptr;
-            if (s.ray_origins) (void)hipFree(s.ray_origins);
-            if (s.ray_dirs) (void)hipFree(s.ray_dirs);
-            s.ray_origins = s.ray_dirs = nullptr;
-            s.rgba = nullptr;
-            s.rgba8 = nullptr;
-            s.grid_tmax = nullptr;
-            s.grid_rgba8 = nullptr;
+            s.rgba.reset();
+            s.rgba8.reset();
+            s.grid_tmax.reset();
+            s.grid_rgba8.reset();
+            s.aa_sub.reset();
+            s.ray_origins.reset();
+            s.ray_dirs.reset();
         }
         rgba = nullptr;
         rgba8 = nullptr;
@@ -276,20 +253,20 @@ struct VolumeRenderer::Impl {
         while ((int)slots.size() < n) {
             Slot s;
             hip_check(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "hipStreamCreate");
-            slots.push_back(s);
+            slots.push_back(std::move(s));
         }
         for (int i = 0; i < n; ++i) {
             Slot &s = slots[i];
-            if (!s.rgba && width > 0 && height > 0) {
-                hip_check(hipMalloc((void **)&s.rgba, (size_t)width * height * 4 * sizeof(float)), "hipMalloc(frame)");
-                hip_check(hipMalloc((void **)&s.rgba8, (size_t)width * height * 4), "hipMalloc(frame8)");
+            if ((!s.rgba || !s.rgba8) && width > 0 && height > 0) {
+                hip_check(s.rgba.alloc((size_t)width * height * 4), "hipMalloc(frame)");
+                hip_check(s.rgba8.alloc((size_t)width * height * 4), "hipMalloc(frame8)");
             }
         }
     }
     void use_slot(int i) {
         cur = i;
-        rgba = slots[i].rgba;
-        rgba8 = slots[i].rgba8;
+        rgba = slots[i].rgba.get();
+        rgba8 = slots[i].rgba8.get();
     }
     // The frame's slot: the next one beside the frames in flight, or slot 0 alone once they have finished.
     Slot &take_slot(const FramePlan &P, int frames_in_flight) {
@@ -321,8 +298,8 @@ struct VolumeRenderer::Impl {
     }
     mnv_tree_edit edit() const {
         mnv_tree_edit e{};
-        e.child = tree->device.child;
-        e.parent = tree->device.parent;
+        e.child = tree->device.child.get();
+        e.parent = tree->device.parent.get();
         for (int i = 0; i < 3; ++i) {
             e.offset[i] = tree->offset[i];
             e.scale[i] = tree->scale[i];
@@ -347,11 +324,11 @@ struct VolumeRenderer::Impl {
         T.track_visit = P.refines && ((camera_has_changed && tree->capacity > max_tree_capacity * 3 / 4) || prune_happened || want_marks);
         if (camera_has_changed) can_reuse_results = false;
         st.track_visit = T.track_visit;
-        T.visited = visit_tracker.get<int32_t>((size_t)std::max<long>(max_tree_capacity, 1));
+        T.visited = sized<int32_t>(visit_tracker, (size_t)std::max<long>(max_tree_capacity, 1));
         if (P.refines && o.use_splitting) {
             const int64_t rows = tracker_rows();
-            T.split = split_tracker.get<float>(rows * 3);
-            T.sample = sample_tracker.get<float>(rows * 3);
+            T.split = sized<float>(split_tracker, rows * 3);
+            T.sample = sized<float>(sample_tracker, rows * 3);
             // The fused kernel writes all three words of both rows for every pixel it renders, so a healthy fused frame does not need
             // the fill (50 us of a 3 ms configs[4] frame) -- but a wavefront that its watchdog abandoned (MNV_E_FAULT, reported by the
             // NEXT fused call) leaves its pixels' rows unwritten, and refine_after_frame edits the tree from these rows in this same
@@ -387,12 +364,12 @@ struct VolumeRenderer::Impl {
 float *VolumeRenderer::Impl::query_rows(const int16_t *d_clusters, const float *d_rand, int dim, int64_t rows, int stride) {
     const int world = comm ? part.world : 1, rank = comm ? part.rank : 0;
     if (world <= 1) {
-        float *d_results = results.get<float>((size_t)rows * stride);
+        float *d_results = sized<float>(results, (size_t)rows * stride);
         mnv_check(mnv_query_submodules(mlp, d_clusters, d_rand, dim, rows, d_results, stride, stream), "mnv_query_submodules");
         return d_results;
     }
     const int64_t per = (rows + world - 1) / world;  // equal blocks (the last one ragged): the all-gather's table is [world][per rows]
-    float *d_results = results.get<float>((size_t)per * world * stride);
+    float *d_results = sized<float>(results, (size_t)per * world * stride);
     const int64_t lo = std::min<int64_t>(rows, per * rank), hi = std::min<int64_t>(rows, per * (rank + 1));
     if (hi > lo)
         mnv_check(mnv_query_submodules(mlp, d_clusters + lo, d_rand + lo * dim, dim, hi - lo, d_results + lo * stride, stride, stream), "mnv_query_submodules");
@@ -403,8 +380,8 @@ float *VolumeRenderer::Impl::query_rows(const int16_t *d_clusters, const float *
 void VolumeRenderer::Impl::expand_voxels(RenderOptions &o, FrameStats &st, uint64_t seed) {
     const int64_t n_px = tracker_rows();
     int32_t n = 0, n_cand = 0;
-    int32_t *d_nodes = nodes.get<int32_t>((size_t)std::max(o.split_batch_size, 1) * 2);
-    mnv_check(mnv_select_split_candidates(split_tracker.get<float>(n_px * 3), n_px, o.split_batch_size, d_nodes, &n, &n_cand, stream),
+    int32_t *d_nodes = sized<int32_t>(nodes, (size_t)std::max(o.split_batch_size, 1) * 2);
+    mnv_check(mnv_select_split_candidates(sized<float>(split_tracker, n_px * 3), n_px, o.split_batch_size, d_nodes, &n, &n_cand, stream),
               "mnv_select_split_candidates");
     st.split_candidates = n_cand;
     if (n_cand == 0) {
@@ -418,15 +395,15 @@ void VolumeRenderer::Impl::expand_voxels(RenderOptions &o, FrameStats &st, uint6
     }
     const int dim = sample_cols(o), spc = o.samples_per_corner, dd = tree->data_dim;
     const int64_t children = (int64_t)n * 8, rows = children * spc;
-    float *d_rand = rand_sample.get<float>((size_t)rows * dim);
-    int16_t *d_clusters = rand_clusters.get<int16_t>((size_t)rows);
+    float *d_rand = sized<float>(rand_sample, (size_t)rows * dim);
+    int16_t *d_clusters = sized<int16_t>(rand_clusters, (size_t)rows);
     mnv_check(mnv_fill_uniform(d_rand, rows * dim, seed, stream), "mnv_fill_uniform");
     const mnv_tree_edit e = edit();
-    mnv_check(mnv_add_children_and_generate_samples(&e, o.c_abi(), d_nodes, n, d_rand, dim, d_clusters, visit_tracker.get<int32_t>(max_tree_capacity),
+    mnv_check(mnv_add_children_and_generate_samples(&e, o.c_abi(), d_nodes, n, d_rand, dim, d_clusters, sized<int32_t>(visit_tracker, max_tree_capacity),
                                                     &grid, stream),
               "mnv_add_children_and_generate_samples");
     float *d_results = query_rows(d_clusters, d_rand, dim, rows, dd + 1);
-    mnv_check(mnv_apply_split_results(tree->device.data, tree->device.sample_counts, tree->capacity, n, d_results, dd + 1, spc, dd, stream),
+    mnv_check(mnv_apply_split_results(tree->device.data.get(), tree->device.sample_counts.get(), tree->capacity, n, d_results, dd + 1, spc, dd, stream),
               "mnv_apply_split_results");
     const int old_capacity = tree->capacity;
     tree->capacity += n;
@@ -439,8 +416,8 @@ void VolumeRenderer::Impl::expand_voxels(RenderOptions &o, FrameStats &st, uint6
 void VolumeRenderer::Impl::get_more_samples(RenderOptions &o, FrameStats &st, uint64_t seed) {
     const int64_t n_px = tracker_rows();
     int32_t n = 0, n_cand = 0;
-    int32_t *d_nodes = nodes.get<int32_t>((size_t)std::max(o.split_batch_size, 1) * 2);
-    mnv_check(mnv_select_sample_candidates(sample_tracker.get<float>(n_px * 3), n_px, o.split_batch_size, d_nodes, &n, &n_cand, stream),
+    int32_t *d_nodes = sized<int32_t>(nodes, (size_t)std::max(o.split_batch_size, 1) * 2);
+    mnv_check(mnv_select_sample_candidates(sized<float>(sample_tracker, n_px * 3), n_px, o.split_batch_size, d_nodes, &n, &n_cand, stream),
               "mnv_select_sample_candidates");
     st.sample_candidates = n_cand;
     if (n == 0) return;
@@ -448,13 +425,13 @@ void VolumeRenderer::Impl::get_more_samples(RenderOptions &o, FrameStats &st, ui
     // writes the view-direction / embedding columns as well; the row is sized like expand_voxels' instead.
     const int dim = sample_cols(o), spc = o.samples_per_corner, dd = tree->data_dim;
     const int64_t rows = (int64_t)n * spc;
-    float *d_rand = rand_sample.get<float>((size_t)rows * dim);
-    int16_t *d_clusters = rand_clusters.get<int16_t>((size_t)rows);
+    float *d_rand = sized<float>(rand_sample, (size_t)rows * dim);
+    int16_t *d_clusters = sized<int16_t>(rand_clusters, (size_t)rows);
     mnv_check(mnv_fill_uniform(d_rand, rows * dim, seed ^ 0x5a5a5a5a5a5a5a5aull, stream), "mnv_fill_uniform");
     const mnv_tree_edit e = edit();
     mnv_check(mnv_generate_samples(&e, o.c_abi(), d_nodes, n, d_rand, dim, d_clusters, &grid, stream), "mnv_generate_samples");
     float *d_results = query_rows(d_clusters, d_rand, dim, rows, dd + 1);
-    mnv_check(mnv_apply_sample_results(tree->device.data, tree->device.sample_counts, d_nodes, n, d_results, dd + 1, spc, dd, stream),
+    mnv_check(mnv_apply_sample_results(tree->device.data.get(), tree->device.sample_counts.get(), d_nodes, n, d_results, dd + 1, spc, dd, stream),
               "mnv_apply_sample_results");
     st.resampled = n;
     can_reuse_results = false;
@@ -467,7 +444,7 @@ void VolumeRenderer::Impl::prune_tree(FrameStats &st) {
     // sample_counts is compacted with the other arrays; the reference forgets it (cuda_renderer.cpp:357-369)
     // A prune renumbers the chunks; the packed accel follows in place (mnv_prune_tree_accel: renumbered node words and lookup grids,
     // compacted colour rows), so that the next frame -- a visit-mark frame, cuda_renderer.cpp:101-102 -- runs on the tuned kernel as well.
-    mnv_check(mnv_prune_tree_accel(&e, tree->device.data, tree->data_dim, tree->device.sample_counts, visit_tracker.get<int32_t>(max_tree_capacity),
+    mnv_check(mnv_prune_tree_accel(&e, tree->device.data.get(), tree->data_dim, tree->device.sample_counts.get(), sized<int32_t>(visit_tracker, max_tree_capacity),
                                    (int32_t)max_tree_capacity, tree->device.accel, &new_cap, &n_del, stream),
               "mnv_prune_tree_accel");
     st.pruned = n_del > 0 ? n_del : -1;
@@ -516,7 +493,7 @@ void VolumeRenderer::set(N3Tree &tree, long max_tree_capacity) {
     impl_->max_tree_capacity = max_tree_capacity;
     ++impl_->tree_version;
     // visit_tracker = zeros, [0] = 1 (cuda_renderer.cpp:504-506)
-    int32_t *visited = impl_->visit_tracker.get<int32_t>((size_t)max_tree_capacity);
+    int32_t *visited = sized<int32_t>(impl_->visit_tracker, (size_t)max_tree_capacity);
     hip_check(hipMemsetAsync(visited, 0, (size_t)max_tree_capacity * 4, impl_->stream), "clear visit marks");
     const int32_t one = 1;
     hip_check(hipMemcpyAsync(visited, &one, 4, hipMemcpyHostToDevice, impl_->stream), "mark root");
@@ -662,7 +639,7 @@ void VolumeRenderer::slot_metrics(int slot, mnv_frame_metric_values *out) {
     if (slot < 0 || slot >= (int)I.slots.size() || !I.slots[slot].scored)
         throw StatusError(MNV_E_INVALID, "slot_metrics: the last frame of this slot was not scored (set_target)");
     hip_check(hipStreamSynchronize(I.slots[slot].stream), "slot_metrics");
-    mnv_check(mnv_metrics_finish(I.slots[slot].sums_host, out), "mnv_metrics_finish");
+    mnv_check(mnv_metrics_finish(I.slots[slot].sums.host.get(), out), "mnv_metrics_finish");
 }
 
 // the frame, then its score: on the frame's slot and stream, whatever kind of frame it was
@@ -673,13 +650,10 @@ void VolumeRenderer::render() {
     Impl::Slot &S = I.slots[I.cur];
     S.scored = false;
     if (!target) return;
-    if (!S.sums_dev) {
-        hip_check(hipMalloc((void **)&S.sums_dev, sizeof(mnv_metric_sums)), "hipMalloc(metric sums)");
-        hip_check(hipHostMalloc((void **)&S.sums_host, sizeof(mnv_metric_sums), hipHostMallocDefault), "hipHostMalloc(metric sums)");
-    }
-    const int rc = mnv_frame_metrics(S.rgba, target, I.width, I.height, I.target_flags, nullptr, S.sums_dev, nullptr, nullptr, S.stream);
+    if (!S.sums) alloc_pair(S.sums, "hipMalloc(metric sums)", "hipHostMalloc(metric sums)");
+    const int rc = mnv_frame_metrics(S.rgba.get(), target, I.width, I.height, I.target_flags, nullptr, S.sums.dev.get(), nullptr, nullptr, S.stream);
     if (rc != MNV_OK) throw StatusError(rc, std::string("mnv_frame_metrics: ") + mnv_last_error());
-    hip_check(hipMemcpyAsync(S.sums_host, S.sums_dev, sizeof(mnv_metric_sums), hipMemcpyDeviceToHost, S.stream), "read metric sums");
+    hip_check(hipMemcpyAsync(S.sums.host.get(), S.sums.dev.get(), sizeof(mnv_metric_sums), hipMemcpyDeviceToHost, S.stream), "read metric sums");
     S.scored = true;
 }
 
@@ -752,7 +726,7 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
     P.guided = guided;
     P.fused = guided && use_fused_guided && !options.render_depth && covered;
     P.packed = packed;
-    P.has_parent = tree && tree->device.parent;
+    P.has_parent = tree && tree->device.parent.get();
     return P;
 }
 
@@ -766,12 +740,11 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
     if (P.kind == FramePlan::PROJECTED) {  // (draws no inputs; anti-aliasing buffers of earlier frames stay until the next pinhole frame)
         if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
             I.sync_all();  // frames in flight read the old table
-            if (I.equirect_dev) (void)hipFree(I.equirect_dev);
-            I.equirect_dev = nullptr;
+            I.equirect_dev.reset();
             std::vector<float> table(((size_t)I.width + I.height) * 2);
             mnv_check(mnv_equirect_tables(I.width, I.height, table.data()), "mnv_equirect_tables");
-            hip_check(hipMalloc((void **)&I.equirect_dev, table.size() * sizeof(float)), "hipMalloc(equirectangular table)");
-            hip_check(hipMemcpy(I.equirect_dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice), "upload equirectangular table");
+            hip_check(I.equirect_dev.alloc(table.size()), "hipMalloc(equirectangular table)");
+            hip_check(hipMemcpy(I.equirect_dev.get(), table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice), "upload equirectangular table");
             I.equirect_w = I.width;
             I.equirect_h = I.height;
         }
@@ -801,14 +774,14 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
         I.sync_all();  // frames in flight read the old table and write the old sub-frame buffers
         if (K != I.aa_k || !I.aa_weights_dev) {
             I.free_aa();
-            hip_check(hipMalloc((void **)&I.aa_weights_dev, (size_t)K * 25 * sizeof(float)), "hipMalloc(filter weights)");
+            hip_check(I.aa_weights_dev.alloc((size_t)K * 25), "hipMalloc(filter weights)");
         }
         I.aa_offsets.resize((size_t)K * 2);
         aa_pattern(K, I.aa_offsets.data());
         I.aa_radius = aa_filter_radius(aa_filter);
         std::vector<float> w((size_t)K * (2 * I.aa_radius + 1) * (2 * I.aa_radius + 1));
         aa_weights(aa_filter, K, I.aa_offsets.data(), w.data());
-        hip_check(hipMemcpy(I.aa_weights_dev, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice), "upload filter weights");
+        hip_check(hipMemcpy(I.aa_weights_dev.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice), "upload filter weights");
         I.aa_k = K;
         I.aa_filter = aa_filter;
     }
@@ -861,15 +834,12 @@ void VolumeRenderer::issue_guided_in_flight(const FramePlan &P, const mnv_camera
     Impl &I = *impl_;
     Impl::Slot &S = I.slots[I.cur];
     const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
-    if (!S.count_dev) {
-        hip_check(hipMalloc((void **)&S.count_dev, sizeof(unsigned long long)), "hipMalloc(sample counter)");
-        hip_check(hipHostMalloc((void **)&S.count_host, sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc(sample count)");
-    }
-    hip_check(hipMemsetAsync(S.count_dev, 0, sizeof(unsigned long long), S.stream), "clear sample counter");
+    if (!S.count) alloc_pair(S.count, "hipMalloc(sample counter)", "hipHostMalloc(sample count)");
+    hip_check(hipMemsetAsync(S.count.dev.get(), 0, sizeof(unsigned long long), S.stream), "clear sample counter");
     mnv_check(mnv_render_guided_fused_track_ex(I.tree->device.accel, &cv, options.c_abi(), {0, 0, I.width, I.height}, &in, I.mlp, &I.grid, I.rgba, I.rgba8,
-                                               nullptr, nullptr, nullptr, nullptr, nullptr, S.count_dev, S.stream),
+                                               nullptr, nullptr, nullptr, nullptr, nullptr, S.count.dev.get(), S.stream),
               "mnv_render_guided_fused_track_ex");
-    hip_check(hipMemcpyAsync(S.count_host, S.count_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream), "read sample counter");
+    hip_check(hipMemcpyAsync(S.count.host.get(), S.count.dev.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream), "read sample counter");
     S.counted = true;
     stats.used_accel = true;
     stats.fused = true;
@@ -889,10 +859,10 @@ bool VolumeRenderer::issue_tree(const FramePlan &P, const mnv_camera &cv) {
         case FramePlan::FUSED_GUIDED: {
             // the guided-sampling frame as ONE kernel (march + networks + composite, no sample buffer); with refinement on as well
             // (configs[4]) the same kernel also writes the trackers and the visit marks
-            unsigned long long *counter = I.fused_counter.get<unsigned long long>(1);
+            unsigned long long *counter = sized<unsigned long long>(I.fused_counter, 1);
             hip_check(hipMemsetAsync(counter, 0, sizeof(unsigned long long), I.stream), "clear sample counter");
             mnv_check(mnv_render_guided_fused_track_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.mlp, &I.grid, I.rgba, I.rgba8, T.split, T.sample,
-                                                       T.split ? tree.device.sample_counts : nullptr, track_visit ? T.visited : nullptr, tree.device.parent,
+                                                       T.split ? tree.device.sample_counts.get() : nullptr, track_visit ? T.visited : nullptr, tree.device.parent.get(),
                                                        counter, I.stream),
                       "mnv_render_guided_fused_track_ex");
             I.read_count_later(counter);
@@ -905,17 +875,17 @@ bool VolumeRenderer::issue_tree(const FramePlan &P, const mnv_camera &cv) {
             // cuda_renderer.cpp:109-139
             const int64_t n_px = (int64_t)I.width * I.height;
             const int samples_dim = 1 + I.sample_cols(options), max_g = options.max_guided_samples, dd = tree.data_dim;
-            int64_t *offsets = I.offsets.get<int64_t>(n_px);
+            int64_t *offsets = sized<int64_t>(I.offsets, n_px);
             if (!I.can_reuse_results) {
-                int16_t *num = I.num_samples.get<int16_t>(n_px);
-                int16_t *clusters = I.cluster_indices.get<int16_t>(n_px * max_g);
-                float *guided = I.guided_samples.get<float>((size_t)n_px * max_g * samples_dim);
+                int16_t *num = sized<int16_t>(I.num_samples, n_px);
+                int16_t *clusters = sized<int16_t>(I.cluster_indices, n_px * max_g);
+                float *guided = sized<float>(I.guided_samples, (size_t)n_px * max_g * samples_dim);
                 hip_check(hipMemsetAsync(num, 0, n_px * 2, I.stream), "clear num_samples");
                 if (P.on_accel(track_visit)) {
                     // visit marks on the packed layout: the march marks leaf chunks, a closure pass adds their ancestors
                     stats.used_accel = true;
                     mnv_check(mnv_get_samples_from_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, T.split, T.sample,
-                                                                         tree.device.sample_counts, track_visit ? T.visited : nullptr, tree.device.parent, num,
+                                                                         tree.device.sample_counts.get(), track_visit ? T.visited : nullptr, tree.device.parent.get(), num,
                                                                          guided, samples_dim, clusters, &I.grid, I.stream),
                               "mnv_get_samples_from_voxels_accel_visit_ex");
                 } else {
@@ -925,27 +895,27 @@ bool VolumeRenderer::issue_tree(const FramePlan &P, const mnv_camera &cv) {
                 }
                 // one call in the steady state: the packed buffers keep the size of the previous frames and grow when a frame
                 // emits more (the call then reports the total it needs)
-                int64_t total = 0, cap_rows = (int64_t)(I.z_vals.bytes / sizeof(float));
+                int64_t total = 0, cap_rows = (int64_t)(I.z_vals.bytes() / sizeof(float));
                 float *z = nullptr, *rows = nullptr, *values = nullptr;
                 int16_t *row_clusters = nullptr;
                 for (int attempt = 0; attempt < 2; ++attempt) {
-                    z = I.z_vals.get<float>((size_t)std::max<int64_t>(cap_rows, 1));
-                    rows = I.sample_rows.get<float>((size_t)std::max<int64_t>(cap_rows, 1) * (samples_dim - 1));
-                    row_clusters = I.sample_clusters.get<int16_t>((size_t)std::max<int64_t>(cap_rows, 1));
+                    z = sized<float>(I.z_vals, (size_t)std::max<int64_t>(cap_rows, 1));
+                    rows = sized<float>(I.sample_rows, (size_t)std::max<int64_t>(cap_rows, 1) * (samples_dim - 1));
+                    row_clusters = sized<int16_t>(I.sample_clusters, (size_t)std::max<int64_t>(cap_rows, 1));
                     const int rc = mnv_compact_guided_samples(num, guided, clusters, n_px, max_g, samples_dim, offsets, z, rows, row_clusters, cap_rows,
                                                               &total, I.stream);
                     if (rc == MNV_OK) break;
                     if (total <= cap_rows || attempt == 1) mnv_check(rc, "mnv_compact_guided_samples");
                     cap_rows = total + total / 8;
                 }
-                values = I.nerf_results.get<float>((size_t)std::max<int64_t>(total, 1) * (dd + 1));
+                values = sized<float>(I.nerf_results, (size_t)std::max<int64_t>(total, 1) * (dd + 1));
                 if (total > 0)
                     mnv_check(mnv_query_submodules(I.mlp, row_clusters, rows, samples_dim - 1, total, values, dd + 1, I.stream), "mnv_query_submodules");
                 I.reuse_total = total;
                 I.can_reuse_results = true;
             }
             stats.guided_samples = I.reuse_total;
-            mnv_check(mnv_render_nerf_results(&dv, &cv, options.c_abi(), full, I.nerf_results.get<float>(1), tree.data_dim + 1, I.z_vals.get<float>(1), offsets,
+            mnv_check(mnv_render_nerf_results(&dv, &cv, options.c_abi(), full, sized<float>(I.nerf_results, 1), tree.data_dim + 1, sized<float>(I.z_vals, 1), offsets,
                                               I.rgba, I.rgba8, I.stream),
                       "mnv_render_nerf_results");
             break;
@@ -953,7 +923,7 @@ bool VolumeRenderer::issue_tree(const FramePlan &P, const mnv_camera &cv) {
         case FramePlan::TRACKED_ACCEL:
             stats.used_accel = true;
             mnv_check(mnv_render_voxels_accel_visit_ex(tree.device.accel, &cv, options.c_abi(), full, &in, I.rgba, I.rgba8, T.split, T.sample,
-                                                       tree.device.sample_counts, track_visit ? T.visited : nullptr, tree.device.parent, I.stream),
+                                                       tree.device.sample_counts.get(), track_visit ? T.visited : nullptr, tree.device.parent.get(), I.stream),
                       "mnv_render_voxels_accel_visit_ex");
             break;
         case FramePlan::REFERENCE_LAYOUT:
@@ -970,7 +940,7 @@ void VolumeRenderer::issue_aa(const FramePlan &P, const mnv_camera &cv) {
     Impl::Slot &S = I.slots[I.cur];
     const int K = aa_samples;
     const size_t frame_floats = (size_t)I.width * I.height * 4;
-    if (!S.aa_sub) hip_check(hipMalloc((void **)&S.aa_sub, (size_t)K * frame_floats * sizeof(float)), "hipMalloc(sub-frames)");
+    if (!S.aa_sub) hip_check(S.aa_sub.alloc((size_t)K * frame_floats), "hipMalloc(sub-frames)");
     const mnv_rect full = {0, 0, I.width, I.height};
     mnv_camera cams[MNV_MAX_BATCH];
     for (int k = 0; k < K; ++k) {
@@ -981,15 +951,15 @@ void VolumeRenderer::issue_aa(const FramePlan &P, const mnv_camera &cv) {
     if (P.draws_inputs) {  // the batch call has no per-pixel inputs: grid pass + march per camera, in stream order (the slot's two grid images are reused)
         for (int k = 0; k < K; ++k) {
             const mnv_frame_inputs in = I.grid_inputs(S, S.stream, cams[k], options);
-            mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub + (size_t)k * frame_floats, nullptr, S.stream),
+            mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub.get() + (size_t)k * frame_floats, nullptr, S.stream),
                       "mnv_render_voxels_accel_ex");
         }
     } else {
         const mnv_partition whole = {0, 1, 0, 0, 0};
-        mnv_check(mnv_render_voxels_accel_batch(I.tree->device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub, nullptr, S.stream),
+        mnv_check(mnv_render_voxels_accel_batch(I.tree->device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub.get(), nullptr, S.stream),
                   "mnv_render_voxels_accel_batch");
     }
-    mnv_check(mnv_resolve_samples(S.aa_sub, K, I.width, I.height, I.aa_weights_dev, I.aa_radius, I.rgba, I.rgba8, S.stream), "mnv_resolve_samples");
+    mnv_check(mnv_resolve_samples(S.aa_sub.get(), K, I.width, I.height, I.aa_weights_dev.get(), I.aa_radius, I.rgba, I.rgba8, S.stream), "mnv_resolve_samples");
     stats.used_accel = true;
 }
 
@@ -997,15 +967,15 @@ void VolumeRenderer::issue_aa(const FramePlan &P, const mnv_camera &cv) {
 void VolumeRenderer::issue_projected(const mnv_camera &cv) {
     Impl &I = *impl_;
     Impl::Slot &S = I.slots[I.cur];
-    const size_t ray_bytes = (size_t)I.width * I.height * 3 * sizeof(float);
-    if (!S.ray_origins) {
-        hip_check(hipMalloc((void **)&S.ray_origins, ray_bytes), "hipMalloc(ray origins)");
-        hip_check(hipMalloc((void **)&S.ray_dirs, ray_bytes), "hipMalloc(ray directions)");
+    const size_t ray_floats = (size_t)I.width * I.height * 3;
+    if (!S.ray_origins || !S.ray_dirs) {
+        hip_check(S.ray_origins.alloc(ray_floats), "hipMalloc(ray origins)");
+        hip_check(S.ray_dirs.alloc(ray_floats), "hipMalloc(ray directions)");
     }
-    mnv_check(mnv_generate_rays(projection, &cv, {0, 0, I.width, I.height}, projection == MNV_PROJ_EQUIRECT ? I.equirect_dev : nullptr, S.ray_origins,
-                                S.ray_dirs, S.stream),
+    mnv_check(mnv_generate_rays(projection, &cv, {0, 0, I.width, I.height}, projection == MNV_PROJ_EQUIRECT ? I.equirect_dev.get() : nullptr,
+                                S.ray_origins.get(), S.ray_dirs.get(), S.stream),
               "mnv_generate_rays");
-    mnv_check(mnv_render_rays_accel(I.tree->device.accel, S.ray_origins, S.ray_dirs, I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
+    mnv_check(mnv_render_rays_accel(I.tree->device.accel, S.ray_origins.get(), S.ray_dirs.get(), I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
               "mnv_render_rays_accel");
     stats.used_accel = true;
 }
@@ -1023,8 +993,8 @@ bool VolumeRenderer::issue_ranks(const FramePlan &P, const mnv_camera &cv) {
     }
     I.rank_px = (int64_t)j_max * I.part.tile_w * I.part.tile_h;
     const int64_t rows = I.rank_px * world;
-    float *local = I.local.get<float>((size_t)I.rank_px * 4);
-    uint8_t *local8 = I.local8.get<uint8_t>((size_t)I.rank_px * 4);
+    float *local = sized<float>(I.local, (size_t)I.rank_px * 4);
+    uint8_t *local8 = sized<uint8_t>(I.local8, (size_t)I.rank_px * 4);
     // the same decisions on every rank: they depend on the camera and on the (replicated) tree only
     const Impl::Trackers T = I.begin_refinement(P, camera, options, stats, (int64_t)rank * I.rank_px);
     const bool track_visit = T.track_visit;
@@ -1032,22 +1002,22 @@ bool VolumeRenderer::issue_ranks(const FramePlan &P, const mnv_camera &cv) {
     if (track_visit && !P.has_parent) throw std::runtime_error("several ranks: visit marks need the tree's parent array");
     stats.used_accel = true;
     if (P.guided) {
-        unsigned long long *counter = I.fused_counter.get<unsigned long long>(1);
+        unsigned long long *counter = sized<unsigned long long>(I.fused_counter, 1);
         hip_check(hipMemsetAsync(counter, 0, sizeof(unsigned long long), I.stream), "clear sample counter");
         mnv_check(mnv_render_guided_fused_track_part(tree.device.accel, &cv, options.c_abi(), full, I.part, I.mlp, &I.grid, local, local8, T.my_split,
-                                                     T.my_sample, T.split ? tree.device.sample_counts : nullptr, track_visit ? T.visited : nullptr,
-                                                     tree.device.parent, counter, I.stream),
+                                                     T.my_sample, T.split ? tree.device.sample_counts.get() : nullptr, track_visit ? T.visited : nullptr,
+                                                     tree.device.parent.get(), counter, I.stream),
                   "mnv_render_guided_fused_track_part");
         I.read_count_later(counter);  // (this rank's share)
         stats.fused = true;
     } else {
         mnv_check(mnv_render_voxels_accel_visit_part(tree.device.accel, &cv, options.c_abi(), full, I.part, local, local8, T.my_split, T.my_sample,
-                                                     tree.device.sample_counts, track_visit ? T.visited : nullptr, tree.device.parent, I.stream),
+                                                     tree.device.sample_counts.get(), track_visit ? T.visited : nullptr, tree.device.parent.get(), I.stream),
                   "mnv_render_voxels_accel_visit_part");
     }
     // the picture: tiles to rank 0, un-permuted there
-    float *table = rank == 0 ? I.table.get<float>((size_t)rows * 4) : nullptr;
-    uint8_t *table8 = rank == 0 ? I.table8.get<uint8_t>((size_t)rows * 4) : nullptr;
+    float *table = rank == 0 ? sized<float>(I.table, (size_t)rows * 4) : nullptr;
+    uint8_t *table8 = rank == 0 ? sized<uint8_t>(I.table8, (size_t)rows * 4) : nullptr;
     mnv_check(mnv_gather_tiles(I.comm, local, table, (size_t)I.rank_px * 16, 0, I.stream), "mnv_gather_tiles");
     mnv_check(mnv_gather_tiles(I.comm, local8, table8, (size_t)I.rank_px * 4, 0, I.stream), "mnv_gather_tiles");
     if (rank == 0) {
@@ -1063,7 +1033,7 @@ bool VolumeRenderer::issue_ranks(const FramePlan &P, const mnv_camera &cv) {
         // the marks of the chunks that exist: the replicas agree on tree.capacity, and a chunk beyond it cannot be marked (the table is
         // sized once for the largest tree -- reallocation would stall the frame -- but only cap words per rank travel and merge)
         const size_t cap = (size_t)tree.capacity;
-        int32_t *marks = I.marks_table.get<int32_t>((size_t)I.max_tree_capacity * world);
+        int32_t *marks = sized<int32_t>(I.marks_table, (size_t)I.max_tree_capacity * world);
         hip_check(hipMemcpyAsync(marks + cap * rank, T.visited, cap * 4, hipMemcpyDeviceToDevice, I.stream), "copy marks");
         mnv_check(mnv_allgather(I.comm, marks, cap * 4, I.stream), "mnv_allgather");
         mnv_check(mnv_merge_visit_marks(marks, world, (int32_t)cap, T.visited, I.stream), "mnv_merge_visit_marks");
@@ -1085,7 +1055,7 @@ long VolumeRenderer::slot_guided_samples(int slot) {
     Impl::Slot &S = I.slots[slot];
     if (!S.counted) return slot == I.cur ? stats.guided_samples : 0;
     hip_check(hipStreamSynchronize(S.stream), "slot_guided_samples");
-    return (long)*S.count_host;
+    return (long)*S.count.host.get();
 }
 
 void VolumeRenderer::download_slot(int slot, std::vector<float> *rgba, std::vector<uint8_t> *rgba8) {
@@ -1094,11 +1064,11 @@ void VolumeRenderer::download_slot(int slot, std::vector<float> *rgba, std::vect
     hip_check(hipStreamSynchronize(impl_->slots[slot].stream), "render");
     if (rgba) {
         rgba->resize(n);
-        hip_check(hipMemcpy(rgba->data(), impl_->slots[slot].rgba, n * sizeof(float), hipMemcpyDeviceToHost), "download rgba");
+        hip_check(hipMemcpy(rgba->data(), impl_->slots[slot].rgba.get(), n * sizeof(float), hipMemcpyDeviceToHost), "download rgba");
     }
     if (rgba8) {
         rgba8->resize(n);
-        hip_check(hipMemcpy(rgba8->data(), impl_->slots[slot].rgba8, n, hipMemcpyDeviceToHost), "download rgba8");
+        hip_check(hipMemcpy(rgba8->data(), impl_->slots[slot].rgba8.get(), n, hipMemcpyDeviceToHost), "download rgba8");
     }
 }
 
