@@ -606,6 +606,14 @@ void mnv_mlp_destroy(mnv_mlp *mlp);
  * cluster_indices: device int16 [n]; results: device float [n][result_stride], columns [0, out_dim) written.
  * Rows whose cluster id is outside [0, n_clusters) get zeros.  Asynchronous on hip_stream; the handle holds the
  * launch scratch, so one handle serves one stream at a time.
+ * Arithmetic, for every p whose octaves p 2^k are finite float32 values: encoded inputs and hidden activations are binary16
+ * values (round to nearest even, subnormals kept: the matrix instruction does not flush them); the embedding index is
+ * truncated toward zero and clamped to the table.  A
+ * coordinate or activation beyond binary16's range is an infinity, and an infinity that meets a zero weight, or one of the
+ * other sign, makes the accumulator NaN: a hidden layer's ReLU sends a NaN accumulator to +0, as it sends a negative one and -0
+ * (the matrix instruction's NaN carries the sign bit, so the kernel's clamp needs no instruction for it); the output layer has
+ * no ReLU and returns it.  On networks whose fp32 partial sums are all exact the result equals the CPU restatement in every bit
+ * (tests/test_mlp_exact_gpu.py); elsewhere it differs by the order of the fp32 sums.
  */
 int mnv_query_submodules(mnv_mlp *mlp, const int16_t *cluster_indices, const float *samples, int32_t samples_stride,
                          int64_t n, float *results, int32_t result_stride, void *hip_stream);

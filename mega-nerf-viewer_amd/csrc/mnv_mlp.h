@@ -83,7 +83,9 @@ __host__ __device__ inline float encode_feature(const MlpShape &S, int f, const 
 
 // ReLU + binary16 rounding of eight accumulators.  Rounding first and clamping the packed halves as signed 16-bit integers (a
 // half with its sign bit set -- negative or -0 -- is a negative integer) gives the bits of half(max(x, 0)) for every non-NaN x:
-// rounding is monotonic and keeps the sign.  Two instructions per pair (v_cvt_pk_f16_f32, v_pk_max_i16) instead of five
+// rounding is monotonic and keeps the sign.  NaN: one with its sign bit set becomes +0, and that is the NaN v_mfma_f32_16x16x32_f16 makes of
+// 0 * inf and inf - inf on gfx950 (measured, tests/test_mlp_exact_gpu.py) -- the definition (include/mnv.h: a NaN accumulator is a zero
+// activation) holds for every accumulator the network makes of finite encoded inputs.  Two instructions per pair (v_cvt_pk_f16_f32, v_pk_max_i16) instead of five
 // (fmaxf lowers to a canonicalising v_max plus the v_max itself, per value).
 __device__ inline half8 relu_pack(const f32x4 &lo, const f32x4 &hi) {
     typedef short short2v __attribute__((ext_vector_type(2)));

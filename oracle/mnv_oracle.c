@@ -1022,6 +1022,7 @@ int orc_mlp_forward(const orc_mlp_desc *D, const uint16_t *params, const int16_t
             for (int o = 0; o < od; ++o) {
                 float acc = orc_half_to_float(bias[o]);
                 for (int k = 0; k < cur_dim; ++k) acc += orc_half_to_float(w[(size_t)o * cur_dim + k]) * cur[k];
+                /* ReLU: negative values, -0 and a NaN accumulator (0 * inf, inf - inf: coordinates beyond binary16) become +0 (include/mnv.h) */
                 dst[o] = layer == D->hidden_layers ? acc : orc_half_to_float(orc_float_to_half(acc > 0.f ? acc : 0.f));
             }
             w = bias + od;
