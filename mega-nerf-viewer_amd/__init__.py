@@ -491,6 +491,8 @@ def hooks_lib() -> C.CDLL:
                 fn.argtypes = args
         h.mnv_hook_set_ref_table_min_rays.restype = None
         h.mnv_hook_set_ref_table_min_rays.argtypes = [C.c_longlong]
+        h.mnv_hook_last_march_variant.restype = None
+        h.mnv_hook_last_march_variant.argtypes = [C.POINTER(C.c_int32)]
         for name, (res, args) in _PROBE_SIGNATURES.items():
             fn = getattr(h, name)
             fn.restype = res
@@ -499,6 +501,14 @@ def hooks_lib() -> C.CDLL:
             raise RuntimeError("ProbeFrame / ProbeCamBlock no longer mirror csrc/mnv_device.h's FrameParams / CamBlock")
         _hooks_lib = h
     return _hooks_lib
+
+
+def last_march_variant():
+    """(BASIS, MODE, BRICK, RAYS) of the march_accel_kernel instantiation that the test-hook build launched last (csrc/mnv_knobs.cpp;
+    (-2, -1, -1, -1) before the first launch).  Says something about this process's launches only when MNV_LIB_PATH selects that build."""
+    out = (C.c_int32 * 4)()
+    hooks_lib().mnv_hook_last_march_variant(out)
+    return tuple(int(x) for x in out)
 
 
 def built_source_sha() -> str:

@@ -3,6 +3,7 @@
 
 #ifdef MNV_TEST_HOOKS
 #include <atomic>
+#include <cstdint>
 #include <cstdlib>
 #endif
 
@@ -23,15 +24,30 @@ int knob_int(Knob k, int dflt) {
 bool knob_set(Knob k) { return knob_str(k) != nullptr; }
 static std::atomic<long long> g_ref_table_min_rays{1 << 16};
 long long ref_table_min_rays() { return g_ref_table_min_rays.load(std::memory_order_relaxed); }
+// bits 0..7: BASIS + 1 (RGBA rows are BASIS -1), 8..15: MODE, 16: BRICK, 17: RAYS, 31: set once a launch was noted
+static std::atomic<uint32_t> g_last_march_variant{0};
+void note_march_variant(int basis, int mode, bool brick, bool rays) {
+    g_last_march_variant.store(0x80000000u | (uint32_t)((basis + 1) & 0xff) | (uint32_t)(mode & 0xff) << 8 | (uint32_t)brick << 16 | (uint32_t)rays << 17,
+                               std::memory_order_relaxed);
+}
 #else
 long long ref_table_min_rays() { return 1 << 16; }
 const char *knob_str(Knob) { return nullptr; }
 int knob_int(Knob, int dflt) { return dflt; }
 bool knob_set(Knob) { return false; }
+void note_march_variant(int, int, bool, bool) {}
 #endif
 
 }  // namespace mnv
 
 #ifdef MNV_TEST_HOOKS
 extern "C" void mnv_hook_set_ref_table_min_rays(long long min_rays) { mnv::g_ref_table_min_rays.store(min_rays, std::memory_order_relaxed); }
+extern "C" void mnv_hook_last_march_variant(int32_t out4[4]) {
+    const uint32_t w = mnv::g_last_march_variant.load(std::memory_order_relaxed);
+    const bool any = (w >> 31) != 0;
+    out4[0] = any ? (int32_t)(w & 0xff) - 1 : -2;
+    out4[1] = any ? (int32_t)(w >> 8 & 0xff) : -1;
+    out4[2] = any ? (int32_t)(w >> 16 & 1) : -1;
+    out4[3] = any ? (int32_t)(w >> 17 & 1) : -1;
+}
 #endif

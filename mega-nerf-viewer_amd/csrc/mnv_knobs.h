@@ -39,5 +39,9 @@ int knob_int(Knob k, int dflt);
 bool knob_set(Knob k);
 // the variable's text, or NULL
 const char *knob_str(Knob k);
+// launch_march_kernel names the march_accel_kernel<BASIS, 256, MODE, BRICK, RAYS> instantiation it is about to launch.  Empty in the shipped
+// build; the test-hook build keeps the last one in one atomic word, which mnv_hook_last_march_variant(int32_t out4[4]) reads back as
+// {basis, mode, brick, rays} ({-2, -1, -1, -1} before the first launch) -- tests/test_march_matrix_gpu.py pins the launcher's rule with it.
+void note_march_variant(int basis, int mode, bool brick, bool rays);
 
 }  // namespace mnv

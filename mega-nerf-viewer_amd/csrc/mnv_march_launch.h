@@ -3,6 +3,7 @@
 // A unit instantiates what its calls of launch_march_mode name: the BASIS values of its switch times the MODEs below.
 #pragma once
 
+#include "mnv_knobs.h"
 #include "mnv_march_accel_kernel.h"
 
 namespace mnv {
@@ -15,6 +16,7 @@ static int launch_march_kernel(const LaunchBlock<RAYS> &K, int n_blocks, size_t 
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return (int)e;
     }
+    note_march_variant(BASIS, MODE, BRICK, RAYS);  // empty in the shipped build (mnv_knobs.cpp)
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(BLOCK), lds_bytes, stream, K);
     return (int)hipGetLastError();
 }

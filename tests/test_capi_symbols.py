@@ -49,6 +49,12 @@ def test_the_drop_in_core_is_thirty_symbols_and_no_call_depends_on_process_wide_
     assert "mnv_hook_" not in out
     hooks = subprocess.run(["nm", "-D", "--defined-only", os.path.join(os.path.dirname(mnv.LIB_PATH), "testhooks", "libmnv.so")], capture_output=True, text=True).stdout
     assert "mnv_hook_set_ref_table_min_rays" in hooks or os.environ.get("MNV_LIB_PATH")
+    # the recorder of the launched march variant (csrc/mnv_knobs.cpp, tests/test_march_matrix_gpu.py) is a hook like the others: the shipped
+    # library's launcher calls an empty function and keeps no record
+    assert "mnv_hook_last_march_variant" in hooks or os.environ.get("MNV_LIB_PATH")
+    # (the dynamic table, which no strip removes: the recorder's reader is not in it, the launcher's empty call target may be)
+    dyn = subprocess.run(["nm", "-D", "-C", "--defined-only", mnv.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert "mnv_version" in dyn and "last_march_variant" not in dyn
 
 
 def test_no_torch_or_oracle_in_the_abi(mnv):
