@@ -913,6 +913,45 @@ int mnv_surface_to_mesh(const mnv_surface *s, int unlit, mnv_mesh **out);
  * cannot be written. */
 int mnv_obj_write(const char *path, const float *vert, int64_t n_verts, const uint32_t *faces, int64_t n_indices, int32_t face_size);
 
+/* ------------------------------------------------ levels of detail: mip the tree's rows, cut the tree at a depth
+ * A tree stores a row for every interior voxel, but those rows hold whatever the voxel had before it was split (zeros in a baked PlenOctree
+ * file): cutting the child links at a depth shows stale colours.  mnv_tree_mip_rows derives every interior row from the voxel's children,
+ * bottom-up; mnv_tree_truncate then cuts the tree at a depth and compacts what is left into an ordinary tree that every march renders.
+ * Depths as mnv_accel_sample_points has them: the root chunk's voxels have depth 1, chunk c + child[c][j] has depth(c) + 1.  N == 2, any
+ * data_dim from 2 to 1024, either row format (the rule never looks at the basis); `parent` is not read.
+ *
+ * mnv_tree_mip_rows.  data_out: device [capacity][8][data_dim], 16-byte aligned, must not overlap tree->data (the input tree is never
+ * modified).  chunk_depth_out: device int32 [capacity] or NULL; 0 = the chunk was not reached from the root.  chunks_at_depth: HOST int64
+ * [24], entry d = chunks of depth d (entry 0 unused, 0).  Waits for hip_stream (it hands the counts back).
+ *
+ * Contract (binary32, operations in the stated order, no contraction, correctly rounded division).  h(bits) is the binary16 value as
+ * binary32, bits that are not finite (infinities, NaNs) read as +0.  half() rounds a binary32 to binary16, to nearest even, once; subnormal
+ * binary16 results are kept, a result of 65520 or more becomes infinity.
+ *   The row of a leaf voxel (child == 0) and every row of a chunk that was not reached are copied bit for bit.
+ *   The row of an interior voxel whose child chunk is k comes from the eight (already mipped) rows r_0 .. r_7 of chunk k; sigma is column
+ *   data_dim - 1:
+ *     w_i = h(sigma_i) > 0 ? h(sigma_i) : 0;   W = ((((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5) + w_6) + w_7.
+ *     W == 0: every half of the row is 0x0000.
+ *     Otherwise sigma' = half(W * 0.125f), and for every other column c: t_i = w_i * h(r_i[c]) (all eight terms, also those with w_i == 0),
+ *     S = ((((((t_0 + t_1) + t_2) + t_3) + t_4) + t_5) + t_6) + t_7, the result is half(S / W).
+ *   No value above is a binary32 subnormal or overflows (the inputs are binary16 values): the device's binary32 denormal mode does not
+ *   enter, and no atomic operation decides an output byte.
+ * MNV_E_INVALID: a null argument, a child link outside [1, capacity), a chunk reached twice, overlapping or misaligned arrays, host arrays in
+ * the view.  MNV_E_UNSUPPORTED: N != 2, more than 23 levels, data_dim above 1024.
+ *
+ * mnv_tree_truncate.  Asynchronous on hip_stream.  tree->data holds the rows to carry (normally the mipped ones), chunk_depth is
+ * mnv_tree_mip_rows' array.  The survivors are the chunks with 1 <= chunk_depth <= max_depth, kept in ascending chunk order: a survivor's
+ * new index is its rank among the survivors.  new_capacity must be the number of survivors (the sum of chunks_at_depth[1 .. max_depth]);
+ * nothing is written at or beyond it.  Outputs (device): child_out int32 [new_capacity][8]: rank(c + child[c][j]) - rank(c) where the voxel
+ * has a child and chunk_depth[c] < max_depth, 0 otherwise; data_out [new_capacity][8][data_dim] (16-byte aligned): the survivors' rows;
+ * parent_out int32 [new_capacity] or NULL: rank(parent chunk) * 8 + j of the voxel above, -1 for the root, derived from `child` (the view's
+ * parent array is not read); sample_counts_out int16 [new_capacity][8] or NULL (skipped when the view has no counts): the survivors' counts.
+ * A max_depth at or beyond the tree's depth gives the same topology (without the chunks that were not reached).
+ * MNV_E_INVALID: a null argument, max_depth < 1, new_capacity outside [1, capacity], misaligned rows.  MNV_E_UNSUPPORTED as above. */
+int mnv_tree_mip_rows(const mnv_tree_view *device_tree, uint16_t *data_out, int32_t *chunk_depth_out, int64_t chunks_at_depth[24], void *hip_stream);
+int mnv_tree_truncate(const mnv_tree_view *device_tree, const int32_t *chunk_depth, int32_t max_depth, int32_t new_capacity, int32_t *child_out,
+                      uint16_t *data_out, int32_t *parent_out, int16_t *sample_counts_out, void *hip_stream);
+
 /* ------------------------------------------------ anti-aliased frames: jittered sub-frames in one launch, filtered resolve
  * Every march kernel sends one ray through each pixel centre.  A supersampled frame is K frames of the SAME camera whose principal point is
  * shifted by a sub-pixel offset (mnv_camera carries cx, cy per camera, and mnv_render_voxels_accel_batch marches up to MNV_MAX_BATCH cameras
@@ -1108,6 +1147,12 @@ int mnv_n3tree_save_npz(const mnv_n3tree *t, const char *npz_path); /* svox layo
  * in the reference's order and float arithmetic.  *n_floats receives the length; out NULL with cap_floats 0 asks for it alone; a buffer
  * shorter than that is MNV_E_INVALID (and *n_floats still says what it needs). */
 int mnv_n3tree_gen_wireframe(const mnv_n3tree *t, int32_t max_depth, float *out, int64_t cap_floats, int64_t *n_floats);
+/* A level of detail of a tree that is on the device (mnv_n3tree_move_to_device): mnv_tree_mip_rows, then mnv_tree_truncate at max_depth, as a
+ * NEW tree on the device -- data, child, parent, sample counts when `t` has them on the device, and the packed accel when `t` has one --
+ * with the same offset / scale / row format; its host arrays are downloaded, so mnv_n3tree_save_npz writes it.  `t` is not changed.  Free
+ * with mnv_n3tree_free.  Runs on the null stream and waits for it.  MNV_E_INVALID: max_depth < 1, a tree that is not on the device;
+ * otherwise the codes of the two calls. */
+int mnv_n3tree_make_lod(mnv_n3tree *t, int32_t max_depth, mnv_n3tree **out);
 /* DataFormat::parse / to_string (src/data_format.cpp:5-41) */
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim);
 int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size_t buflen);
@@ -1223,6 +1268,13 @@ int mnv_renderer_set_projection(mnv_renderer *r, int32_t projection);
  * target together with mnv_renderer_set_ranks, in either order. */
 int mnv_renderer_set_target(mnv_renderer *r, const uint8_t *rgba8_device, int32_t flags);
 int mnv_renderer_slot_metrics(mnv_renderer *r, int32_t slot, mnv_frame_metric_values *out);
+/* VolumeRenderer::set_lod (default 0 = off: every frame is what it is without this call, byte for byte).  max_depth >= 1: the frames march
+ * the tree of mnv_n3tree_make_lod(max_depth) instead of the tree that was set -- plain frames, frames in flight, anti-aliased and projected
+ * frames, the grid overlay (the grid of the truncated tree) and meshes.  The renderer builds that tree at the first frame that needs it,
+ * keeps one per depth and drops them all when mnv_renderer_set gets a tree (or a refinement frame edits it).  mnv_renderer_render answers
+ * MNV_E_INVALID while a level of detail meets what would edit or vote on the tree: options.use_splitting, options.use_guided_sampling,
+ * several ranks (level 0 renders again).  MNV_E_INVALID here: a negative depth. */
+int mnv_renderer_set_lod(mnv_renderer *r, int32_t max_depth);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

@@ -406,6 +406,10 @@ _SIGNATURES = {
     "mnv_surface_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mnv_surface_to_mesh": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "mnv_obj_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "mnv_tree_mip_rows": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "mnv_tree_truncate": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_n3tree_make_lod": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mnv_renderer_set_lod": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -711,6 +715,13 @@ class N3Tree:
 
     def save_npz(self, path: str) -> None:
         _check(lib().mnv_n3tree_save_npz(self._h, os.fsencode(path)))
+
+    def make_lod(self, depth: int) -> "N3Tree":
+        """N3Tree::make_lod: a new tree on the device (with its accel where this one has one) whose interior rows are mipped from their
+        children and which is cut at `depth` (the root chunk's voxels have depth 1); its host arrays are filled.  Needs move_to_device."""
+        h = C.c_void_p()
+        _check(lib().mnv_n3tree_make_lod(self._h, int(depth), C.byref(h)))
+        return N3Tree(h.value)
 
     def gen_wireframe(self, max_depth: int = 100000) -> np.ndarray:
         """N3Tree::gen_wireframe (n3tree.cpp:249-329) on the host arrays: float32 [n_vertices, 9] (position, colour, normal), 24 vertices
@@ -1272,6 +1283,12 @@ class Renderer:
         raises there, with MNV_E_INVALID."""
         _check(lib().mnv_renderer_set_projection(self._h, int(projection)))
 
+    def set_lod(self, depth: int) -> None:
+        """VolumeRenderer::set_lod: depth >= 1 has every frame march N3Tree.make_lod(depth) of the tree that was set (built at the first
+        frame that needs it, one kept per depth); 0 (the default) is the full tree, unchanged.  What render() refuses with a level of
+        detail (use_splitting, use_guided_sampling, ranks) raises there, with MNV_E_INVALID."""
+        _check(lib().mnv_renderer_set_lod(self._h, int(depth)))
+
     def set_target(self, target=None, flags: int = 0) -> None:
         """VolumeRenderer::set_target: score every frame against `target`, a contiguous uint8 device tensor [height, width, 4], on the
         device (METRIC_QUANTISED / METRIC_MASK_ALPHA / METRIC_SSIM); metrics(slot) collects a frame's score.  The tensor may change per
@@ -1595,6 +1612,25 @@ def extract_surface(accel: int, level: int, iso: float, colour: bool = True, all
     h = C.c_void_p()
     _check(lib().mnv_extract_surface(C.c_void_p(accel), C.byref(p), C.c_void_p(stream), C.byref(h)))
     return Surface(h.value)
+
+
+def tree_mip_rows(tree_view: TreeView, data_out, chunk_depth_out=None, stream: int = 0) -> np.ndarray:
+    """mnv_tree_mip_rows: the rows of a device tree view with every interior row derived from the voxel's children, into data_out (int16 /
+    uint16 / float16 device tensor [capacity, 8, data_dim]; never the tree's own array); chunk_depth_out: int32 device tensor [capacity]
+    or None.  Returns chunks_at_depth, int64 [24] (entry d: chunks of depth d).  Waits for `stream`."""
+    counts = np.zeros(24, np.int64)
+    _check(lib().mnv_tree_mip_rows(C.byref(tree_view), _ptr(data_out), _ptr(chunk_depth_out), counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                   C.c_void_p(stream)))
+    return counts
+
+
+def tree_truncate(tree_view: TreeView, chunk_depth, max_depth: int, new_capacity: int, child_out, data_out, parent_out=None,
+                  sample_counts_out=None, stream: int = 0) -> None:
+    """mnv_tree_truncate (asynchronous on `stream`): the chunks of depth 1 .. max_depth of a device tree view, compacted in order, into
+    device tensors of new_capacity chunks (child int32 [n, 8], data 16-bit [n, 8, data_dim], parent int32 [n] or None, sample counts int16
+    [n, 8] or None); tree_view.data holds the rows to carry, chunk_depth is tree_mip_rows' array."""
+    _check(lib().mnv_tree_truncate(C.byref(tree_view), _ptr(chunk_depth), int(max_depth), int(new_capacity), _ptr(child_out), _ptr(data_out),
+                                   _ptr(parent_out), _ptr(sample_counts_out), C.c_void_p(stream)))
 
 
 MAX_BATCH = 64

@@ -177,6 +177,22 @@ int mnv_n3tree_gen_wireframe(const mnv_n3tree *t, int32_t max_depth, float *out,
     });
 }
 
+int mnv_n3tree_make_lod(mnv_n3tree *t, int32_t max_depth, mnv_n3tree **out) {
+    if (!t || !out) return mnv::set_error(MNV_E_INVALID, "null argument");
+    *out = nullptr;
+    return guarded([&] {
+        auto *h = new mnv_n3tree();
+        try {
+            t->tree.make_lod_into(h->tree, max_depth);
+        } catch (...) {
+            delete h;
+            throw;
+        }
+        *out = h;
+        return MNV_OK;
+    });
+}
+
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim) {
     viewer::DataFormat f;
     f.parse(str ? str : "");
@@ -466,6 +482,14 @@ int mnv_renderer_set_target(mnv_renderer *r, const uint8_t *rgba8_device, int32_
     if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
     return guarded([&] {
         r->rend.set_target(rgba8_device, flags);
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_set_lod(mnv_renderer *r, int32_t max_depth) {
+    if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
+    return guarded([&] {
+        r->rend.set_lod(max_depth);
         return MNV_OK;
     });
 }

@@ -46,6 +46,9 @@
 //                    --extract_iso S, default 10, the density the surface follows).  Frames rendered by the same run draw the mesh under
 //                    the volume like --mesh (--extract_unlit: with its vertex colours alone); --frames 0 writes the file only.  Refused
 //                    with --gpus and a projection other than pinhole, as --mesh is.
+//   --lod D          the frames march the tree truncated at depth D (the root chunk's voxels have depth 1), every interior row mipped
+//                    from its children first (VolumeRenderer::set_lod, N3Tree::make_lod: mnv_tree_mip_rows + mnv_tree_truncate).
+//                    --save_lod OUT.npz writes that tree.  Refused with --gpus, --use_splitting and --use_guided_sampling.
 //   --target PREFIX  score frame f against PREFIX_%04d.ppm (the P6 files --out writes) on the device (VolumeRenderer::set_target,
 //                    mnv_frame_metrics with MNV_METRIC_QUANTISED: the file --out would write against the file that was read) and print
 //                    "frame F: psnr ..." when the frame is collected, then the means over the frames.  --ssim adds SSIM (11 x 11 Gaussian
@@ -140,6 +143,7 @@ void usage() {
               "                  [--in_flight K] [--guided_in_flight] [--aa K [--aa_filter box|tent]] [--projection pinhole|ortho|equirect] [--gpus N [--reserve_cus R] [--root_period M]]\n"
               "                  [--mesh FILE.obj[,unlit] [--mesh_color r,g,b] [--mesh_translate x,y,z] [--mesh_rotate x,y,z] [--mesh_scale s]]...\n"
               "                  [--extract_mesh OUT.obj [--extract_level L] [--extract_iso S] [--extract_unlit]]   the density's iso-surface as a mesh\n"
+              "                  [--lod D [--save_lod OUT.npz]]   march (and write) the tree truncated at depth D, interior rows mipped from their children\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
               "                   0 = excluded): PSNR and, with --ssim, SSIM per frame and their means; not with --gpus.  Out of scope: pose\n"
               "                   lists (poses stay --orbit or the API) and LPIPS (it needs a network this repository does not have)\n"
@@ -616,6 +620,11 @@ int main(int argc, char **argv) {
         if (args.has("gpus") && (args.has("target") || args.has("target_mask") || args.has("ssim")))
             throw std::runtime_error("--target scores the frames of one GPU: it cannot be combined with --gpus");
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
+        const long lod = args.l("lod", 0);
+        if (args.has("lod") && lod < 1) throw std::runtime_error("--lod takes a depth of at least 1");
+        if (args.has("save_lod") && !args.has("lod")) throw std::runtime_error("--save_lod needs --lod");
+        if (args.has("lod") && (args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
+            throw std::runtime_error("--lod renders a truncated copy of the tree on one GPU: it cannot be combined with --gpus, --use_splitting or --use_guided_sampling");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 
@@ -668,6 +677,15 @@ int main(int argc, char **argv) {
         rend.aa_samples = (int)args.l("aa", 1);
         rend.aa_filter = aa_filter == "box" ? MNV_AA_BOX : MNV_AA_TENT;
         rend.projection = projection == "ortho" ? MNV_PROJ_ORTHO : projection == "equirect" ? MNV_PROJ_EQUIRECT : MNV_PROJ_PINHOLE;
+        if (lod > 0) {
+            if (tree.N <= 0) throw std::runtime_error("--lod needs a tree (N > 0)");
+            rend.set_lod((int)lod);
+            if (args.has("save_lod")) {
+                const std::unique_ptr<viewer::N3Tree> cut = tree.make_lod((int)lod);
+                cut->save_npz(args.get("save_lod", ""));
+                std::printf("save_lod: depth %ld, %d of %d chunks -> %s\n", lod, cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
+            }
+        }
         // --target: one device image per frame slot, filled before the frame that takes the slot is issued
         const std::string target = args.get("target", ""), target_mask = args.get("target_mask", "");
         const bool score = !target.empty(), ssim = args.has("ssim");

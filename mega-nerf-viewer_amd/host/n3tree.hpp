@@ -11,6 +11,7 @@
 
 #include <array>
 #include <cstdint>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -101,6 +102,13 @@ struct N3Tree {
     // contract, level 3 .. 10), extracted on the device from the packed accel and downloaded; colour == false leaves the vertices white.
     // Needs move_to_device (StatusError(MNV_E_INVALID) before).  The mesh has no device handle yet: update() uploads it for drawing.
     Mesh extract_surface(int level, float iso, bool colour = true, void *hip_stream = nullptr) const;
+
+    // A level of detail: this tree with every interior row mipped from its children (mnv_tree_mip_rows) and cut at max_depth
+    // (mnv_tree_truncate; the root chunk's voxels have depth 1), as a new tree on the device -- parent, sample counts where this tree has
+    // them there, the packed accel where this tree has one -- with the same offset / scale / format and its host arrays downloaded
+    // (save_npz writes it).  This tree is not changed.  Needs move_to_device (StatusError(MNV_E_INVALID) before); waits for the stream.
+    std::unique_ptr<N3Tree> make_lod(int max_depth, void *hip_stream = nullptr) const;
+    void make_lod_into(N3Tree &out, int max_depth, void *hip_stream = nullptr) const;  // the same into an existing (empty) tree
 
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;

@@ -179,6 +179,22 @@ struct VolumeRenderer::Impl {
     // projection == MNV_PROJ_EQUIRECT: the device table of mnv_equirect_tables (shared by the slots) and the size it was made for
     mnv::Buffer<float> equirect_dev;
     int equirect_w = 0, equirect_h = 0;
+    // set_lod: the depth frames are cut at (0: off), the truncated trees built so far (one per depth) and the structure of `tree` they
+    // were made from (tree_version), and the tree this frame marches (set by update_shared; null: `tree` itself)
+    int lod = 0, wire_lod = 0;
+    struct LodTree {
+        int depth;
+        std::unique_ptr<N3Tree> tree;
+    };
+    std::vector<LodTree> lod_trees;
+    uint64_t lod_version = 0;
+    N3Tree *lod_tree = nullptr;
+    N3Tree &march_tree() const { return lod_tree ? *lod_tree : *tree; }
+    void drop_lod_trees() {  // (frames in flight may march them)
+        if (!lod_trees.empty()) sync_all();
+        lod_trees.clear();
+        lod_tree = nullptr;
+    }
     // what draws this frame's inputs (set by render()): the grid, the visible meshes of VolumeRenderer::meshes, or both
     bool pass_grid = false;
     std::vector<const mnv_mesh *> pass_meshes;
@@ -488,6 +504,7 @@ VolumeRenderer::~VolumeRenderer() {}
 
 void VolumeRenderer::set(N3Tree &tree, long max_tree_capacity) {
     impl_->sync_all();
+    impl_->drop_lod_trees();
     tree.move_to_device(max_tree_capacity, true, true, impl_->stream);
     impl_->tree = &tree;
     impl_->max_tree_capacity = max_tree_capacity;
@@ -565,7 +582,14 @@ void VolumeRenderer::load_model(const std::string &npz_path) {
     set_model(desc, p.data<uint16_t>(), p.num_vals(), grid);
 }
 
+void VolumeRenderer::set_lod(int max_depth) {
+    if (max_depth < 0) throw StatusError(MNV_E_INVALID, "set_lod: the depth must be 0 (off) or at least 1");
+    impl_->lod = max_depth;
+}
+int VolumeRenderer::lod() const { return impl_->lod; }
+
 void VolumeRenderer::clear() {
+    impl_->drop_lod_trees();
     impl_->tree = nullptr;
     ++impl_->tree_version;
 }
@@ -670,6 +694,7 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
                           tree->data_format.basis_dim == 9 || tree->data_format.basis_dim == 16);
     const bool out_dim_differs = tree && model_on && I.mlp_desc.out_dim != tree->data_dim + 1;
     const bool inputs_set = I.inputs.tmax_px || I.inputs.rgba8_init;
+    const bool lod = tree && I.lod > 0;
     bool mesh_visible = false;
     for (const mnv_mesh *m : meshes) mesh_visible = mesh_visible || (m && mnv_mesh_visible(m));
     const bool projected = projection != MNV_PROJ_PINHOLE, aa = !projected && aa_samples != 1, ranks = !projected && !aa && I.comm;
@@ -685,6 +710,9 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
         const char *text;
     } refusals[] = {
         {I.target && I.comm, true, "set_target scores the frame of one rank: it cannot be combined with set_ranks"},
+        {lod && (options.use_splitting || options.use_guided_sampling), true,
+         "set_lod: frames of a truncated tree cannot edit or vote on the tree (use_splitting / use_guided_sampling)"},
+        {lod && I.comm, true, "set_lod is for one rank: it cannot be combined with set_ranks"},
         {projected && projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT, true, "projection: unknown projection"},
         {projected && inputs_set, true, "projection: set_frame_inputs holds images of a pinhole camera; it cannot be combined with another projection"},
         {projected && I.comm, true, "projection: orthographic / equirectangular frames are for one rank (set_ranks)"},
@@ -737,6 +765,20 @@ int VolumeRenderer::next_slot() const { return plan().overlaps ? (impl_->cur + 1
 // or write waits for them first (sync_all clears `overlapped`, so none of this may follow take_slot).
 void VolumeRenderer::update_shared(const FramePlan &P) {
     Impl &I = *impl_;
+    // set_lod: the tree this frame marches.  Trees made from another structure of the renderer's tree go (the refusals keep a frame with a
+    // level of detail from editing it, a frame without one may have); a missing one is built on slot 0's stream, which holds those edits.
+    I.lod_tree = nullptr;
+    if (I.lod > 0 && P.kind != FramePlan::BACKGROUND) {
+        if (I.lod_version != I.tree_version) I.drop_lod_trees();
+        I.lod_version = I.tree_version;
+        for (auto &e : I.lod_trees)
+            if (e.depth == I.lod) I.lod_tree = e.tree.get();
+        if (!I.lod_tree) {
+            I.sync_all();
+            I.lod_trees.push_back({I.lod, I.tree->make_lod(I.lod, I.stream)});
+            I.lod_tree = I.lod_trees.back().tree.get();
+        }
+    }
     if (P.kind == FramePlan::PROJECTED) {  // (draws no inputs; anti-aliasing buffers of earlier frames stay until the next pinhole frame)
         if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
             I.sync_all();  // frames in flight read the old table
@@ -759,14 +801,15 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
     for (const mnv_mesh *m : meshes)
         if (m && mnv_mesh_visible(m)) I.pass_meshes.push_back(m);
     if (!I.pass_meshes.empty()) I.can_reuse_results = false;  // (a mesh may have moved: the samples of the last guided frame were limited by it)
-    if (P.show_grid && (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version)) {
+    if (P.show_grid && (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version || I.wire_lod != I.lod)) {
         I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
-        const mnv_tree_view dv = I.tree->device_view();
+        const mnv_tree_view dv = I.march_tree().device_view();
         const int rc = I.wire ? mnv_wireframe_update(I.wire, &dv, options.grid_max_depth, I.stream)
                               : mnv_wireframe_create(&dv, options.grid_max_depth, I.stream, &I.wire);
         if (rc != MNV_OK) throw StatusError(rc, std::string("show_grid: ") + mnv_last_error());  // keeps the code (N != 2: unsupported)
         I.wire_depth = options.grid_max_depth;
         I.wire_version = I.tree_version;
+        I.wire_lod = I.lod;
         I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
     }
     if (P.kind == FramePlan::AA && (aa_samples != I.aa_k || aa_filter != I.aa_filter)) {
@@ -825,7 +868,7 @@ void VolumeRenderer::issue_background(const FramePlan &P, const mnv_camera &cv) 
 void VolumeRenderer::issue_plain(const FramePlan &P, const mnv_camera &cv) {
     Impl &I = *impl_;
     const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
-    mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cv, options.c_abi(), {0, 0, I.width, I.height}, &in, I.rgba, I.rgba8, I.slots[I.cur].stream),
+    mnv_check(mnv_render_voxels_accel_ex(I.march_tree().device.accel, &cv, options.c_abi(), {0, 0, I.width, I.height}, &in, I.rgba, I.rgba8, I.slots[I.cur].stream),
               "mnv_render_voxels_accel_ex");
     stats.used_accel = true;
 }
@@ -849,7 +892,7 @@ void VolumeRenderer::issue_guided_in_flight(const FramePlan &P, const mnv_camera
 // a frame alone on slot 0 that may refine the tree; returns whether it took visit marks
 bool VolumeRenderer::issue_tree(const FramePlan &P, const mnv_camera &cv) {
     Impl &I = *impl_;
-    N3Tree &tree = *I.tree;
+    N3Tree &tree = I.march_tree();
     const mnv_rect full = {0, 0, I.width, I.height};
     const mnv_frame_inputs in = I.frame_inputs(P, cv, options);
     const Impl::Trackers T = I.begin_refinement(P, camera, options, stats, 0);
@@ -951,12 +994,12 @@ void VolumeRenderer::issue_aa(const FramePlan &P, const mnv_camera &cv) {
     if (P.draws_inputs) {  // the batch call has no per-pixel inputs: grid pass + march per camera, in stream order (the slot's two grid images are reused)
         for (int k = 0; k < K; ++k) {
             const mnv_frame_inputs in = I.grid_inputs(S, S.stream, cams[k], options);
-            mnv_check(mnv_render_voxels_accel_ex(I.tree->device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub.get() + (size_t)k * frame_floats, nullptr, S.stream),
+            mnv_check(mnv_render_voxels_accel_ex(I.march_tree().device.accel, &cams[k], options.c_abi(), full, &in, S.aa_sub.get() + (size_t)k * frame_floats, nullptr, S.stream),
                       "mnv_render_voxels_accel_ex");
         }
     } else {
         const mnv_partition whole = {0, 1, 0, 0, 0};
-        mnv_check(mnv_render_voxels_accel_batch(I.tree->device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub.get(), nullptr, S.stream),
+        mnv_check(mnv_render_voxels_accel_batch(I.march_tree().device.accel, cams, K, options.c_abi(), full, whole, S.aa_sub.get(), nullptr, S.stream),
                   "mnv_render_voxels_accel_batch");
     }
     mnv_check(mnv_resolve_samples(S.aa_sub.get(), K, I.width, I.height, I.aa_weights_dev.get(), I.aa_radius, I.rgba, I.rgba8, S.stream), "mnv_resolve_samples");
@@ -975,7 +1018,7 @@ void VolumeRenderer::issue_projected(const mnv_camera &cv) {
     mnv_check(mnv_generate_rays(projection, &cv, {0, 0, I.width, I.height}, projection == MNV_PROJ_EQUIRECT ? I.equirect_dev.get() : nullptr,
                                 S.ray_origins.get(), S.ray_dirs.get(), S.stream),
               "mnv_generate_rays");
-    mnv_check(mnv_render_rays_accel(I.tree->device.accel, S.ray_origins.get(), S.ray_dirs.get(), I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
+    mnv_check(mnv_render_rays_accel(I.march_tree().device.accel, S.ray_origins.get(), S.ray_dirs.get(), I.width, I.height, options.c_abi(), nullptr, I.rgba, I.rgba8, S.stream),
               "mnv_render_rays_accel");
     stats.used_accel = true;
 }

@@ -150,6 +150,15 @@ struct VolumeRenderer {
     // Refused (StatusError, MNV_E_INVALID): unknown flag bits; a target together with set_ranks, in either order.
     void set_target(const uint8_t *rgba8_device, int flags = 0);
     void slot_metrics(int slot, mnv_frame_metric_values *out);
+    // Levels of detail (the reference has none).  0 (the default): render() is what it is without this call.  D >= 1: every frame marches
+    // N3Tree::make_lod(D) of the tree that was set -- interior rows mipped from their children, the tree cut at depth D -- instead of the
+    // tree itself: plain frames with or without frames in flight, anti-aliased and projected frames, the grid overlay (the grid of the
+    // truncated tree) and meshes.  The truncated tree is built at the first frame that needs it (the frames in flight are waited for),
+    // kept per depth, and all of them are dropped when set() gets a tree, clear() is called, or the tree was edited since.
+    // Refused by render() (StatusError, MNV_E_INVALID) with D >= 1, because such a frame would edit or vote on the tree:
+    // options.use_splitting, options.use_guided_sampling (hence visit marks), set_ranks.  A negative D is refused here.
+    void set_lod(int max_depth);
+    int lod() const;
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
