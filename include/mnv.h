@@ -952,6 +952,51 @@ int mnv_tree_mip_rows(const mnv_tree_view *device_tree, uint16_t *data_out, int3
 int mnv_tree_truncate(const mnv_tree_view *device_tree, const int32_t *chunk_depth, int32_t max_depth, int32_t new_capacity, int32_t *child_out,
                       uint16_t *data_out, int32_t *parent_out, int16_t *sample_counts_out, void *hip_stream);
 
+/* View-dependent levels of detail: one depth for the whole tree coarsens the voxels in front of the camera as much as those a kilometre
+ * away.  mnv_tree_select_cut decides per interior voxel whether its children are worth keeping for a LIST of viewpoints -- full depth where
+ * a voxel covers many pixels, coarse where several voxels share one -- and mnv_tree_cut compacts the tree along that set (rows: normally
+ * mnv_tree_mip_rows').  No look direction enters: the cut serves every direction from the listed eyes.  N == 2, depths as above.
+ *
+ * mnv_tree_select_cut.  views: HOST array of n_views viewpoints (world-space eye, focal length in pixels).  keep_out: device uint8
+ * [capacity], 1 = the chunk is kept, 0 = it is not (chunks that were not reached included).  kept_at_depth: HOST int64 [24], entry d = kept
+ * chunks of depth d (entry 0 unused, 0).  Waits for hip_stream (it hands the counts back).  tree->data is not read.
+ *
+ * Contract (binary32, one operation at a time in the stated order, no contraction, correctly rounded division, subnormals kept).
+ *   Host, once per view v:  q_k = offset[k] + scale[k] * eye[k] (the product, then the sum): the eye in tree space.  For d = 0 .. 23:
+ *     e_d = max_k(2^-d / scale[k]),  r = (focal_px * e_d) / pixels,  R2[v][d] = r * r; overflow to +inf is fine and means "always refine";
+ *     pixels == 0 makes every R2 +inf.
+ *   The root chunk is kept.  For a kept chunk c of depth d and a voxel j of it with child[c][j] != 0 (j = 4 x + 2 y + z): the chunk
+ *   c + child[c][j] is kept iff d < max_depth and (d < min_depth or D2 <= R2[v][d] for some view v), where, with (i_x, i_y, i_z) the
+ *   voxel's integer corner at depth d (twice the corner of the voxel above c, plus (x, y, z); the root's is 0):
+ *     lo_k = i_k * 2^-d,  hi_k = (i_k + 1) * 2^-d  (both exact),
+ *     g_k = max(max(lo_k - q_k, q_k - hi_k), 0),  w_k = g_k / scale[k],  D2 = (w_x * w_x + w_y * w_y) + w_z * w_z.
+ *   An eye inside the voxel has D2 == 0 and always refines.  A chunk under a chunk that is not kept is never reached, so the set is
+ *   parent-closed by construction.  In words: a voxel's children are kept when, from some listed eye, the voxel could cover `pixels`
+ *   pixels or more.  The walk visits kept chunks only; the order in which it does depends on the schedule and decides no output byte (every
+ *   byte of keep_out is the constant the rule gives, the counts are list sizes): no atomic operation decides an output byte.
+ * MNV_E_INVALID: a null argument; n_views outside [1, 4096]; an eye or focal_px that is not finite, focal_px <= 0, a q that is not finite;
+ * pixels negative or not finite; a scale[k] that is not finite and positive, an offset that is not finite; min_depth < 1 or
+ * max_depth < min_depth; among the links the walk FOLLOWS (those of voxels that refine): one outside [1, capacity), a chunk reached twice;
+ * host arrays in the view.  MNV_E_UNSUPPORTED: N != 2, kept chunks beyond 23 levels, data_dim above 1024.
+ *
+ * mnv_tree_cut is mnv_tree_truncate with the survivor predicate keep[c] != 0 (keep: device uint8 [capacity]) in place of the depth test: the
+ * survivors stay in ascending chunk order, a survivor's new index is its rank among them (an exclusive scan).  new_capacity must be the
+ * number of survivors (the sum of kept_at_depth); nothing is written at or beyond it.  child_out [new_capacity][8]: rank(c + child[c][j]) -
+ * rank(c) where the voxel has a child inside the tree that is kept, 0 otherwise; data_out (16-byte aligned), parent_out or NULL,
+ * sample_counts_out or NULL as mnv_tree_truncate has them.  THE CALLER guarantees that keep is parent-closed (mnv_tree_select_cut's is): a
+ * kept chunk under a parent that is not kept is compacted like the others but never linked, and its parent entry stays -1.  With keep =
+ * (1 <= chunk_depth <= D) the outputs are mnv_tree_truncate's at D, byte for byte.  Asynchronous on hip_stream for everything it writes; it
+ * reads keep[0] first, which waits for the work queued on hip_stream before the call.
+ * MNV_E_INVALID: a null argument, keep[0] == 0, new_capacity outside [1, capacity], misaligned rows, host arrays.  MNV_E_UNSUPPORTED as above. */
+typedef struct mnv_lod_view {
+    float eye[3];   /* world space */
+    float focal_px; /* focal length in pixels */
+} mnv_lod_view;
+int mnv_tree_select_cut(const mnv_tree_view *device_tree, const mnv_lod_view *views /*HOST*/, int32_t n_views, float pixels, int32_t min_depth,
+                        int32_t max_depth, uint8_t *keep_out /*device [capacity]*/, int64_t kept_at_depth[24] /*HOST*/, void *hip_stream);
+int mnv_tree_cut(const mnv_tree_view *device_tree, const uint8_t *keep, int32_t new_capacity, int32_t *child_out, uint16_t *data_out,
+                 int32_t *parent_out, int16_t *sample_counts_out, void *hip_stream);
+
 /* ------------------------------------------------ anti-aliased frames: jittered sub-frames in one launch, filtered resolve
  * Every march kernel sends one ray through each pixel centre.  A supersampled frame is K frames of the SAME camera whose principal point is
  * shifted by a sub-pixel offset (mnv_camera carries cx, cy per camera, and mnv_render_voxels_accel_batch marches up to MNV_MAX_BATCH cameras
@@ -1153,6 +1198,12 @@ int mnv_n3tree_gen_wireframe(const mnv_n3tree *t, int32_t max_depth, float *out,
  * with mnv_n3tree_free.  Runs on the null stream and waits for it.  MNV_E_INVALID: max_depth < 1, a tree that is not on the device;
  * otherwise the codes of the two calls. */
 int mnv_n3tree_make_lod(mnv_n3tree *t, int32_t max_depth, mnv_n3tree **out);
+/* The view-dependent level of detail of a tree that is on the device: mnv_tree_mip_rows, mnv_tree_select_cut for the n_views viewpoints, then
+ * mnv_tree_cut, as a NEW tree exactly as mnv_n3tree_make_lod makes one (arrays, accel, host arrays downloaded; `t` is not changed).
+ * kept_at_depth: int64 [24] or NULL, the kept chunks per depth.  Runs on the null stream and waits for it.  MNV_E_INVALID: a tree that is
+ * not on the device; otherwise the codes of the three calls. */
+int mnv_n3tree_make_view_lod(mnv_n3tree *t, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth,
+                             int64_t *kept_at_depth, mnv_n3tree **out);
 /* DataFormat::parse / to_string (src/data_format.cpp:5-41) */
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim);
 int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size_t buflen);
@@ -1275,6 +1326,14 @@ int mnv_renderer_slot_metrics(mnv_renderer *r, int32_t slot, mnv_frame_metric_va
  * MNV_E_INVALID while a level of detail meets what would edit or vote on the tree: options.use_splitting, options.use_guided_sampling,
  * several ranks (level 0 renders again).  MNV_E_INVALID here: a negative depth. */
 int mnv_renderer_set_lod(mnv_renderer *r, int32_t max_depth);
+/* VolumeRenderer::set_view_lod (n_views == 0, the default, = off: every frame is what it is without this call, byte for byte).  With
+ * n_views >= 1 the frames march the tree of mnv_n3tree_make_view_lod(views, pixels, min_depth, max_depth) instead of the tree that was set,
+ * for the frame kinds of mnv_renderer_set_lod.  The caller names the viewpoints the cut must serve (an offline renderer knows its poses up
+ * front); the renderer builds the tree at the first frame that needs it, keeps it until the views or parameters change, and drops it where
+ * it drops the trees of mnv_renderer_set_lod.  The views are copied.  mnv_renderer_render answers MNV_E_INVALID while a view cut meets
+ * options.use_splitting, options.use_guided_sampling, several ranks, or mnv_renderer_set_lod with a depth above 0.  MNV_E_INVALID here:
+ * n_views outside [0, 4096], views NULL with n_views > 0, and what mnv_tree_select_cut refuses in views, pixels, min_depth, max_depth. */
+int mnv_renderer_set_view_lod(mnv_renderer *r, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

@@ -410,6 +410,10 @@ _SIGNATURES = {
     "mnv_tree_truncate": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mnv_n3tree_make_lod": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "mnv_renderer_set_lod": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mnv_tree_select_cut": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "mnv_tree_cut": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_n3tree_make_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
+    "mnv_renderer_set_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -722,6 +726,18 @@ class N3Tree:
         h = C.c_void_p()
         _check(lib().mnv_n3tree_make_lod(self._h, int(depth), C.byref(h)))
         return N3Tree(h.value)
+
+    def make_view_lod(self, views, pixels: float, min_depth: int = 1, max_depth: int = 23, return_counts: bool = False):
+        """N3Tree::make_view_lod: a new tree on the device, as make_lod's, cut where `views` -- a sequence of ((x, y, z), focal_px):
+        world-space eyes and focal lengths in pixels -- say so: a voxel's children stay when the voxel could cover `pixels` pixels from
+        one of the eyes; nothing is cut above min_depth, nothing kept below max_depth.  return_counts: also the kept chunks per depth
+        (int64 [24]).  Needs move_to_device."""
+        table = lod_views(views)
+        h, kept = C.c_void_p(), np.zeros(24, np.int64)
+        _check(lib().mnv_n3tree_make_view_lod(self._h, table.ctypes.data, int(table.shape[0]), float(pixels), int(min_depth), int(max_depth),
+                                              kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
+        out = N3Tree(h.value)
+        return (out, kept) if return_counts else out
 
     def gen_wireframe(self, max_depth: int = 100000) -> np.ndarray:
         """N3Tree::gen_wireframe (n3tree.cpp:249-329) on the host arrays: float32 [n_vertices, 9] (position, colour, normal), 24 vertices
@@ -1289,6 +1305,15 @@ class Renderer:
         detail (use_splitting, use_guided_sampling, ranks) raises there, with MNV_E_INVALID."""
         _check(lib().mnv_renderer_set_lod(self._h, int(depth)))
 
+    def set_view_lod(self, views=(), pixels: float = 1.0, min_depth: int = 1, max_depth: int = 23) -> None:
+        """VolumeRenderer::set_view_lod: every frame marches N3Tree.make_view_lod(views, pixels, min_depth, max_depth) of the tree that was
+        set (built at the first frame that needs it, kept until the views or parameters change); an empty list (the default) is the full
+        tree, unchanged.  What render() refuses with a view cut (use_splitting, use_guided_sampling, ranks, set_lod above 0) raises
+        there, with MNV_E_INVALID."""
+        table = lod_views(views)
+        _check(lib().mnv_renderer_set_view_lod(self._h, table.ctypes.data if table.shape[0] else None, int(table.shape[0]), float(pixels),
+                                               int(min_depth), int(max_depth)))
+
     def set_target(self, target=None, flags: int = 0) -> None:
         """VolumeRenderer::set_target: score every frame against `target`, a contiguous uint8 device tensor [height, width, 4], on the
         device (METRIC_QUANTISED / METRIC_MASK_ALPHA / METRIC_SSIM); metrics(slot) collects a frame's score.  The tensor may change per
@@ -1631,6 +1656,30 @@ def tree_truncate(tree_view: TreeView, chunk_depth, max_depth: int, new_capacity
     [n, 8] or None); tree_view.data holds the rows to carry, chunk_depth is tree_mip_rows' array."""
     _check(lib().mnv_tree_truncate(C.byref(tree_view), _ptr(chunk_depth), int(max_depth), int(new_capacity), _ptr(child_out), _ptr(data_out),
                                    _ptr(parent_out), _ptr(sample_counts_out), C.c_void_p(stream)))
+
+
+def lod_views(views) -> np.ndarray:
+    """A sequence of ((x, y, z), focal_px) as the float32 [n, 4] array that is mnv_lod_view[n] (an [n, 4] array passes through)."""
+    if isinstance(views, np.ndarray):
+        return np.ascontiguousarray(views, np.float32).reshape(-1, 4)
+    return np.array([[e[0], e[1], e[2], f] for e, f in views], np.float32).reshape(-1, 4)
+
+
+def tree_select_cut(tree_view: TreeView, views, pixels: float, min_depth: int, max_depth: int, keep_out, stream: int = 0) -> np.ndarray:
+    """mnv_tree_select_cut: which chunks of a device tree view are worth keeping for `views` (lod_views' forms) at `pixels`, into keep_out
+    (uint8 device tensor [capacity]: 1 kept, 0 not).  Returns kept_at_depth, int64 [24].  Waits for `stream`."""
+    table = lod_views(views)
+    kept = np.zeros(24, np.int64)
+    _check(lib().mnv_tree_select_cut(C.byref(tree_view), table.ctypes.data if table.shape[0] else None, int(table.shape[0]), float(pixels), int(min_depth),
+                                     int(max_depth), _ptr(keep_out), kept.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(stream)))
+    return kept
+
+
+def tree_cut(tree_view: TreeView, keep, new_capacity: int, child_out, data_out, parent_out=None, sample_counts_out=None, stream: int = 0) -> None:
+    """mnv_tree_cut (asynchronous on `stream`): the chunks with keep != 0 of a device tree view, compacted in order, into device tensors of
+    new_capacity chunks, as tree_truncate's; `keep` (uint8 device tensor [capacity]) must be parent-closed (tree_select_cut's is)."""
+    _check(lib().mnv_tree_cut(C.byref(tree_view), _ptr(keep), int(new_capacity), _ptr(child_out), _ptr(data_out), _ptr(parent_out),
+                              _ptr(sample_counts_out), C.c_void_p(stream)))
 
 
 MAX_BATCH = 64

@@ -193,6 +193,24 @@ int mnv_n3tree_make_lod(mnv_n3tree *t, int32_t max_depth, mnv_n3tree **out) {
     });
 }
 
+int mnv_n3tree_make_view_lod(mnv_n3tree *t, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth,
+                             int64_t *kept_at_depth, mnv_n3tree **out) {
+    if (!t || !out || !views) return mnv::set_error(MNV_E_INVALID, "null argument");
+    *out = nullptr;
+    if (n_views < 1 || n_views > 4096) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_make_view_lod: n_views outside [1, 4096]");
+    return guarded([&] {
+        auto *h = new mnv_n3tree();
+        try {
+            t->tree.make_view_lod_into(h->tree, std::vector<mnv_lod_view>(views, views + n_views), pixels, min_depth, max_depth, nullptr, kept_at_depth);
+        } catch (...) {
+            delete h;
+            throw;
+        }
+        *out = h;
+        return MNV_OK;
+    });
+}
+
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim) {
     viewer::DataFormat f;
     f.parse(str ? str : "");
@@ -490,6 +508,15 @@ int mnv_renderer_set_lod(mnv_renderer *r, int32_t max_depth) {
     if (!r) return mnv::set_error(MNV_E_INVALID, "null argument");
     return guarded([&] {
         r->rend.set_lod(max_depth);
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_set_view_lod(mnv_renderer *r, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth) {
+    if (!r || (n_views > 0 && !views)) return mnv::set_error(MNV_E_INVALID, "null argument");
+    if (n_views < 0 || n_views > 4096) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_view_lod: n_views outside [0, 4096]");
+    return guarded([&] {
+        r->rend.set_view_lod(n_views ? std::vector<mnv_lod_view>(views, views + n_views) : std::vector<mnv_lod_view>(), pixels, min_depth, max_depth);
         return MNV_OK;
     });
 }

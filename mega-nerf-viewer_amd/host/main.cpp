@@ -49,6 +49,12 @@
 //   --lod D          the frames march the tree truncated at depth D (the root chunk's voxels have depth 1), every interior row mipped
 //                    from its children first (VolumeRenderer::set_lod, N3Tree::make_lod: mnv_tree_mip_rows + mnv_tree_truncate).
 //                    --save_lod OUT.npz writes that tree.  Refused with --gpus, --use_splitting and --use_guided_sampling.
+//   --lod_pixels P   the frames march a view-dependent cut of the tree (VolumeRenderer::set_view_lod, N3Tree::make_view_lod:
+//                    mnv_tree_mip_rows + mnv_tree_select_cut + mnv_tree_cut): a voxel's children stay where the voxel could cover P pixels
+//                    from the eye of one of the poses this run renders (the --frames / --orbit loop is stepped on a copy of the camera
+//                    first; focal length max(fx, fy)); nothing is cut above depth --lod_min (default 1), nothing kept below --lod_max
+//                    (default 23).  Prints the kept chunks per depth; --save_lod OUT.npz writes the tree.  Refused with --lod, --gpus,
+//                    --use_splitting and --use_guided_sampling.
 //   --target PREFIX  score frame f against PREFIX_%04d.ppm (the P6 files --out writes) on the device (VolumeRenderer::set_target,
 //                    mnv_frame_metrics with MNV_METRIC_QUANTISED: the file --out would write against the file that was read) and print
 //                    "frame F: psnr ..." when the frame is collected, then the means over the frames.  --ssim adds SSIM (11 x 11 Gaussian
@@ -144,6 +150,8 @@ void usage() {
               "                  [--mesh FILE.obj[,unlit] [--mesh_color r,g,b] [--mesh_translate x,y,z] [--mesh_rotate x,y,z] [--mesh_scale s]]...\n"
               "                  [--extract_mesh OUT.obj [--extract_level L] [--extract_iso S] [--extract_unlit]]   the density's iso-surface as a mesh\n"
               "                  [--lod D [--save_lod OUT.npz]]   march (and write) the tree truncated at depth D, interior rows mipped from their children\n"
+              "                  [--lod_pixels P [--lod_min D] [--lod_max D] [--save_lod OUT.npz]]   march (and write) the tree cut where a voxel covers\n"
+              "                   less than P pixels from every pose of this run\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
               "                   0 = excluded): PSNR and, with --ssim, SSIM per frame and their means; not with --gpus.  Out of scope: pose\n"
               "                   lists (poses stay --orbit or the API) and LPIPS (it needs a network this repository does not have)\n"
@@ -622,7 +630,14 @@ int main(int argc, char **argv) {
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
         const long lod = args.l("lod", 0);
         if (args.has("lod") && lod < 1) throw std::runtime_error("--lod takes a depth of at least 1");
-        if (args.has("save_lod") && !args.has("lod")) throw std::runtime_error("--save_lod needs --lod");
+        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels")) throw std::runtime_error("--save_lod needs --lod or --lod_pixels");
+        const float lod_pixels = args.f("lod_pixels", 0.f);
+        const long lod_min = args.l("lod_min", 1), lod_max = args.l("lod_max", 23);
+        if (args.has("lod_pixels") && (!std::isfinite(lod_pixels) || lod_pixels < 0.f)) throw std::runtime_error("--lod_pixels takes a finite size in pixels, 0 or more");
+        if ((args.has("lod_min") || args.has("lod_max")) && !args.has("lod_pixels")) throw std::runtime_error("--lod_min and --lod_max need --lod_pixels");
+        if (args.has("lod_pixels") && (lod_min < 1 || lod_max < lod_min)) throw std::runtime_error("--lod_pixels: need 1 <= --lod_min <= --lod_max");
+        if (args.has("lod_pixels") && (args.has("lod") || args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
+            throw std::runtime_error("--lod_pixels renders a cut copy of the tree on one GPU: it cannot be combined with --lod, --gpus, --use_splitting or --use_guided_sampling");
         if (args.has("lod") && (args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
             throw std::runtime_error("--lod renders a truncated copy of the tree on one GPU: it cannot be combined with --gpus, --use_splitting or --use_guided_sampling");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
@@ -684,6 +699,28 @@ int main(int argc, char **argv) {
                 const std::unique_ptr<viewer::N3Tree> cut = tree.make_lod((int)lod);
                 cut->save_npz(args.get("save_lod", ""));
                 std::printf("save_lod: depth %ld, %d of %d chunks -> %s\n", lod, cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
+            }
+        }
+        if (args.has("lod_pixels")) {
+            if (tree.N <= 0) throw std::runtime_error("--lod_pixels needs a tree (N > 0)");
+            // the eye of every pose this run renders: the frame loop below, stepped on a copy of the camera
+            std::vector<mnv_lod_view> views;
+            viewer::Camera walk = rend.camera;
+            for (long f = 0; f < std::max<long>(frames, 1) && views.size() < 4096; ++f) {
+                views.push_back({{walk.center.x, walk.center.y, walk.center.z}, std::max(walk.fx, walk.fy)});
+                if (orbit == 0.0) break;  // (every frame has the same pose)
+                orbit_step(walk, orbit);
+            }
+            if (orbit != 0.0 && frames > 4096) throw std::runtime_error("--lod_pixels serves at most 4096 poses (--frames)");
+            rend.set_view_lod(views, lod_pixels, (int)lod_min, (int)lod_max);
+            int64_t kept[24];
+            const std::unique_ptr<viewer::N3Tree> cut = tree.make_view_lod(views, lod_pixels, (int)lod_min, (int)lod_max, nullptr, kept);
+            std::printf("lod_pixels: %g pixels, %zu view(s), %d of %d chunks, kept per depth:", (double)lod_pixels, views.size(), cut->capacity, tree.capacity);
+            for (int d = 1; d < 24 && kept[d] > 0; ++d) std::printf(" %lld", (long long)kept[d]);
+            std::printf("\n");
+            if (args.has("save_lod")) {
+                cut->save_npz(args.get("save_lod", ""));
+                std::printf("save_lod: %d of %d chunks -> %s\n", cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
             }
         }
         // --target: one device image per frame slot, filled before the frame that takes the slot is issued

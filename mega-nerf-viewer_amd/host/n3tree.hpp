@@ -11,6 +11,7 @@
 
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -110,6 +111,15 @@ struct N3Tree {
     std::unique_ptr<N3Tree> make_lod(int max_depth, void *hip_stream = nullptr) const;
     void make_lod_into(N3Tree &out, int max_depth, void *hip_stream = nullptr) const;  // the same into an existing (empty) tree
 
+    // A view-dependent level of detail: the rows mipped as above, then the tree cut where mnv_tree_select_cut says so for the listed
+    // viewpoints (a voxel's children stay when, from some eye, the voxel could cover `pixels` pixels; nothing below min_depth is cut,
+    // nothing beyond max_depth is kept) and compacted by mnv_tree_cut.  The result is what make_lod's is: a new tree on the device with
+    // this tree's accel / parent / sample counts where it has them, host arrays downloaded.  kept_at_depth: int64 [24] or null.
+    std::unique_ptr<N3Tree> make_view_lod(const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23,
+                                          void *hip_stream = nullptr, int64_t *kept_at_depth = nullptr) const;
+    void make_view_lod_into(N3Tree &out, const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23,
+                            void *hip_stream = nullptr, int64_t *kept_at_depth = nullptr) const;
+
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;
 
@@ -122,6 +132,9 @@ struct N3Tree {
 private:
     int N2_ = 0, N3_ = 0;
     void check_sizes();
+    // the common end of make_lod_into / make_view_lod_into: `o` becomes a device tree of new_cap chunks that `cut` fills
+    // (child, data, parent, sample counts or null), with host arrays and, where this tree has one, an accel
+    void compact_into(N3Tree &o, int64_t new_cap, const std::function<void(int32_t *, uint16_t *, int32_t *, int16_t *)> &cut, void *hip_stream) const;
 };
 
 }  // namespace viewer

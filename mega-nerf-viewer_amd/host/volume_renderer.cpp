@@ -189,10 +189,19 @@ struct VolumeRenderer::Impl {
     std::vector<LodTree> lod_trees;
     uint64_t lod_version = 0;
     N3Tree *lod_tree = nullptr;
+    // set_view_lod: the viewpoints (empty: off) and parameters of the view-dependent cut, the tree built for them (until they change or
+    // the trees above go), and a number that changes with every call (the grid overlay's edge list belongs to one of them)
+    std::vector<mnv_lod_view> view_lod_views;
+    float view_lod_pixels = 1.f;
+    int view_lod_min = 1, view_lod_max = 23;
+    std::unique_ptr<N3Tree> view_lod_tree;
+    int view_lod_gen = 0, wire_view_gen = 0;
+    int view_lod_token() const { return view_lod_views.empty() ? 0 : view_lod_gen; }
     N3Tree &march_tree() const { return lod_tree ? *lod_tree : *tree; }
     void drop_lod_trees() {  // (frames in flight may march them)
-        if (!lod_trees.empty()) sync_all();
+        if (!lod_trees.empty() || view_lod_tree) sync_all();
         lod_trees.clear();
+        view_lod_tree.reset();
         lod_tree = nullptr;
     }
     // what draws this frame's inputs (set by render()): the grid, the visible meshes of VolumeRenderer::meshes, or both
@@ -588,6 +597,29 @@ void VolumeRenderer::set_lod(int max_depth) {
 }
 int VolumeRenderer::lod() const { return impl_->lod; }
 
+void VolumeRenderer::set_view_lod(const std::vector<mnv_lod_view> &views, float pixels, int min_depth, int max_depth) {
+    Impl &I = *impl_;
+    if (views.size() > 4096) throw StatusError(MNV_E_INVALID, "set_view_lod: at most 4096 viewpoints");
+    if (!views.empty()) {
+        if (!std::isfinite(pixels) || pixels < 0.f) throw StatusError(MNV_E_INVALID, "set_view_lod: pixels must be finite and not negative");
+        if (min_depth < 1 || max_depth < min_depth) throw StatusError(MNV_E_INVALID, "set_view_lod: need 1 <= min_depth <= max_depth");
+        for (const mnv_lod_view &v : views)
+            if (!std::isfinite(v.eye[0]) || !std::isfinite(v.eye[1]) || !std::isfinite(v.eye[2]) || !std::isfinite(v.focal_px) || !(v.focal_px > 0.f))
+                throw StatusError(MNV_E_INVALID, "set_view_lod: an eye must be finite, focal_px finite and positive");
+    }
+    if (I.view_lod_tree) {  // (frames in flight may march it)
+        I.sync_all();
+        I.view_lod_tree.reset();
+        I.lod_tree = nullptr;
+    }
+    I.view_lod_views = views;
+    I.view_lod_pixels = pixels;
+    I.view_lod_min = min_depth;
+    I.view_lod_max = max_depth;
+    ++I.view_lod_gen;
+}
+bool VolumeRenderer::view_lod() const { return !impl_->view_lod_views.empty(); }
+
 void VolumeRenderer::clear() {
     impl_->drop_lod_trees();
     impl_->tree = nullptr;
@@ -694,7 +726,7 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
                           tree->data_format.basis_dim == 9 || tree->data_format.basis_dim == 16);
     const bool out_dim_differs = tree && model_on && I.mlp_desc.out_dim != tree->data_dim + 1;
     const bool inputs_set = I.inputs.tmax_px || I.inputs.rgba8_init;
-    const bool lod = tree && I.lod > 0;
+    const bool lod = tree && I.lod > 0, view_lod = tree && !I.view_lod_views.empty();
     bool mesh_visible = false;
     for (const mnv_mesh *m : meshes) mesh_visible = mesh_visible || (m && mnv_mesh_visible(m));
     const bool projected = projection != MNV_PROJ_PINHOLE, aa = !projected && aa_samples != 1, ranks = !projected && !aa && I.comm;
@@ -713,6 +745,10 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
         {lod && (options.use_splitting || options.use_guided_sampling), true,
          "set_lod: frames of a truncated tree cannot edit or vote on the tree (use_splitting / use_guided_sampling)"},
         {lod && I.comm, true, "set_lod is for one rank: it cannot be combined with set_ranks"},
+        {view_lod && (options.use_splitting || options.use_guided_sampling), true,
+         "set_view_lod: frames of a cut tree cannot edit or vote on the tree (use_splitting / use_guided_sampling)"},
+        {view_lod && I.comm, true, "set_view_lod is for one rank: it cannot be combined with set_ranks"},
+        {view_lod && lod, true, "set_view_lod and set_lod choose the tree a frame marches: only one of them can be on"},
         {projected && projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT, true, "projection: unknown projection"},
         {projected && inputs_set, true, "projection: set_frame_inputs holds images of a pinhole camera; it cannot be combined with another projection"},
         {projected && I.comm, true, "projection: orthographic / equirectangular frames are for one rank (set_ranks)"},
@@ -779,6 +815,15 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
             I.lod_tree = I.lod_trees.back().tree.get();
         }
     }
+    if (!I.view_lod_views.empty() && P.kind != FramePlan::BACKGROUND) {  // set_view_lod: the same with the one tree of the current views
+        if (I.lod_version != I.tree_version) I.drop_lod_trees();
+        I.lod_version = I.tree_version;
+        if (!I.view_lod_tree) {
+            I.sync_all();
+            I.view_lod_tree = I.tree->make_view_lod(I.view_lod_views, I.view_lod_pixels, I.view_lod_min, I.view_lod_max, I.stream);
+        }
+        I.lod_tree = I.view_lod_tree.get();
+    }
     if (P.kind == FramePlan::PROJECTED) {  // (draws no inputs; anti-aliasing buffers of earlier frames stay until the next pinhole frame)
         if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
             I.sync_all();  // frames in flight read the old table
@@ -801,7 +846,8 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
     for (const mnv_mesh *m : meshes)
         if (m && mnv_mesh_visible(m)) I.pass_meshes.push_back(m);
     if (!I.pass_meshes.empty()) I.can_reuse_results = false;  // (a mesh may have moved: the samples of the last guided frame were limited by it)
-    if (P.show_grid && (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version || I.wire_lod != I.lod)) {
+    if (P.show_grid && (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version || I.wire_lod != I.lod ||
+                        I.wire_view_gen != I.view_lod_token())) {
         I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
         const mnv_tree_view dv = I.march_tree().device_view();
         const int rc = I.wire ? mnv_wireframe_update(I.wire, &dv, options.grid_max_depth, I.stream)
@@ -810,6 +856,7 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
         I.wire_depth = options.grid_max_depth;
         I.wire_version = I.tree_version;
         I.wire_lod = I.lod;
+        I.wire_view_gen = I.view_lod_token();
         I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
     }
     if (P.kind == FramePlan::AA && (aa_samples != I.aa_k || aa_filter != I.aa_filter)) {

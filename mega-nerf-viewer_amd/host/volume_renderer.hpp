@@ -159,6 +159,16 @@ struct VolumeRenderer {
     // options.use_splitting, options.use_guided_sampling (hence visit marks), set_ranks.  A negative D is refused here.
     void set_lod(int max_depth);
     int lod() const;
+    // View-dependent levels of detail.  An empty list (the default): render() is what it is without this call.  Otherwise every frame
+    // marches N3Tree::make_view_lod(views, pixels, min_depth, max_depth) of the tree that was set: full depth where a voxel could cover
+    // `pixels` pixels from one of the listed eyes, coarser elsewhere.  The CALLER names the viewpoints the cut must serve -- an offline
+    // renderer knows its poses up front, and a cut that serves all of them is built once: nothing is re-cut per frame.  Same frame
+    // kinds as set_lod; the tree is built at the first frame that needs it, kept until the views or parameters change, and dropped
+    // where set_lod's trees are.  Refused by render() (StatusError, MNV_E_INVALID) with options.use_splitting,
+    // options.use_guided_sampling, set_ranks, and set_lod(D > 0) at the same time.  Refused here: more than 4096 views, an eye or
+    // focal length that is not finite, focal_px <= 0, pixels negative or not finite, min_depth < 1, max_depth < min_depth.
+    void set_view_lod(const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23);
+    bool view_lod() const;
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
