@@ -470,6 +470,8 @@ _PROBE_SIGNATURES = {
     "mnv_hook_probe_half": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_sh": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_half_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mnv_hook_probe_sh_mix": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_setup_ray": (C.c_int, [C.POINTER(ProbeFrame), C.POINTER(ProbeCamBlock), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -88,7 +88,22 @@ __device__ __forceinline__ void load_exp_table(uint64_t *lds_tab) {
     __syncthreads();
 }
 
+// fma(fma(fma(c0, r, c1), r, c2), r, 1.0) on literals c0, c1, c2: three v_fma_f64.  The first two are written out so that c0 and c2 come
+// from scalar register pairs (VOP3 reads one scalar operand; c1 is the one vector constant).  From __builtin_fma the compiler selects
+// the two-address form (v_fmac_f64), which wants its constant addend in vector registers: it then keeps c1 AND c2 in VGPR pairs for the
+// whole kernel and copies one before every use -- four registers the march kernel (64 VGPRs, 8 wavefronts per SIMD) has to spill for.
+__device__ __forceinline__ double expf_poly(double r, double c0, double c1, double c2) {
+    double z, y;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(z) : "s"(c0), "v"(r), "v"(c1));
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(y) : "v"(z), "v"(r), "s"(c2));
+    return __builtin_fma(y, r, 1.0);
+}
+
 // expf, bit-compatible with glibc 2.35 (non-FMA variant); `tab` lives in LDS.
+// The polynomial is glibc's (C0 r + C1) r^2 + (C2 r + 1) in Horner form with explicit fused operations: 3 binary64 instructions for 5,
+// and the same binary32 result for every input that reaches it -- tools/expf_contraction_proof.cpp enumerates them
+// (tests/test_expf_contraction_host.py), tests/test_primitives_gpu.py holds the device function on all 2^32 inputs.  Range reduction,
+// table, the final product with s and the special cases are glibc's, statement for statement.
 __device__ __forceinline__ float exact_expf(float x, const uint64_t *tab) {
     const uint32_t ix = __float_as_uint(x);
     const uint32_t abstop = (ix >> 20) & 0x7ffu;
@@ -113,10 +128,7 @@ __device__ __forceinline__ float exact_expf(float x, const uint64_t *tab) {
     uint64_t t = tab[ki & 31u];
     t += ki << 47;
     const double s = __longlong_as_double((long long)t);
-    z = C0 * r + C1;
-    const double r2 = r * r;
-    double y = C2 * r + 1.0;
-    y = z * r2 + y;
+    double y = expf_poly(r, C0, C1, C2);
     y = y * s;
     return (float)y;
 }
@@ -141,10 +153,7 @@ __device__ __forceinline__ float exact_expf_select(float x, const uint64_t *tab)
     uint64_t t = tab[ki & 31u];
     t += ki << 47;
     const double s = __longlong_as_double((long long)t);
-    z = C0 * r + C1;
-    const double r2 = r * r;
-    double y = C2 * r + 1.0;
-    y = z * r2 + y;
+    double y = expf_poly(r, C0, C1, C2);
     y = y * s;
     float res = (float)y;
     const uint32_t ix = __float_as_uint(x);
@@ -399,6 +408,41 @@ __device__ __forceinline__ float sh_channel(const float *b, F coef, int off) {
     }
     if constexpr (BASIS >= 4) {
         tmp += b[1] * coef(off + 1) + b[2] * coef(off + 2) + b[3] * coef(off + 3);
+    }
+    return tmp;
+}
+
+// (float)half * b in one instruction, for the march kernels' colour blocks: v_fma_mix_f32 takes the binary16 operand straight from the
+// low or the high half (`hi`) of a raw 32-bit row word -- no v_cvt_f32_f16, no shift or mask -- and its addend is -0: x * y + (-0) is
+// x * y for every x and y, the sign of a zero product included (an addend of +0 would turn a product of -0 into +0).  The -0 is the
+// inline constant 0 under the instruction's negate modifier, so it costs no register.  The instruction is written out: from
+// __builtin_fmaf((float)h, b, -0.0f) the compiler folds the addend away and selects the conversion and the product again.  `hi` is a
+// constant wherever the kernels call this.  tests/test_half_product_gpu.py holds it against the binary32 product on all 65,536 patterns
+// of either half.  (Not for the guided fused kernels: a VOP3P instruction with op_sel beside MFMAs, see the Makefile's NOPK.)
+__device__ __forceinline__ float half_mul(uint32_t word, bool hi, float b) {
+    float r;
+    if (hi) asm("v_fma_mix_f32 %0, %1, %2, neg(0) op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(word), "v"(b));
+    else asm("v_fma_mix_f32 %0, %1, %2, neg(0) op_sel_hi:[1,0,0]" : "=v"(r) : "v"(word), "v"(b));
+    return r;
+}
+
+// sh_channel on the raw words of a row: `word(j)` returns 32-bit word j (coefficients 2j and 2j + 1 of the row), and coefficient
+// off + k meets b[k] in half_mul.  The same products in the same summation order, term for term.
+template <int BASIS, typename W>
+__device__ __forceinline__ float sh_channel_mix(const float *b, W word, int off) {
+    auto p = [&](int k) -> float { return half_mul(word((off + k) >> 1), ((off + k) & 1) != 0, b[k]); };
+    float tmp = p(0);
+    if constexpr (BASIS >= 25) {
+        tmp += p(16) + p(17) + p(18) + p(19) + p(20) + p(21) + p(22) + p(23) + p(24);
+    }
+    if constexpr (BASIS >= 16) {
+        tmp += p(9) + p(10) + p(11) + p(12) + p(13) + p(14) + p(15);
+    }
+    if constexpr (BASIS >= 9) {
+        tmp += p(4) + p(5) + p(6) + p(7) + p(8);
+    }
+    if constexpr (BASIS >= 4) {
+        tmp += p(1) + p(2) + p(3);
     }
     return tmp;
 }

@@ -732,11 +732,8 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         constexpr int NW = CHAN_BYTES / 4;
                         ChanWords<NW> cw;
                         cw = *reinterpret_cast<const ChanWords<NW> *>(A.rows + (int64_t)vx * ROW_BYTES + my_c * CHAN_BYTES);
-                        auto coef = [&](int k) -> float {
-                            const uint32_t wd = cw.w[k >> 1];
-                            return half_bits_to_float((uint16_t)((k & 1) ? (wd >> 16) : (wd & 0xffffu)));
-                        };
-                        const float tmp = sh_channel<BASIS>(b, coef, 0);
+                        // binary16 coefficient times binary32 basis straight from the raw words (half_mul: no conversion instruction)
+                        const float tmp = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return cw.w[j]; }, 0);
                         // (both expressions are copied in mnv_probe.hip: colour_sigmoid_hw / colour_sigmoid_exact; change them together)
                         if constexpr (MODE == 4) {
                             // colour-only arithmetic: it feeds no branch (opacity, transmittance and the step sequence stay exact),
@@ -810,8 +807,8 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
 #pragma unroll
                     for (int k = 0; k < NB; ++k) b[k] = my_ray[k * BLOCK];
                     auto chan = [&](int c) -> float {
-                        auto coef = [&](int k) -> float { return half_bits_to_float((uint16_t)half_at(k)); };
-                        const float tmp = sh_channel<BASIS>(b, coef, c * BASIS);
+                        // binary16 coefficient times binary32 basis straight from the raw row words (half_mul: no conversion instruction)
+                        const float tmp = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, c * BASIS);
                         // (both expressions are copied in mnv_probe.hip: colour_sigmoid_hw / colour_sigmoid_exact; change them together)
                         if constexpr (MODE == 4) {
                             // colour-only arithmetic: it feeds no branch (opacity, transmittance and the step sequence stay exact),
@@ -840,9 +837,9 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                     const uint2 qd = *reinterpret_cast<const uint2 *>(A.rows + (int64_t)vox * ROW_BYTES);
                     if constexpr (BRICK) settle(qd.y >> 16);
                     if (dense) {
-                        o0 += half_bits_to_float((uint16_t)(qd.x & 0xffffu)) * weight;
-                        o1 += half_bits_to_float((uint16_t)(qd.x >> 16)) * weight;
-                        o2 += half_bits_to_float((uint16_t)(qd.y & 0xffffu)) * weight;
+                        o0 += half_mul(qd.x, false, weight);
+                        o1 += half_mul(qd.x, true, weight);
+                        o2 += half_mul(qd.y, false, weight);
                     }
                 }
             }

@@ -133,6 +133,37 @@ __global__ void __launch_bounds__(kThreads) probe_sh_kernel(const float *__restr
     for (int c = 0; c < 3; ++c) channel_out[3 * i + c] = mnv::sh_channel<B>(b, coef, c * B);
 }
 
+// half_mul on every pair (word w, multiplier m): out[0][m][w] from the low half of words[w], out[1][m][w] from its high half -- every
+// thread, so every lane position, runs both forms of the instruction
+__global__ void __launch_bounds__(kThreads) probe_half_product_kernel(const uint32_t *__restrict__ words, int64_t n_words, const float *__restrict__ mult,
+                                                                      int64_t n_mult, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n_words * n_mult) return;
+    const uint32_t w = words[i % n_words];
+    const float b = mult[i / n_words];
+    out[i] = mnv::half_mul(w, false, b);
+    out[n_words * n_mult + i] = mnv::half_mul(w, true, b);
+}
+
+// basis [n][B], coefs [n][3 * B] binary16 bits (channel c at c * B, as a voxel row) -> channel_out [n][3] through sh_channel_mix on the
+// row's 32-bit words, as the march kernels' per-lane colour block calls it (channel offsets 0, B, 2 B: odd ones for odd B)
+template <int B>
+__global__ void __launch_bounds__(kThreads) probe_sh_mix_kernel(const float *__restrict__ basis, const uint16_t *__restrict__ coefs, int64_t n,
+                                                                float *__restrict__ channel_out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    float b[B];
+#pragma unroll
+    for (int k = 0; k < B; ++k) b[k] = basis[i * B + k];
+    constexpr int NW = (3 * B + 1) / 2;
+    const uint16_t *row = coefs + i * 3 * B;
+    uint32_t rw[NW];
+#pragma unroll
+    for (int j = 0; j < NW; ++j) rw[j] = (uint32_t)row[2 * j] | (2 * j + 1 < 3 * B ? (uint32_t)row[2 * j + 1] << 16 : 0u);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) channel_out[3 * i + c] = mnv::sh_channel_mix<B>(b, [&](int j) -> uint32_t { return rw[j]; }, c * B);
+}
+
 // one row of kSetupRow floats per element: dir[3] invdir[3] delta_scale tmin tmax in_bbox basis[25] true_dir[3] vdir[3]
 template <int B>
 __global__ void __launch_bounds__(kThreads) probe_setup_ray_kernel(const mnv::FrameParams P, const mnv::CamBlock cam, const int32_t *__restrict__ ix,
@@ -243,6 +274,35 @@ int mnv_hook_probe_sh(int basis_dim, const float *dirs, const uint16_t *coefs, i
     default: return set_error(MNV_E_INVALID, "mnv_hook_probe_sh: basis_dim must be 1, 4, 9, 16 or 25");
     }
     return check_hip(hipGetLastError(), "probe_sh_kernel");
+}
+
+// words [n_words] uint32, mult [n_mult] float -> out [2][n_mult][n_words] float: half_mul of the low (out[0]) and the high (out[1]) half
+// of every word with every multiplier
+int mnv_hook_probe_half_product(const uint32_t *words, int64_t n_words, const float *mult, int64_t n_mult, float *out, void *hip_stream) {
+    if (n_words < 0 || n_mult < 0 || n_words > (1 << 24) || n_mult > (1 << 10) || (n_words > 0 && n_mult > 0 && (!words || !mult || !out)))
+        return set_error(MNV_E_INVALID, "mnv_hook_probe_half_product: bad arguments");
+    if (n_words == 0 || n_mult == 0) return MNV_OK;
+    hipLaunchKernelGGL(probe_half_product_kernel, dim3(grid_for(n_words * n_mult)), dim3(kThreads), 0, (hipStream_t)hip_stream, words, n_words, mult,
+                       n_mult, out);
+    return check_hip(hipGetLastError(), "probe_half_product_kernel");
+}
+
+// sh_channel_mix (the march kernels' channel sum on raw row words): basis [n][basis_dim] float, coefs [n][3 * basis_dim] binary16 bits
+// -> channel_out [n][3]
+int mnv_hook_probe_sh_mix(int basis_dim, const float *basis, const uint16_t *coefs, int64_t n, float *channel_out, void *hip_stream) {
+    if (n < 0 || (n > 0 && (!basis || !coefs || !channel_out))) return set_error(MNV_E_INVALID, "mnv_hook_probe_sh_mix: bad arguments");
+    if (n == 0) return MNV_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const dim3 grid(grid_for(n)), block(kThreads);
+    switch (basis_dim) {
+    case 1: hipLaunchKernelGGL(probe_sh_mix_kernel<1>, grid, block, 0, stream, basis, coefs, n, channel_out); break;
+    case 4: hipLaunchKernelGGL(probe_sh_mix_kernel<4>, grid, block, 0, stream, basis, coefs, n, channel_out); break;
+    case 9: hipLaunchKernelGGL(probe_sh_mix_kernel<9>, grid, block, 0, stream, basis, coefs, n, channel_out); break;
+    case 16: hipLaunchKernelGGL(probe_sh_mix_kernel<16>, grid, block, 0, stream, basis, coefs, n, channel_out); break;
+    case 25: hipLaunchKernelGGL(probe_sh_mix_kernel<25>, grid, block, 0, stream, basis, coefs, n, channel_out); break;
+    default: return set_error(MNV_E_INVALID, "mnv_hook_probe_sh_mix: basis_dim must be 1, 4, 9, 16 or 25");
+    }
+    return check_hip(hipGetLastError(), "probe_sh_mix_kernel");
 }
 
 // frame: host pointer to a FrameParams; cam: host pointer to a CamBlock, or NULL for frame->cam (the kernels take the camera apart from
