@@ -126,6 +126,17 @@ struct AccelView {
     int32_t data_dim, basis_dim, format, capacity;
 };
 
+// Buffers of the march's measurement instruments (test-hook build, diagnostics instantiation; filled and read by mnv_accel_diag.hip)
+struct AccelDiag {
+    Buffer<unsigned long long> stats;     // MNV_STATS: 16 counters, then the phase sums
+    Buffer<uint32_t> line_bits;           // MNV_FOOTPRINT=<file>: one bit per 128-byte line of grid2i / grid2, recs, nodes, rows, grid2_vox, grid_vox
+    uint32_t line_base[7] = {};           // first line of each of those regions in the bitmap; [6] = all lines
+    Buffer<unsigned long long> timeline;  // MNV_TIMELINE=<file>: tile / wavefront time stamps of the last launch
+    size_t timeline_tiles = 0, timeline_waves = 0, timeline_tiles_per_frame = 0;
+    Buffer<uint8_t> shadow_nodes;         // MNV_SHADOW shadow loads: copies of nodes (or recs) / rows at other addresses, read with the same
+    Buffer<uint8_t> shadow_rows;          // access pattern to attribute the HBM traffic by array
+};
+
 }  // namespace mnv
 
 struct mnv_accel {
@@ -135,8 +146,6 @@ struct mnv_accel {
     mnv::Buffer<uint32_t> grid, grid_vox, grid2, grid2_vox;
     mnv::Buffer<uint32_t> grid2i;              // [2^L2]^3
     mnv::Buffer<uint2> recs;                   // [reserved][8]
-    mnv::Buffer<uint8_t> shadow_nodes;         // MNV_ABLATE shadow loads (test-hook build, diagnostics instantiation): copies of nodes (or recs) / rows at
-    mnv::Buffer<uint8_t> shadow_rows;          // other addresses, read with the same access pattern to attribute the HBM traffic by array
     mnv::Buffer<uint32_t> nodes_spare;         // second set of nodes / rows / depth, allocated by the first prune (accel_apply_prune writes the
     mnv::Buffer<uint8_t> rows_spare;           // survivors out of place, then the sets swap)
     mnv::Buffer<int32_t> depth_spare;
@@ -144,14 +153,10 @@ struct mnv_accel {
     mnv::Buffer<int32_t> flags;                // [8] device scratch of refresh: changed, deepest depth, grids dirty, shallowest voxel, patch items (appended / changed)
     mnv::Buffer<uint32_t> patch_prefix;        // refresh: first patch item of every affected voxel (grow-only)
     int64_t reserved = 0;                      // chunks the nodes / rows / depth arrays have room for
-    mnv::Buffer<unsigned long long> stats;     // MNV_STATS=1 diagnostics
+    mnv::AccelDiag diag;                       // buffers of the march's measurement instruments
     mnv::Mirrored<uint32_t> fault;             // [1] guided_fused2_kernel: spin-waits abandoned by the watchdog since creation (always counted, with or without
                                                // mnv_set_fused_diag); the pinned mirror is refreshed behind every fused launch -- mnv_accel_fused_faults
     uint32_t fault_reported = 0;               // faults already answered with MNV_E_FAULT
-    mnv::Buffer<uint32_t> line_bits;           // MNV_FOOTPRINT=<file> diagnostics: one bit per 128-byte line of grid2i / grid2, recs, nodes, rows, grid2_vox, grid_vox
-    uint32_t line_base[7] = {};                // first line of each of those regions in the bitmap; [6] = all lines
-    mnv::Buffer<unsigned long long> timeline;  // MNV_TIMELINE=<file> diagnostics: tile / wavefront time stamps of the last launch
-    size_t timeline_tiles = 0, timeline_waves = 0, timeline_tiles_per_frame = 0;
     // per-launch slots: [kNumQueues] ray-queue heads (64 B apart; a queue spans the frames of a batch) + [n_frames] camera blocks,
     // written on the launch stream by stage_launch_kernel; kSlots launches may be in flight
     mnv::Buffer<uint8_t> slots_dev;

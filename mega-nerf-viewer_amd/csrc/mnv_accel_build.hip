@@ -319,9 +319,6 @@ int mnv_accel_create_reserved(const mnv_tree_view *t, int64_t max_capacity, void
     for (int i = 0; i < kSlots; ++i)
         if ((rc = check_hip(a->slot_done[i].create(hipEventDisableTiming), "hipEventCreate(slot)"))) return rc;
 
-    if ((rc = check_hip(a->stats.alloc(32), "hipMalloc(stats)"))) return rc;
-    if ((rc = check_hip(hipMemsetAsync(a->stats.get(), 0, a->stats.bytes(), stream), "memset stats"))) return rc;
-
     if ((rc = accel_build(a.get(), t, stream))) return rc;
     *out = a.release();
     return MNV_OK;
@@ -339,50 +336,7 @@ int mnv_accel_rebuild(mnv_accel *a, const mnv_tree_view *t, void *hip_stream) {
 
 void mnv_accel_destroy(mnv_accel *a) {
     if (!a) return;
-    if (a->stats && knob_set(KNOB_STATS)) {
-        unsigned long long h[16];
-        if (hipMemcpy(h, a->stats.get(), sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
-            unsigned long long ph[8] = {};
-            if (hipMemcpy(ph, a->stats.get() + 16, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess && ph[4] > 0)
-                fprintf(stderr, "[mnv phases] share of the wavefronts' time (serialised by the stamps): lookup %.3f, step arithmetic + opacity %.3f, row wait %.3f, "
-                                "colour arithmetic %.3f, other (refill, ray set-up, flush, loop) %.3f; wave-steps %llu\n",
-                        (double)ph[0] / ph[4], (double)ph[1] / ph[4], (double)ph[2] / ph[4], (double)ph[3] / ph[4], 1.0 - (double)(ph[0] + ph[1] + ph[2] + ph[3]) / ph[4], ph[5]);
-            const char *names[] = {"outer_iter", "refill", "march_step", "node_load", "dense", "colour_pass"};
-            for (int i = 0; i < 6; ++i)
-                fprintf(stderr, "[mnv stats] %-13s wave-level %llu lane-level %llu (%.1f lanes)\n", names[i], h[2 * i], h[2 * i + 1],
-                        h[2 * i] ? (double)h[2 * i + 1] / (double)h[2 * i] : 0.0);
-        }
-    }
-    if (a->timeline && knob_str(KNOB_TIMELINE)) {
-        const size_t words = a->timeline_tiles * 4 + a->timeline_waves * 2;
-        std::vector<unsigned long long> h(words + 3);
-        h[0] = a->timeline_tiles;
-        h[1] = a->timeline_waves;
-        h[2] = a->timeline_tiles_per_frame;
-        if (hipMemcpy(h.data() + 3, a->timeline.get(), words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE *f = fopen(knob_str(KNOB_TIMELINE), "wb")) {
-                fwrite(h.data(), 8, h.size(), f);
-                fclose(f);
-            }
-        }
-    }
-    if (a->line_bits && knob_str(KNOB_FOOTPRINT)) {
-        // unique 128-byte lines per array, as JSON (tools/footprint.py reads it)
-        const size_t words = ((size_t)a->line_base[6] + 31) / 32;
-        std::vector<uint32_t> h(words);
-        if (hipMemcpy(h.data(), a->line_bits.get(), words * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-            static const char *names[6] = {"grid2", "records", "nodes", "rows", "grid2_vox", "grid_vox"};
-            unsigned long long lines[6] = {};
-            for (int r = 0; r < 6; ++r)
-                for (uint32_t l = a->line_base[r]; l < a->line_base[r + 1]; ++l) lines[r] += (h[l >> 5] >> (l & 31u)) & 1u;
-            if (FILE *f = fopen(knob_str(KNOB_FOOTPRINT), "w")) {
-                fprintf(f, "{");
-                for (int r = 0; r < 6; ++r) fprintf(f, "\"%s_lines\": %llu, ", names[r], lines[r]);
-                fprintf(f, "\"line_bytes\": 128}\n");
-                fclose(f);
-            }
-        }
-    }
+    report_diagnostics(a);
     delete a;
 }
 

@@ -133,71 +133,6 @@ static int grid_blocks(const mnv_accel *accel, const AccelLaunch &K, bool rays) 
     return n_blocks < 1 ? 1 : n_blocks;
 }
 
-// The diagnostics of a launch (knobs of the DESIGN.md section 5.2 table; read once): counters, ablations, the tile / wavefront timeline, the
-// footprint bitmap and the shadow copies.  The caller holds the launch lock; the buffers belong to the accel.
-static int attach_diagnostics(mnv_accel *mut, AccelLaunch &K, bool rays, bool fused, int n_blocks, hipStream_t stream) {
-    const mnv_accel *accel = mut;
-    static const int env_ablate = knob_int(KNOB_ABLATE, 0);
-    K.ablate = env_ablate;
-    static const bool env_stats = knob_set(KNOB_STATS);
-    static const char *env_timeline = knob_str(KNOB_TIMELINE);
-    static const char *env_footprint = knob_str(KNOB_FOOTPRINT);
-    K.stats = (env_stats || env_ablate || env_timeline || env_footprint) && !rays ? accel->stats.get() : nullptr;  // all four run on the diagnostics instantiation (camera frames only)
-    static const int env_stats_level = env_stats ? std::max(1, knob_int(KNOB_STATS, 1)) : 0;
-    K.count_stats = env_stats ? env_stats_level : 0;
-    if (env_footprint && !fused) {
-        // one bit per 128-byte line of every array the march loads from; the bits of all launches accumulate until mnv_accel_destroy counts them
-        if (!mut->line_bits) {
-            const uint64_t cells2 = accel->view.grid2_level > 0 ? (uint64_t)1 << (3 * accel->view.grid2_level) : 0, cells1 = (uint64_t)1 << (3 * accel->view.grid_level);
-            const uint64_t nvox = (uint64_t)accel->reserved * 8;
-            const uint64_t bytes[6] = {cells2 * 4, (uint64_t)accel->reserved * kRecWords * 4, nvox * 4, nvox * (uint64_t)accel->view.row_bytes, cells2 * 4, cells1 * 4};
-            uint64_t at = 0;
-            for (int i = 0; i < 6; ++i) {
-                mut->line_base[i] = (uint32_t)at;
-                at += (bytes[i] + 127) / 128 + 1;
-            }
-            mut->line_base[6] = (uint32_t)at;
-            const size_t words = (size_t)(at + 31) / 32;
-            if (mut->line_bits.alloc(words) != hipSuccess) return (int)hipErrorOutOfMemory;
-            (void)hipMemsetAsync(mut->line_bits.get(), 0, words * 4, stream);
-        }
-        K.line_bits = mut->line_bits.get();
-        for (int i = 0; i < 6; ++i) K.line_base[i] = mut->line_base[i];
-    }
-    static const int env_shadow = knob_int(KNOB_SHADOW, 0);
-    if (env_shadow & (16 | 32 | 64)) {
-        // shadow loads (test-hook build + a -DMNV_SHADOW_MASK variant of the march): copies of the arrays at other addresses, made once
-        const size_t nvox = (size_t)accel->reserved * 8;
-        auto shadow = [&](Buffer<uint8_t> &dst, const void *src, size_t bytes) -> int {
-            if (dst || !src) return 0;
-            hipError_t es = dst.alloc(bytes);
-            if (es == hipSuccess) es = hipMemcpyAsync(dst.get(), src, bytes, hipMemcpyDeviceToDevice, stream);
-            return (int)es;
-        };
-        int es = 0;
-        if (env_shadow & 16) es = shadow(mut->shadow_nodes, accel->nodes.get(), nvox * 4);
-        if (!es && (env_shadow & 32)) es = shadow(mut->shadow_rows, accel->rows.get(), nvox * (size_t)accel->view.row_bytes);
-        if (!es && (env_shadow & 64) && accel->recs) es = shadow(mut->shadow_nodes, accel->recs.get(), (size_t)accel->reserved * kRecWords * 4);  // (bits 16 and 64 are not combined)
-        if (es) return es;
-        K.shadow_nodes = reinterpret_cast<const uint32_t *>(accel->shadow_nodes.get());
-        K.shadow_rows = accel->shadow_rows.get();
-        K.shadow_recs = reinterpret_cast<const uint2 *>(accel->shadow_nodes.get());
-    }
-    if (env_timeline && K.stats) {
-        // (re)allocate the record buffer of this launch; mnv_accel_destroy writes the last launch's records to the file
-        const size_t tiles = (size_t)K.n_tiles * (size_t)K.n_frames, waves = (size_t)n_blocks * 4;
-        const size_t bytes = (tiles * 4 + waves * 2) * 8;
-        if (grow(mut->timeline, bytes / 8, bytes / 8, stream, false) != hipSuccess) return (int)hipErrorOutOfMemory;
-        (void)hipMemsetAsync(mut->timeline.get(), 0, bytes, stream);
-        mut->timeline_tiles = tiles;
-        mut->timeline_waves = waves;
-        mut->timeline_tiles_per_frame = K.n_tiles;
-        K.timeline = mut->timeline.get();
-        K.timeline_tiles = (uint32_t)tiles;
-    }
-    return 0;
-}
-
 // The launch of a validated request: P and cams are what render_accel derived from it (a ray list's `cams` only fills the launch slot).
 static int launch_accel(const AccelFrame &R, const FrameParams &P, const CamBlock *cams) {
     const mnv_accel *accel = R.accel;

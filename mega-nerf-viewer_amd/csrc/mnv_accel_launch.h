@@ -3,11 +3,14 @@
 //   mnv_accel_build.hip          build kernels, mnv_accel_create / _rebuild / _destroy
 //   mnv_accel_refresh_prune.hip  mnv_accel_refresh (patch after a refinement step), accel_apply_prune (the layout follows a prune)
 //   mnv_march_accel_kernel.h     march_accel_kernel (the tuned march)
+//   mnv_march_diag.h             its measurement instruments (MarchProbe: counters, footprint, timeline, phase clocks; shadow loads)
+//   mnv_accel_diag.hip           their host half: the diagnostics knobs and buffers of a launch, the reports at mnv_accel_destroy
 //   mnv_march_launch.h           its launcher and MODE choice, shared by the instantiation units mnv_accel_march[_brick|_rays].hip
 //   mnv_guided_fused*.h          the guided-sampling frame as one kernel, instantiated by mnv_accel_fused.hip
 //   mnv_accel_capi.hip           request validation (render_accel), launch planning (launch_accel), tile assembly, the C-ABI entry points
 #pragma once
 
+#include <cstddef>
 #include <type_traits>
 
 #include "mnv_accel.h"
@@ -58,6 +61,13 @@ __device__ __forceinline__ uint2 brick_record_entry(const uint32_t *__restrict__
     return make_uint2(child, codes);
 }
 
+// `prefix` with the child index of q (integer cell coordinates) at the level of bit sh appended (prefix 0: the octant alone)
+__device__ __forceinline__ uint32_t octant(const uint32_t (&q)[3], int sh, uint32_t prefix = 0u) {
+    uint32_t v = (prefix << 1) | __builtin_amdgcn_ubfe(q[0], (uint32_t)sh, 1u);
+    v = (v << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)sh, 1u);
+    return (v << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)sh, 1u);
+}
+
 // The levels below the LDS grid for the kernels that need a leaf's sigma in the step itself and read no colour row (the sample march of the
 // fused guided kernels): the second lookup grid -- with inline cell words when A.grid2i is there -- then a brick record, then node words.  A
 // non-empty leaf found through an inline word or a record fetches its node word (depth + sigma); an empty one costs nothing more.
@@ -80,9 +90,7 @@ __device__ __forceinline__ uint32_t descend_to_leaf(const AccelView &A, const ui
         src = 1;
         vox = gi;
         if (!(word & kLeafBit) && A.grid2i) {
-            uint32_t s1 = __builtin_amdgcn_ubfe(q[0], (uint32_t)(sh2 - 1), 1u);
-            s1 = (s1 << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)(sh2 - 1), 1u);
-            s1 = (s1 << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)(sh2 - 1), 1u);
+            const uint32_t s1 = octant(q, sh2 - 1);
             if (word & kInlineBit) {
                 vox = (((word & ((1u << kInlineMaskShift) - 1u)) + A.inline_base) << 3) | s1;
                 src = 2;
@@ -90,9 +98,7 @@ __device__ __forceinline__ uint32_t descend_to_leaf(const AccelView &A, const ui
                 return filled ? A.nodes[vox] : (kLeafBit | ((uint32_t)(L2 + 1) << 16));
             }
             if (A.recs != nullptr) {
-                uint32_t s2 = __builtin_amdgcn_ubfe(q[0], (uint32_t)(sh2 - 2), 1u);
-                s2 = (s2 << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)(sh2 - 2), 1u);
-                s2 = (s2 << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)(sh2 - 2), 1u);
+                const uint32_t s2 = octant(q, sh2 - 2);
                 const uint2 e = A.recs[(int64_t)word * 8 + s1];
                 const uint32_t code = __builtin_amdgcn_ubfe(e.y, s2 << 1, 2u);
                 if (code != 0u) {  // 1 / 2: an empty leaf of depth L2 + 1 / L2 + 2; 3: a leaf of depth L2 + 2 with sigma != 0
@@ -109,9 +115,7 @@ __device__ __forceinline__ uint32_t descend_to_leaf(const AccelView &A, const ui
     }
     while (!(word & kLeafBit)) {
         --sh;
-        uint32_t v = (word << 1) | __builtin_amdgcn_ubfe(q[0], (uint32_t)sh, 1u);
-        v = (v << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)sh, 1u);
-        v = (v << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)sh, 1u);
+        const uint32_t v = octant(q, sh, word);
         word = A.nodes[v];
         src = 2;
         vox = v;
@@ -136,12 +140,14 @@ struct AccelLaunch {
     uint32_t macro_w, macro_h;            // macro tile size in pixels
     uint32_t macros_x;                    // macro tiles per row of the rectangle
     uint32_t micro_x, micro_per_macro;    // 8x8 micro tiles per macro-tile row / per macro tile
-    unsigned long long *stats;            // MODE 1 only: 16 counters
-    int32_t count_stats;                  // MODE 1 only: 0 = ablation run without the counters' atomics
-    unsigned long long *timeline;         // MODE 1 only (MNV_TIMELINE): per tile {t_grab, t_done, wave, iterations}, then per wave {t_entry, t_exit} (100 MHz ticks)
-    uint32_t timeline_tiles;              // tile records (n_tiles * n_frames)
-    uint32_t *line_bits;                  // MODE 1 only (MNV_FOOTPRINT): bitmap of the 128-byte lines the loads of this launch touch
-    uint32_t line_base[6];                // regions: 0 grid2i / grid2, 1 brick records, 2 node words, 3 colour rows, 4 grid2_vox, 5 grid_vox
+    struct Diag {                         // MODE 1 only (mnv_march_diag.h; filled in by attach_diagnostics, mnv_accel_diag.hip)
+        unsigned long long *stats;        // 16 counters, then the phase sums; non-NULL selects the diagnostics instantiation
+        int32_t count_stats;              // 0 = ablation run without the counters' atomics
+        unsigned long long *timeline;     // MNV_TIMELINE: per tile {t_grab, t_done, wave, iterations}, then per wave {t_entry, t_exit} (100 MHz ticks)
+        uint32_t timeline_tiles;          // tile records (n_tiles * n_frames)
+        uint32_t *line_bits;              // MNV_FOOTPRINT: bitmap of the 128-byte lines the loads of this launch touch
+        uint32_t line_base[6];            // regions: 0 grid2i / grid2, 1 brick records, 2 node words, 3 colour rows, 4 grid2_vox, 5 grid_vox
+    } diag;
     // MODE 2 only: refinement trackers (rt_core.cuh:179-180,237-252,308-321), indexed like the pixels
     float *split_track, *sample_track;
     const int16_t *sample_counts;         // reference layout [capacity][8], may be NULL
@@ -169,6 +175,11 @@ struct AccelLaunch {
 struct AccelLaunchRays : AccelLaunch {
     const float *ray_origins, *ray_dirs;
 };
+// The block is a kernel argument: its offsets are immediates of every march and fused kernel's scalar loads
+static_assert(sizeof(AccelLaunch) == 704 && sizeof(AccelLaunchRays) == 720, "AccelLaunch changed its size");
+static_assert(offsetof(AccelLaunch, diag) == 496 && offsetof(AccelLaunch, split_track) == 560 && offsetof(AccelLaunch, fast_colour) == 600 &&
+                  offsetof(AccelLaunch, num_samples) == 648 && offsetof(AccelLaunch, range) == 692,
+              "AccelLaunch changed its layout");
 template <bool RAYS>
 using LaunchBlock = std::conditional_t<RAYS, AccelLaunchRays, AccelLaunch>;
 
@@ -310,6 +321,9 @@ void launch_build_grid2i(const uint32_t *nodes, const uint32_t *grid2, uint32_t 
 int min_chunk_of_depth(const int32_t *depth, int32_t capacity, int32_t d, int32_t *scratch, hipStream_t stream, uint32_t *out);
 void launch_build_grid(const uint32_t *nodes, uint32_t *grid, uint32_t *grid_vox, int32_t L, hipStream_t stream);
 void launch_build_grid2(const uint32_t *nodes, uint32_t *grid2, uint32_t *grid2_vox, int32_t L2, hipStream_t stream);
+// the diagnostics of a launch and their reports at mnv_accel_destroy (mnv_accel_diag.hip); the caller of the first holds the launch lock
+int attach_diagnostics(mnv_accel *a, AccelLaunch &K, bool rays, bool fused, int n_blocks, hipStream_t stream);
+void report_diagnostics(const mnv_accel *a);
 // march_accel_kernel for the row format `basis` (-1 RGBA, 1 / 4 / 9 / 16 / 25 SH) in the mode the launch block asks for
 // (mnv_accel_march.hip); kUnsupportedBasis or a hipError_t
 int launch_march(const AccelLaunch &K, int basis, bool colourless, int n_blocks, size_t lds_bytes, hipStream_t stream);

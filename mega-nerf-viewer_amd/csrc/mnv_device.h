@@ -166,6 +166,25 @@ __device__ __forceinline__ float exact_expf_select(float x, const uint64_t *tab)
     return res;
 }
 
+// w / (1 + exp(-tmp)): a dense sample's weight times the sigmoid of its channel sum (rt_core.cuh:254-291), as the march kernels'
+// colour blocks evaluate it.  FAST (mnv_accel_set_colour_math): colour-only arithmetic -- it feeds no branch (opacity, transmittance
+// and the step sequence stay exact), so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else.  Scaled so that
+// neither instruction leaves its range: v_rcp_f32 returns 0 for a subnormal result and exp2 overflows from 2^128, which lost every term
+// below 2^-126 (t < -87.3).  The reciprocal is taken of (1 + e) * 2^-32, beyond x = 96 of (2^-64 + exp2(x - 64)) * 2^-32 (x - 64 is
+// exact there), and the product scaled back.
+template <bool FAST>
+__device__ __forceinline__ float colour_sigmoid(float w, float tmp, const uint64_t *s_exp) {
+    if constexpr (FAST) {
+        const float x = tmp * -1.44269504088896341f;
+        const bool big = x > 96.f;
+        const float e = __builtin_amdgcn_exp2f(big ? x - 64.f : x);
+        const float den = __builtin_ldexpf((big ? 0x1p-64f : 1.f) + e, -32);
+        return __builtin_ldexpf(w * __builtin_amdgcn_rcpf(den), big ? -96 : -32);
+    } else {
+        return w / (1.f + exact_expf(-tmp, s_exp));
+    }
+}
+
 __device__ __forceinline__ float half_bits_to_float(uint16_t h) {
     _Float16 v;
     __builtin_memcpy(&v, &h, 2);

@@ -25,20 +25,11 @@
 // summation order (DESIGN.md "Why no MFMA").
 #pragma once
 
-#include "mnv_accel_launch.h"
+#include "mnv_march_diag.h"
 
 #pragma clang fp contract(off)
 
 namespace mnv {
-
-// Attribution of the L2 misses by array (tools/traffic_by_array.sh builds variants of the library with -DMNV_SHADOW_MASK=<bits>): every load
-// of the chosen array is repeated at the same index of a copy at other addresses -- results stay right, the miss counters grow by about
-// that array's share.  8 grid2 (its shadow is grid2_vox), 16 nodes, 32 rows, 64 brick records.  0 in every shipped build.
-#ifndef MNV_SHADOW_MASK
-#define MNV_SHADOW_MASK 0
-#endif
-constexpr int kShadow = MNV_SHADOW_MASK;
-
 
 // One step of the march on integer cell coordinates.  pos in [0, 1-1e-6] is scaled by 2^Lq
 // (Lq = deepest voxel depth of the tree, <= 23: the product is exact and < 2^24) and truncated;
@@ -67,10 +58,6 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
         if constexpr (MODE == 0 || MODE == 4) return false;
         else if constexpr (MODE == 5) return true;
         else return K.P.render_depth != 0;
-    };
-    auto ablate = [&](int bit) -> bool {
-        if constexpr (MODE == 1) return (K.ablate & bit) != 0;
-        else return false;
     };
     // per-lane ray constants that only the dense-sample / finish code needs live in LDS, not in VGPRs:
     // [k][thread] for k < NB: SH basis; then delta_scale and the output pixel index
@@ -263,61 +250,15 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
     uint32_t frame = 0;    // frame of the rays this wavefront holds (wave-uniform)
     uint32_t pix_base = 0;
 
-    // MODE 1 + MNV_TIMELINE: when each tile was grabbed and finished and by which wavefront (tools/timeline.py)
-    uint32_t tl_rec = ~0u, tl_iters = 0;
-    auto tl_close = [&](unsigned long long now) {
-        if constexpr (MODE == 1) {
-            if (K.timeline && tl_rec != ~0u && lane == 0) {
-                K.timeline[(size_t)tl_rec * 4 + 1] = now;
-                K.timeline[(size_t)tl_rec * 4 + 3] = tl_iters;
-            }
-        }
-    };
-    if constexpr (MODE == 1) {
-        if (K.timeline && lane == 0) K.timeline[(size_t)K.timeline_tiles * 4 + (size_t)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)) * 2] = wall_clock64();
-    }
-
-    // MODE 1 + MNV_FOOTPRINT: the 128-byte line a load touches, by array (region) and byte offset into it
-    auto touch = [&](int region, uint64_t byte_off) {
-        if constexpr (MODE == 1) {
-            if (K.line_bits) {
-                const uint32_t line = K.line_base[region] + (uint32_t)(byte_off >> 7);
-                atomicOr(&K.line_bits[line >> 5], 1u << (line & 31u));
-            }
-        }
-    };
-    auto stat = [&](int slot, bool pred) {
-        if constexpr (MODE == 1) {
-            if (!K.count_stats) return;
-            const uint64_t m = __ballot(pred);
-            if (m && lane == (int)__builtin_ctzll(m)) {
-                atomicAdd(&K.stats[slot], 1ull);
-                atomicAdd(&K.stats[slot + 1], (unsigned long long)__popcll(m));
-            }
-        }
-    };
-
-    // MNV_STATS=2 (diagnostics instantiation only): where the cycles of a wavefront's step go.  Every stamp waits for all outstanding
-    // memory operations first, so the phases do not overlap as they may in the product kernel: this is the DEPENDENT chain, what
-    // bounds a launch that drains.  stats[16..]: lookup (LDS grid -> grid2 -> node words), step arithmetic + opacity, row wait,
-    // colour arithmetic, the wavefront's whole time, wave-steps (tools/step_phases.py; LAB_NOTEBOOK.md round 3).
-    unsigned long long ph_lookup = 0, ph_step = 0, ph_row = 0, ph_colour = 0, ph_steps = 0, ph_mark = 0;
-    auto phase_clock = [&]() -> unsigned long long {
-        if constexpr (MODE == 1) {
-            if (K.count_stats == 2) {
-                __builtin_amdgcn_s_waitcnt(0);
-                return (unsigned long long)__builtin_readcyclecounter();
-            }
-        }
-        return 0ull;
-    };
-    const unsigned long long ph_begin = phase_clock();
+    // the measurement instruments (mnv_march_diag.h): every call below is empty outside the diagnostics instantiation (MODE 1)
+    MarchProbe<MODE, RAYS, BLOCK> probe(K, lane);
+    probe.wave_begin();
 
     for (;;) {
         const uint64_t idle = __ballot(!alive);
         const int n_idle = __popcll(idle);
-        stat(0, true);
-        if constexpr (MODE == 1) ++tl_iters;
+        probe.count(kCountOuterIter, true);
+        probe.iteration();
         // Tile-sized refills keep a wavefront's rays coherent (sweep in DESIGN.md).
         if (!drained && n_idle >= K.refill_min) {
             flush_finished();  // the idle lanes' pixels, before they take new rays
@@ -349,24 +290,13 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 }
             }
             const uint32_t base = begin + off, end = begin + span;
-            if constexpr (MODE == 1) {
-                if (K.timeline) {
-                    const unsigned long long now = wall_clock64();
-                    tl_close(now);
-                    tl_rec = f * K.n_tiles + (base >> 6);
-                    tl_iters = 0;
-                    if (lane == 0) {
-                        K.timeline[(size_t)tl_rec * 4 + 0] = now;
-                        K.timeline[(size_t)tl_rec * 4 + 2] = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-                    }
-                }
-            }
+            probe.tile_grabbed(f, base);
             if (!alive) {
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                 const uint32_t id = base + rank;
                 if (rank < grab && id < end) {
                     int bx, by;
-                    stat(2, true);
+                    probe.count(kCountRefill, true);
                     uint32_t pix;
                     if (ray_pixel(K, id, bx, by, pix)) {
                         pix += pix_base;
@@ -433,12 +363,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
             }
         }
         if (__ballot(alive) == 0) {
-            if constexpr (MODE == 1) {
-                if (K.timeline && tl_rec != ~0u) {  // the tile is done; what follows is queue polling
-                    tl_close(wall_clock64());
-                    tl_rec = ~0u;
-                }
-            }
+            probe.tile_done();
             if (drained) {
                 flush_finished();
                 break;
@@ -478,14 +403,14 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 }
             }
         };
-        ph_mark = phase_clock();
+        probe.step_begin();
         if (alive) {
             if (!(t < tmax)) {
                 // loop exit, rt_core.cuh:325-330: the pixel is finished in flush_finished()
                 fin = 1;
                 alive = false;
             } else {
-                stat(4, true);
+                probe.count(kCountMarchStep, true);
                 float pos[3];
                 uint32_t q[3];
                 pos[0] = cen0 + t * dir0;
@@ -513,13 +438,10 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         vox = (g << 2) | __builtin_amdgcn_ubfe(q[2], (uint32_t)sh2, 2u);
                         if constexpr (BRICK) word = A.grid2i[vox];
                         else word = A.grid2[vox];
-                        touch(0, (uint64_t)vox * 4);
+                        probe.touch(kLinesGrid2, (uint64_t)vox * 4);
                         src = 1;
                         sh = sh2;
-                        if constexpr ((kShadow & 8) != 0) {  // shadow load: the same cell of grid2_vox (same size, same order, other addresses)
-                            const uint32_t w2 = A.grid2_vox[vox];
-                            asm volatile("" ::"v"(w2));
-                        }
+                        if constexpr ((kShadow & 8) != 0) shadow_load(A.grid2_vox + vox);  // the same cell of grid2_vox (same size, same order, other addresses)
                         if constexpr (BRICK) {
                             // the two levels below the grid cell from the 64-byte record of the chunk it names: ONE 8-byte load -- entry s1 = {child
                             // chunk of voxel s1, 2-bit codes of its eight sub-cells}; empty leaves of either level end here
@@ -537,18 +459,15 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                                 }
                             }
                             if (!(word & kLeafBit) && A.recs != nullptr) {
-                                stat(6, true);
+                                probe.count(kCountNodeLoad, true);
                                 uint32_t s1 = __builtin_amdgcn_ubfe(q[0], (uint32_t)(sh2 - 1), 1u), s2 = __builtin_amdgcn_ubfe(q[0], (uint32_t)(sh2 - 2), 1u);
                                 s1 = (s1 << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)(sh2 - 1), 1u);
                                 s2 = (s2 << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)(sh2 - 2), 1u);
                                 s1 = (s1 << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)(sh2 - 1), 1u);
                                 s2 = (s2 << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)(sh2 - 2), 1u);
                                 const uint2 e = A.recs[(int64_t)word * 8 + s1];
-                                touch(1, ((uint64_t)word * 8 + s1) * 8);
-                                if constexpr ((kShadow & 64) != 0) {
-                                    const uint2 e2 = K.shadow_recs[(int64_t)word * 8 + s1];
-                                    asm volatile("" ::"v"(e2.x));
-                                }
+                                probe.touch(kLinesRecs, ((uint64_t)word * 8 + s1) * 8);
+                                if constexpr ((kShadow & 64) != 0) shadow_load(K.shadow_recs + ((int64_t)word * 8 + s1));
                                 const uint32_t code = __builtin_amdgcn_ubfe(e.y, s2 << 1, 2u);
                                 // 0: walk on from the chunk (word stays); 1 / 2: an empty leaf of depth L2 + 1 / L2 + 2; 3: a leaf of depth L2 + 2
                                 // with sigma != 0 -- its voxel through the entry's child word, its sigma with its colour row (cand)
@@ -561,18 +480,15 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         }
                     }
                     while (!(word & kLeafBit)) {
-                        stat(6, true);
+                        probe.count(kCountNodeLoad, true);
                         --sh;
                         uint32_t v = (word << 1) | __builtin_amdgcn_ubfe(q[0], (uint32_t)sh, 1u);
                         v = (v << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)sh, 1u);
                         vox = (v << 1) | __builtin_amdgcn_ubfe(q[2], (uint32_t)sh, 1u);
                         word = A.nodes[vox];
-                        touch(2, (uint64_t)vox * 4);
+                        probe.touch(kLinesNodes, (uint64_t)vox * 4);
                         src = 2;
-                        if constexpr ((kShadow & 16) != 0) {
-                            const uint32_t w2 = K.shadow_nodes[vox];
-                            asm volatile("" ::"v"(w2));
-                        }
+                        if constexpr ((kShadow & 16) != 0) shadow_load(K.shadow_nodes + vox);
                     }
                 }
                 if constexpr (BRICK && MODE == 3) {
@@ -583,13 +499,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         cand = false;
                     }
                 }
-                if constexpr (MODE == 1) {
-                    if (K.count_stats == 2) {
-                        const unsigned long long now = phase_clock();
-                        ph_lookup += now - ph_mark;
-                        ph_mark = now;
-                    }
-                }
+                probe.template phase_end<kPhaseLookup>();
                 const int depth = (int)((word >> 16) & 0x7fu);
                 const float sc = __uint_as_float((uint32_t)(127 + depth) << 23);        // 2^depth
                 const float inv_cube = __uint_as_float((uint32_t)(127 - depth) << 23);  // 2^-depth
@@ -605,7 +515,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 }
                 delta_t = tu * inv_cube + P.step_size;
                 const float sigma = half_bits_to_float((uint16_t)word);
-                const bool is_dense = sigma > P.sigma_thresh && !ablate(2);
+                const bool is_dense = sigma > P.sigma_thresh && !probe.ablate(2);
                 bool need_vox = is_dense;
                 if constexpr (MODE == 2 || MODE == 3) need_vox = is_dense || cand || K.visited != nullptr;  // (leaves without a dense sample: by their t, see sp_t / sa_t)
                 if (need_vox) {
@@ -613,9 +523,9 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                     if (src == 0) {
                         const uint32_t gc = ((((q[0] >> shg) << A.grid_level) + (q[1] >> shg)) << A.grid_level) + (q[2] >> shg);
                         vox = A.grid_vox[gc];
-                        touch(5, (uint64_t)gc * 4);
+                        probe.touch(kLinesGridVox, (uint64_t)gc * 4);
                     } else if (src == 1) {
-                        touch(4, (uint64_t)vox * 4);
+                        probe.touch(kLinesGrid2Vox, (uint64_t)vox * 4);
                         vox = A.grid2_vox[vox];
                     }
                 }
@@ -625,7 +535,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 }
                 if constexpr (BRICK && MODE != 3) {
                     // the opacity of every dense sample is worked out in the colour block (settle): a candidate's sigma arrives there with its row
-                    dense = (is_dense || cand) && !ablate(2);
+                    dense = (is_dense || cand) && !probe.ablate(2);
                     sigma_held = sigma;
                 } else if (is_dense) {
                     // opacity of a dense sample, rt_core.cuh:233-235
@@ -668,18 +578,11 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 }
             }
         }
-        if constexpr (MODE == 1) {
-            if (K.count_stats == 2) {
-                const unsigned long long now = phase_clock();
-                ph_step += now - ph_mark;
-                ph_mark = now;
-                ++ph_steps;
-            }
-        }
+        probe.template phase_end<kPhaseStep>();
         // ---- colour of the dense samples of this iteration (rt_core.cuh:254-291)
         const uint64_t dense_mask = __ballot(dense);
         if (dense_mask != 0) {
-            stat(8, dense);
+            probe.count(kCountDense, dense);
             // BRICK: whether a sample is dense at all (rt_core.cuh:233) and its opacity (:234-235) are settled here, in one place -- a
             // candidate (leaf with sigma != 0 out of a brick record) learns its sigma from its row, the half behind the three channel blocks
             [[maybe_unused]] auto settle = [&](uint32_t row_sigma_bits) {
@@ -693,7 +596,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
             };
             [[maybe_unused]] auto settle_from_memory = [&]() {  // frames that read no colour row: the sigma half alone
                 if constexpr (BRICK) {
-                    if (dense && cand) touch(3, (uint64_t)vox * A.row_bytes + A.sigma_off);
+                    if (dense && cand) probe.touch(kLinesRows, (uint64_t)vox * A.row_bytes + A.sigma_off);
                     if (dense) settle(cand ? (uint32_t)*reinterpret_cast<const uint16_t *>(A.rows + (int64_t)vox * A.row_bytes + A.sigma_off) : 0u);
                 }
             };
@@ -702,7 +605,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
             } else if (depth_mode()) {
                 settle_from_memory();
                 if (dense) o0 += weight * t;
-            } else if (ablate(1)) {
+            } else if (probe.ablate(1)) {
                 settle_from_memory();
             } else if constexpr (BASIS >= 16) {
                 // SH16 / SH25 (a row is 96 / 150 bytes: per-lane rows would need 24 / 39 registers and spill -- 6234 against 8687 Mrays/s for
@@ -719,11 +622,11 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 for (int base = 0; base < n_dense; base += 21) {
                     const int smp = base + my_s;
                     const bool task = my_s < 21 && smp < n_dense;
-                    stat(10, task);  // colour passes and their busy task lanes
+                    probe.count(kCountColourPass, task);  // colour passes and their busy task lanes
                     const int owner = task ? (int)map[smp] : lane;
                     const float w = lane_read(weight, owner);
                     uint32_t vx = lane_read(vox, owner);
-                    if (ablate(4)) vx &= 0xffffu;  // diagnostics: rows served from cache (wrong colours)
+                    if (probe.ablate(4)) vx &= 0xffffu;  // diagnostics: rows served from cache (wrong colours)
                     float b[NB];
 #pragma unroll
                     for (int k = 0; k < NB; ++k) b[k] = wave_ray[k * BLOCK + owner];  // the owner's SH basis, from LDS
@@ -734,21 +637,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         cw = *reinterpret_cast<const ChanWords<NW> *>(A.rows + (int64_t)vx * ROW_BYTES + my_c * CHAN_BYTES);
                         // binary16 coefficient times binary32 basis straight from the raw words (half_mul: no conversion instruction)
                         const float tmp = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return cw.w[j]; }, 0);
-                        // (both expressions are copied in mnv_probe.hip: colour_sigmoid_hw / colour_sigmoid_exact; change them together)
-                        if constexpr (MODE == 4) {
-                            // colour-only arithmetic: it feeds no branch (opacity, transmittance and the step sequence stay exact),
-                            // so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else.  Scaled so that
-                            // neither instruction leaves its range: v_rcp_f32 returns 0 for a subnormal result and exp2 overflows
-                            // from 2^128, which lost every term below 2^-126 (t < -87.3).  The reciprocal is taken of (1 + e) * 2^-32,
-                            // beyond x = 96 of (2^-64 + exp2(x - 64)) * 2^-32 (x - 64 is exact there), and the product scaled back
-                            const float x = tmp * -1.44269504088896341f;
-                            const bool big = x > 96.f;
-                            const float e = __builtin_amdgcn_exp2f(big ? x - 64.f : x);
-                            const float den = __builtin_ldexpf((big ? 0x1p-64f : 1.f) + e, -32);
-                            v = __builtin_ldexpf(w * __builtin_amdgcn_rcpf(den), big ? -96 : -32);
-                        } else {
-                            v = w / (1.f + exact_expf(-tmp, s_exp));
-                        }
+                        v = colour_sigmoid<MODE == 4>(w, tmp, s_exp);
                     }
                     const int rl = rank - base;
                     const bool mine = dense && rl >= 0 && rl < 21;
@@ -767,15 +656,12 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                 // one lane per (sample, channel), 21 samples per pass: more lanes busy per VALU instruction, but an iteration with 22+
                 // dense lanes waited for two or three passes' row misses one after the other -- LAB_NOTEBOOK.md.)
                 if (dense) {
-                    stat(10, true);
+                    probe.count(kCountColourPass, true);
                     uint32_t vx = vox;
-                    if (ablate(4)) vx &= 0xffffu;  // diagnostics: rows served from cache (wrong colours)
+                    if (probe.ablate(4)) vx &= 0xffffu;  // diagnostics: rows served from cache (wrong colours)
                     const uint8_t *row = A.rows + (int64_t)vx * ROW_BYTES;
-                    touch(3, (uint64_t)vx * ROW_BYTES);
-                    if constexpr ((kShadow & 32) != 0) {  // shadow load: one dword of the same row of the copy (one more line fill)
-                        const uint32_t w2 = *reinterpret_cast<const uint32_t *>(K.shadow_rows + (int64_t)vx * ROW_BYTES);
-                        asm volatile("" ::"v"(w2));
-                    }
+                    probe.touch(kLinesRows, (uint64_t)vx * ROW_BYTES);
+                    if constexpr ((kShadow & 32) != 0) shadow_load(reinterpret_cast<const uint32_t *>(K.shadow_rows + (int64_t)vx * ROW_BYTES));  // one dword of the copy's row
                     // the whole row -- 3 * BASIS coefficient halfs, then sigma -- with 16-byte loads (SH9: four; until round 5 three channel
                     // blocks of 20 bytes each took six load instructions)
                     constexpr int RW = ROW_BYTES / 4;
@@ -794,13 +680,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                         rw[0] = x.x;
                         rw[1] = x.y;
                     }
-                    if constexpr (MODE == 1) {
-                        if (K.count_stats == 2) {
-                            const unsigned long long now = phase_clock();   // the rows have arrived
-                            ph_row += now - ph_mark;
-                            ph_mark = now;
-                        }
-                    }
+                    probe.template phase_end<kPhaseRow>();  // the rows have arrived
                     auto half_at = [&](int hidx) -> uint32_t { return (hidx & 1) ? (rw[hidx >> 1] >> 16) : (rw[hidx >> 1] & 0xffffu); };
                     if constexpr (BRICK) settle(half_at(3 * BASIS));
                     float b[NB];
@@ -809,21 +689,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                     auto chan = [&](int c) -> float {
                         // binary16 coefficient times binary32 basis straight from the raw row words (half_mul: no conversion instruction)
                         const float tmp = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, c * BASIS);
-                        // (both expressions are copied in mnv_probe.hip: colour_sigmoid_hw / colour_sigmoid_exact; change them together)
-                        if constexpr (MODE == 4) {
-                            // colour-only arithmetic: it feeds no branch (opacity, transmittance and the step sequence stay exact),
-                            // so hardware exp2 / rcp (about 1 ulp each) move a colour by ~1e-7 and nothing else.  Scaled so that
-                            // neither instruction leaves its range: v_rcp_f32 returns 0 for a subnormal result and exp2 overflows
-                            // from 2^128, which lost every term below 2^-126 (t < -87.3).  The reciprocal is taken of (1 + e) * 2^-32,
-                            // beyond x = 96 of (2^-64 + exp2(x - 64)) * 2^-32 (x - 64 is exact there), and the product scaled back
-                            const float x = tmp * -1.44269504088896341f;
-                            const bool big = x > 96.f;
-                            const float e = __builtin_amdgcn_exp2f(big ? x - 64.f : x);
-                            const float den = __builtin_ldexpf((big ? 0x1p-64f : 1.f) + e, -32);
-                            return __builtin_ldexpf(weight * __builtin_amdgcn_rcpf(den), big ? -96 : -32);
-                        } else {
-                            return weight / (1.f + exact_expf(-tmp, s_exp));
-                        }
+                        return colour_sigmoid<MODE == 4>(weight, tmp, s_exp);
                     };
                     if (dense) {  // (a candidate may have turned out not to be dense)
                         o0 += chan(0);
@@ -856,23 +722,9 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
             if (dense_mask == 0) track_update();
         }
         t += delta_t;  // 0 for lanes that did not step
-        if constexpr (MODE == 1) {
-            if (K.count_stats == 2) ph_colour += phase_clock() - ph_mark;  // (iterations without a dense lane: the ballot and the transmittance update)
-        }
+        probe.template phase_end<kPhaseColour>();  // (iterations without a dense lane: the ballot and the transmittance update)
     }
-    if constexpr (MODE == 1) {
-        if (K.count_stats == 2 && lane == 0) {
-            atomicAdd(&K.stats[16], ph_lookup);
-            atomicAdd(&K.stats[17], ph_step);
-            atomicAdd(&K.stats[18], ph_row);
-            atomicAdd(&K.stats[19], ph_colour);
-            atomicAdd(&K.stats[20], phase_clock() - ph_begin);
-            atomicAdd(&K.stats[21], ph_steps);
-        }
-    }
-    if constexpr (MODE == 1) {
-        if (K.timeline && lane == 0) K.timeline[(size_t)K.timeline_tiles * 4 + (size_t)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)) * 2 + 1] = wall_clock64();
-    }
+    probe.wave_end();
 }
 
 }  // namespace mnv

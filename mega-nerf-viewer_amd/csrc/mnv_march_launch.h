@@ -28,7 +28,7 @@ template <int BASIS, bool BRICK, bool RAYS>
 static int launch_march_mode(const LaunchBlock<RAYS> &K, int n_blocks, size_t lds_bytes, hipStream_t stream) {
     if constexpr (!RAYS) {
         if constexpr (BASIS == 9) {
-            if (K.stats) return launch_march_kernel<BASIS, 1, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
+            if (K.diag.stats) return launch_march_kernel<BASIS, 1, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
             if (K.samples) return launch_march_kernel<BASIS, 3, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);
         }
         if (K.split_track || K.sample_track || K.visited) return launch_march_kernel<BASIS, 2, BRICK, RAYS>(K, n_blocks, lds_bytes, stream);

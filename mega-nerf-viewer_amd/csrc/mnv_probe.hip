@@ -1,8 +1,7 @@
 // mnv_probe.hip -- element-wise probes of the device functions of mnv_device.h, for tests/test_primitives_gpu.py.  Linked into
 // testhooks/libmnv.so only: the shipped library exports no mnv_hook_ symbol (tests/test_capi_symbols.py).
 //
-// Every kernel calls the very function the march kernels call -- nothing is restated here but the two colour-sigmoid expressions, see
-// below -- under the same compiler flags (the Makefile's csrc/%.o rule).  One thread per element, bounds-checked, 256-thread blocks; the
+// Every kernel calls the very function the march kernels call -- nothing is restated here -- under the same compiler flags (the Makefile's csrc/%.o rule).  One thread per element, bounds-checked, 256-thread blocks; the
 // expf table sits in LDS through load_exp_table as in the real kernels.  All array arguments are device pointers, `frame` / `cam` of
 // mnv_hook_probe_setup_ray are host pointers to the argument blocks that the kernels take by value.  Every entry point returns MNV_OK or
 // an MNV_E_* / HIP code and is asynchronous on `hip_stream`.
@@ -26,19 +25,6 @@ unsigned grid_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads);
 
 __device__ __forceinline__ float expf_variant(float x, int which, const uint64_t *tab) {
     return which ? mnv::exact_expf_select(x, tab) : mnv::exact_expf(x, tab);
-}
-
-// The two colour-sigmoid expressions of mnv_march_accel_kernel.h (the colour block of the wave-shared pass and `chan` of the per-lane
-// pass), COPIED: moving them into functions of mnv_device.h changed the march kernels' instruction selection (where the negation of the
-// argument is folded), so the kernel header keeps them inline and names this copy.  Change them together.
-__device__ __forceinline__ float colour_sigmoid_exact(float w, float tmp, const uint64_t *s_exp) { return w / (1.f + mnv::exact_expf(-tmp, s_exp)); }
-
-__device__ __forceinline__ float colour_sigmoid_hw(float w, float tmp) {
-    const float x = tmp * -1.44269504088896341f;
-    const bool big = x > 96.f;
-    const float e = __builtin_amdgcn_exp2f(big ? x - 64.f : x);
-    const float den = __builtin_ldexpf((big ? 0x1p-64f : 1.f) + e, -32);
-    return __builtin_ldexpf(w * __builtin_amdgcn_rcpf(den), big ? -96 : -32);
 }
 
 // result bits with every NaN replaced by the one quiet NaN (the digests and the variant comparison do not see NaN payloads)
@@ -113,7 +99,7 @@ __global__ void __launch_bounds__(kThreads) probe_sigmoid_kernel(const float *__
     mnv::load_exp_table(s_exp);
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    out[i] = mode ? colour_sigmoid_hw(w[i], t[i]) : colour_sigmoid_exact(w[i], t[i], s_exp);
+    out[i] = mode ? mnv::colour_sigmoid<true>(w[i], t[i], s_exp) : mnv::colour_sigmoid<false>(w[i], t[i], s_exp);
 }
 
 // dirs [n][3], coefs [n][3 * B] binary16 bits (channel c at c * B, as a voxel row) -> basis_out [n][B], channel_out [n][3]
@@ -252,7 +238,7 @@ int mnv_hook_probe_half(const uint16_t *bits, int64_t n, float *out, void *hip_s
     return check_hip(hipGetLastError(), "probe_half_kernel");
 }
 
-// mode 0: colour_sigmoid_exact, 1: colour_sigmoid_hw
+// mode 0: colour_sigmoid<false> (exact), 1: colour_sigmoid<true> (hardware exp2 / rcp)
 int mnv_hook_probe_sigmoid(const float *w, const float *t, int64_t n, int mode, float *out, void *hip_stream) {
     if (n < 0 || (n > 0 && (!w || !t || !out)) || mode < 0 || mode > 1) return set_error(MNV_E_INVALID, "mnv_hook_probe_sigmoid: bad arguments");
     if (n == 0) return MNV_OK;

@@ -32,7 +32,7 @@ SHELL = {8: dict(radius=0.3, sigma_lo=5.0, sigma_hi=60.0), 10: dict(radius=0.08,
          12: dict(radius=0.03, sigma_lo=200.0, sigma_hi=1600.0)}
 RANDOM_POSES = [((-2.5, 1.4, 1.8), (-0.74, 0.4, 0.54)), ((2.2, -1.9, 1.1), (0.7, -0.6, 0.39)), ((1.3, 2.4, -1.5), (0.42, 0.77, -0.48))]
 
-# Every instantiation of march_accel_kernel outside the diagnostics MODE 1, read off the three units that instantiate it
+# Every instantiation of march_accel_kernel outside the diagnostics MODE 1 (tests/test_march_diag_gpu.py runs that one), read off the three units that instantiate it
 # (csrc/mnv_accel_march.hip, mnv_accel_march_brick.hip, mnv_accel_march_rays.hip times the MODEs of csrc/mnv_march_launch.h):
 # (BASIS, MODE, BRICK, RAYS).  MODE 3 (samples) and 5 (depth image) exist for BASIS 9 only, MODE 4 (fast colour) for SH rows of frames only.
 VARIANTS = sorted(
