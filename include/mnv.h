@@ -1168,6 +1168,82 @@ int mnv_metrics_finish(const mnv_metric_sums *host_copy, mnv_frame_metric_values
 int mnv_pnm_read(const char *path, int32_t expect_width, int32_t expect_height, uint8_t *data /* host */, int64_t cap_bytes, int32_t *width,
                  int32_t *height, int32_t *channels);
 
+/* ------------------------------------------------ fitting a tree's rows to target rays: the march's gradient and a row update, on the device
+ * The frame metrics above measure the gap between a tree's frames and target images; these three entry points close it.  The octree family
+ * (PlenOctrees, svox) is differentiable in its row data: mnv_rays_grad marches a ray list and accumulates d(loss)/d(row) for every leaf row the
+ * rays sample, mnv_rows_sgd_step applies one gradient step to a float32 master copy of the rows and writes the binary16 rows back.  The tree's
+ * structure (child) never changes.  The reference has no counterpart.
+ *
+ * mnv_rays_grad works on the tree VIEW's own device arrays (child, binary16 data): the rows change between iterations, so it takes no accel.
+ *   origins / dirs   device float [height][width][3], world space, as mnv_render_rays_accel takes them (a flat list is height == 1; 8 x 8 ray
+ *                    tiles per wavefront, 64 x 1 for height == 1)
+ *   target           device float [height][width][4]: the ray's target colour; alpha == 0 EXCLUDES the ray (weight 0), any other alpha
+ *                    (NaN too) includes it (weight 1)
+ *   tmax             device float [height][width] or NULL (1e9f), the ray limit as in mnv_frame_inputs
+ *   rgba_out         device float [height][width][4] or NULL: written for every ray, excluded rays too
+ *   acc              device int64 [capacity * 8][data_dim], 8-byte aligned: the kernel ADDS into it (the caller zeroes it; mnv_rows_sgd_step
+ *                    clears what it consumed)
+ *   sums             device mnv_fit_sums, 8-byte aligned: the kernel ADDS into it (the caller zeroes it)
+ * Forward contract: mnv_render_rays_accel's, exactly.  rgba_out equals that call's float output bit for bit -- degenerate rays and misses
+ * included -- for options without render_depth and without an image under the volume.
+ * Names.  The ray's dense samples s = 0 .. n-1 are its march steps with sigma > sigma_thresh, in march order.  Sample s has its leaf voxel v_s
+ * (chunk * 8 + child index), d_s = delta_t * delta_scale, att_s = expf(-d_s sigma) as the forward computes it, T_s the light before the sample,
+ * w_s = T_s * (1.f - att_s), T_{s+1} = T_s * att_s, and the colour c_sk of channel k: for SH rows 1.f / (1.f + expf(-tmp_k)), tmp_k the
+ * channel sum of the forward; for RGBA rows the row's value.  S_k are the forward's running sums BEFORE the early-stop rescale, T_end the
+ * light at the end, stopped is true when T_{s+1} < stop_thresh ended the ray, scale = stopped ? 1.f / (1.f - T_end) : 1.f (the forward's own
+ * factor), C_k the composited pixel (rgba_out), B_k = stopped ? C_k : background_brightness.
+ * Backward contract (binary32, one operation at a time in the stated order, no contraction, then ONE rounding to fixed point):
+ *   g_k = C_k - target_k                                         (the loss is 1/2 sum_k g_k^2 over the included rays)
+ *   se = (g_0*g_0 + g_1*g_1) + g_2*g_2                            -> sums.se_q32
+ *   gs_k = g_k * scale;   bt_k = B_k * T_end                      (once per ray)
+ *   the same steps are marched again with the prefix P_k accumulated exactly as the forward accumulates S_k; at sample s, after adding it:
+ *     Q_k  = S_k - P_k
+ *     gc_k = gs_k * w_s
+ *     RGBA rows: column k gets gc_k.
+ *     SH rows:   gt_k = gc_k * (c_sk * (1.f - c_sk));  column k * basis_dim + j gets gt_k * basis_j for basis_min <= j <= basis_max -- basis_j
+ *                the SH basis of the view direction after rot_dirs, as the forward multiplies it; masked coefficients get no term
+ *     e_k  = (T_{s+1} * c_sk - Q_k) - bt_k
+ *     column data_dim - 1 (sigma) gets (d_s * scale) * ((g_0*e_0 + g_1*e_1) + g_2*e_2)
+ *   That is the derivative of the pixel with the sample set held fixed, the early-stop normalisation S_k / (1 - T_end) included (DESIGN.md
+ *   5.16 derives it).  Every term x is added to acc[v_s][column] as the integer q32(x) = llrint((double)sat(x) * 2^32), sat(x) = x clamped to
+ *   [-32, 32] (a NaN term: 0); se goes to sums.se_q32 the same way.  From that rounding on every addition is an integer addition, so the
+ *   words do not depend on lane mapping, launch shape, ray order or atomic order, and a numpy restatement reproduces them exactly
+ *   (tests/fit_ref.py).
+ *   A ray with a non-finite C_k or g_k, or whose descent leaves the tree (below), contributes NOTHING and is counted in n_skipped.
+ * Sums (the included rays that were not skipped): n_rays; n_stopped (early-stopped ones); n_samples (their dense samples); se_q32; and
+ *   n_skipped.
+ * Headroom.  One term is at most 2^5 * 2^32 = 2^37 in magnitude (terms of SH rows against targets in [0, 1] stay below 8; the clamp is the
+ * guard for everything else), so a word of acc cannot wrap before it has received 2^25 terms (2^25 * 2^37 = 2^62).  A ray adds to a word
+ * once per dense step it takes in that voxel (one, except where rounding keeps a step inside its leaf).  One call takes at most 2^22 rays
+ * (two 1080p frames: more is MNV_E_INVALID); clear acc -- mnv_rows_sgd_step does -- before the ray total since the last clear passes 2^24.
+ * se_q32: 2^24 * 2^37 < 2^62.
+ * The descent is bounded and link-checked as mnv_accel_sample_points' is: at most 23 levels, a link that leaves [1, capacity) is not followed;
+ * a ray that meets either is skipped.  (A tree deeper than 23 levels cannot be told from the host without a launch: its rays are skipped.)
+ * MNV_E_UNSUPPORTED, before any launch: options.render_depth, N != 2, rows other than RGBA and SH 1 / 4 / 9 / 16 / 25 (what the ray march
+ *   offers).  (There is no image under the volume here: the entry point takes no rgba8_init.)
+ * MNV_E_INVALID, before any launch: a null tree / array / options / acc / sums, width or height < 1, width * height > 2^22, capacity < 1,
+ *   a data_dim too small for the row format, acc / sums not 8-byte aligned, rgba_out / target not 16-byte aligned, and step_size not finite
+ *   or <= 0 -- a march that cannot advance never reaches the device.
+ *
+ * mnv_rows_master_init: master[i] = (float)data[i] for n binary16 values, exact; non-finite bit patterns (inf, NaN) read as +0.
+ * mnv_rows_sgd_step (elementwise): for every row r < n_rows with a non-zero word in acc[r][0 .. data_dim), per column c:
+ *     g = (float)((double)acc[r][c] * 2^-32);  lr = c == data_dim - 1 ? lr_sigma : lr_colour;  m = master[r][c] - lr * g  (the product is
+ *     rounded before the difference);  the sigma column: m = m < 0 ? 0 : m;  master[r][c] = m;
+ *     data[r][c] = binary16(m), round to nearest even, saturating at +-65504 (no infinity is written; a NaN m writes +0)
+ *   and acc[r][.] is cleared.  Rows whose words are all zero keep master and bytes untouched.
+ *   MNV_E_INVALID: null arrays, n_rows < 0, data_dim < 1, a learning rate that is not finite.
+ */
+typedef struct mnv_fit_sums {
+    int64_t n_rays, n_stopped, n_samples, n_skipped, se_q32, reserved[3];
+} mnv_fit_sums;
+int mnv_rays_grad(const mnv_tree_view *device_tree, const float *origins, const float *dirs /* device [height][width][3] */,
+                  const float *target /* device [height][width][4] */, const float *tmax /* device [height][width] or NULL */, int32_t width,
+                  int32_t height, const mnv_render_options *opt, float *rgba_out /* device or NULL */, int64_t *acc /* device */,
+                  mnv_fit_sums *sums /* device */, void *hip_stream);
+int mnv_rows_master_init(const uint16_t *data /* device [n] */, int64_t n, float *master_out /* device [n] */, void *hip_stream);
+int mnv_rows_sgd_step(uint16_t *data, float *master, int64_t *acc /* device [n_rows][data_dim] each */, int64_t n_rows, int32_t data_dim,
+                      float lr_colour, float lr_sigma, void *hip_stream);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -1204,6 +1280,26 @@ int mnv_n3tree_make_lod(mnv_n3tree *t, int32_t max_depth, mnv_n3tree **out);
  * not on the device; otherwise the codes of the three calls. */
 int mnv_n3tree_make_view_lod(mnv_n3tree *t, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth,
                              int64_t *kept_at_depth, mnv_n3tree **out);
+/* N3Tree::fit: optimise the rows of a tree that is on the device against target frames, full batch.  Per iteration: for each camera,
+ * mnv_generate_rays(MNV_PROJ_PINHOLE, the whole image) then mnv_rays_grad against targets[i] (a DEVICE float [height][width][4] frame of that
+ * camera's size; alpha 0 excludes a pixel), all into one accumulator; then one mnv_rows_sgd_step.  The float32 master copy is made at the
+ * start (mnv_rows_master_init).  At the end the packed accel is rebuilt (where the tree has one) and the host arrays are refreshed, so
+ * mnv_n3tree_save_npz and every march see the result.  se_q32_out: HOST int64 [iterations], the se_q32 of each iteration's rays BEFORE
+ * its step (exact integers; or NULL).  Runs on the null stream and waits for it.  MNV_E_INVALID: a tree that is not on the device, no camera,
+ * a null target, iterations < 0, learning rates that are not finite or negative, a camera of more than 2^22 pixels, cameras whose pixels together pass 2^24 (the headroom
+ * between two clears); otherwise the codes of the calls. */
+typedef struct mnv_fit_params {
+    int32_t iterations;
+    float lr_colour, lr_sigma;
+    int32_t reserved;
+} mnv_fit_params;
+int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets /* HOST array of n_cams device pointers */,
+                   const mnv_render_options *opt, const mnv_fit_params *params, int64_t *se_q32_out);
+/* N3Tree::fit_to: the targets are the teacher's frames -- mnv_render_voxels_accel of `teacher` (on the device, with its accel) at each camera,
+ * float, as they are: a pixel where the teacher accumulated no opacity (alpha 0) is excluded -- then mnv_n3tree_fit.  A level of detail
+ * (mnv_n3tree_make_lod of the teacher) fitted this way is the use. */
+int mnv_n3tree_fit_to_tree(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt,
+                           const mnv_fit_params *params, int64_t *se_q32_out);
 /* DataFormat::parse / to_string (src/data_format.cpp:5-41) */
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim);
 int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size_t buflen);
@@ -1334,6 +1430,12 @@ int mnv_renderer_set_lod(mnv_renderer *r, int32_t max_depth);
  * options.use_splitting, options.use_guided_sampling, several ranks, or mnv_renderer_set_lod with a depth above 0.  MNV_E_INVALID here:
  * n_views outside [0, 4096], views NULL with n_views > 0, and what mnv_tree_select_cut refuses in views, pixels, min_depth, max_depth. */
 int mnv_renderer_set_view_lod(mnv_renderer *r, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth);
+/* VolumeRenderer::set_lod_fit (n_cams == 0 or params->iterations == 0, the default, = off: every frame is what it is without this call, byte
+ * for byte).  Otherwise every tree mnv_renderer_set_lod / mnv_renderer_set_view_lod builds from now on is fitted, right after it is built,
+ * to the frames of the tree that was set at the listed cameras (mnv_n3tree_fit_to_tree with `params`); trees built before are dropped.  The
+ * cameras are copied.  Refused wherever a level of detail is (mnv_renderer_render says so).  MNV_E_INVALID here: a null argument, a negative
+ * count, negative iterations, learning rates that are not finite or negative; the fit's own refusals surface at the frame that builds the tree. */
+int mnv_renderer_set_lod_fit(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, const mnv_fit_params *params);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

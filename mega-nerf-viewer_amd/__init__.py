@@ -147,6 +147,14 @@ class RendererStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class FitParams(C.Structure):
+    """mnv_fit_params"""
+    _fields_ = [("iterations", C.c_int32), ("lr_colour", C.c_float), ("lr_sigma", C.c_float), ("reserved", C.c_int32)]
+
+
+FIT_SUMS = ("n_rays", "n_stopped", "n_samples", "n_skipped", "se_q32")   # the first five int64 words of mnv_fit_sums (8 in all)
+
+
 class MetricSums(C.Structure):
     """mnv_metric_sums: the five int64 words mnv_frame_metrics leaves in device memory."""
     _fields_ = [("n_px", C.c_int64), ("se_q32", C.c_int64), ("n_win", C.c_int64), ("ssim_q32", C.c_int64), ("reserved", C.c_int64)]
@@ -414,6 +422,13 @@ _SIGNATURES = {
     "mnv_tree_cut": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mnv_n3tree_make_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
     "mnv_renderer_set_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32]),
+    "mnv_renderer_set_lod_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FitParams)]),
+    "mnv_rays_grad": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RenderOptions), C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_rows_master_init": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mnv_rows_sgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    "mnv_n3tree_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(FitParams), C.c_void_p]),
+    "mnv_n3tree_fit_to_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RenderOptions), C.POINTER(FitParams), C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -740,6 +755,36 @@ class N3Tree:
                                               kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
         out = N3Tree(h.value)
         return (out, kept) if return_counts else out
+
+    def fit(self, cams, targets, opt: RenderOptions, iterations: int, lr_colour: float, lr_sigma: float) -> np.ndarray:
+        """N3Tree::fit: `iterations` full-batch gradient steps on this tree's rows (on the device) against `targets`, one float32 device
+        tensor [height, width, 4] per camera of `cams` (alpha 0 excludes a pixel).  The accel is rebuilt and the host arrays are refreshed.
+        -> int64 [iterations]: se_q32 of each iteration's rays before its step."""
+        import torch
+
+        n = len(cams)
+        if n < 1 or len(targets) != n:
+            raise MnvError(MNV_E_INVALID, "one target frame per camera, at least one camera")
+        for c, t in zip(cams, targets):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != c.width * c.height * 4:
+                raise MnvError(MNV_E_INVALID, "a target must be a contiguous float32 device tensor [height, width, 4] of its camera's size")
+        arr = (CameraStruct * n)(*[c.c for c in cams])
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in targets])
+        se = np.zeros(max(int(iterations), 0), np.int64)
+        p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
+        _check(lib().mnv_n3tree_fit(self._h, arr, n, ptrs, C.byref(opt), C.byref(p), se.ctypes.data))
+        return se
+
+    def fit_to(self, teacher: "N3Tree", cams, opt: RenderOptions, iterations: int, lr_colour: float, lr_sigma: float) -> np.ndarray:
+        """N3Tree::fit_to: fit against the frames the accel march renders of `teacher` (on the device) at `cams`; as fit otherwise."""
+        n = len(cams)
+        if n < 1:
+            raise MnvError(MNV_E_INVALID, "at least one camera")
+        arr = (CameraStruct * n)(*[c.c for c in cams])
+        se = np.zeros(max(int(iterations), 0), np.int64)
+        p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
+        _check(lib().mnv_n3tree_fit_to_tree(self._h, teacher._h, arr, n, C.byref(opt), C.byref(p), se.ctypes.data))
+        return se
 
     def gen_wireframe(self, max_depth: int = 100000) -> np.ndarray:
         """N3Tree::gen_wireframe (n3tree.cpp:249-329) on the host arrays: float32 [n_vertices, 9] (position, colour, normal), 24 vertices
@@ -1316,6 +1361,14 @@ class Renderer:
         _check(lib().mnv_renderer_set_view_lod(self._h, table.ctypes.data if table.shape[0] else None, int(table.shape[0]), float(pixels),
                                                int(min_depth), int(max_depth)))
 
+    def set_lod_fit(self, cams=(), iterations: int = 0, lr_colour: float = 0.0, lr_sigma: float = 0.0) -> None:
+        """VolumeRenderer::set_lod_fit: every tree set_lod / set_view_lod builds from now on is fitted to the full tree at `cams`
+        (N3Tree.fit_to) right after it is built; no camera or no iteration (the default) switches it off."""
+        cams = list(cams)
+        arr = (CameraStruct * max(len(cams), 1))(*[c.c for c in cams])
+        p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
+        _check(lib().mnv_renderer_set_lod_fit(self._h, arr if cams else None, len(cams), C.byref(p)))
+
     def set_target(self, target=None, flags: int = 0) -> None:
         """VolumeRenderer::set_target: score every frame against `target`, a contiguous uint8 device tensor [height, width, 4], on the
         device (METRIC_QUANTISED / METRIC_MASK_ALPHA / METRIC_SSIM); metrics(slot) collects a frame's score.  The tensor may change per
@@ -1847,6 +1900,61 @@ def render_rays_accel(accel: int, origins, dirs, opt: RenderOptions, rgba=None, 
     with _timed(stream):
         _check(lib().mnv_render_rays_accel(C.c_void_p(accel), origins.data_ptr(), dirs.data_ptr(), width, height, C.byref(opt),
                                            C.byref(inputs) if inputs is not None else None, _ptr(rgba), _ptr(rgba8), C.c_void_p(stream)))
+
+
+def _check_dev(name: str, t, dtype, numel: int):
+    if t is None or not hasattr(t, "is_cuda") or not t.is_cuda or not t.is_contiguous() or t.dtype != dtype or t.numel() < numel:
+        raise MnvError(MNV_E_INVALID, f"{name} must be a contiguous {dtype} device tensor with at least {numel} elements")
+
+
+def rays_grad(view: TreeView, origins, dirs, target, opt: RenderOptions, acc, sums, rgba=None, tmax=None, stream: int = 0) -> None:
+    """mnv_rays_grad (asynchronous on `stream`): marches the rays (as render_rays_accel takes them) through the DEVICE tree view and ADDS the
+    gradient of 1/2 |pixel - target|^2 into acc (int64 [capacity * 8, data_dim], fixed point 2^-32) and the ray counts and squared error into
+    sums (int64 [8], FIT_SUMS names the first five); both are the caller's to zero.  target: float32 [.., 4], alpha 0 excludes a ray."""
+    import torch
+
+    _check_rays("origins", origins)
+    _check_rays("dirs", dirs, tuple(origins.shape))
+    height, width = (1, int(origins.shape[0])) if origins.dim() == 2 else (int(origins.shape[0]), int(origins.shape[1]))
+    n = width * height
+    _check_dev("target", target, torch.float32, n * 4)
+    _check_dev("acc", acc, torch.int64, view.capacity * 8 * view.data_dim)
+    _check_dev("sums", sums, torch.int64, 8)
+    _check_out("rgba", rgba, n, "f32")
+    if tmax is not None:
+        _check_dev("tmax", tmax, torch.float32, n)
+    with _timed(stream):
+        _check(lib().mnv_rays_grad(C.byref(view), origins.data_ptr(), dirs.data_ptr(), target.data_ptr(), _ptr(tmax), width, height, C.byref(opt), _ptr(rgba),
+                                   acc.data_ptr(), sums.data_ptr(), C.c_void_p(stream)))
+
+
+def rows_master_init(data, master=None, stream: int = 0):
+    """mnv_rows_master_init: the float32 master copy of binary16 rows (a uint16 / float16 device tensor); non-finite bit patterns read +0."""
+    import torch
+
+    if not data.is_cuda or not data.is_contiguous() or data.element_size() != 2:
+        raise MnvError(MNV_E_INVALID, "data must be a contiguous 16-bit device tensor")
+    if master is None:
+        master = torch.empty(tuple(data.shape), dtype=torch.float32, device=data.device)
+    _check_dev("master", master, torch.float32, data.numel())
+    _check(lib().mnv_rows_master_init(data.data_ptr(), data.numel(), master.data_ptr(), C.c_void_p(stream)))
+    return master
+
+
+def rows_sgd_step(data, master, acc, data_dim: int, lr_colour: float, lr_sigma: float, n_rows: Optional[int] = None, stream: int = 0) -> None:
+    """mnv_rows_sgd_step: one gradient step on the rows whose accumulators are not all zero (master float32, data binary16 and acc int64
+    device tensors of n_rows * data_dim elements each; data may be a raw device pointer); clears the accumulators it consumed."""
+    import torch
+
+    if n_rows is None:
+        n_rows = master.numel() // int(data_dim)
+    n = int(n_rows) * int(data_dim)
+    _check_dev("master", master, torch.float32, n)
+    _check_dev("acc", acc, torch.int64, n)
+    if not isinstance(data, int) and (not data.is_cuda or not data.is_contiguous() or data.element_size() != 2 or data.numel() < n):
+        raise MnvError(MNV_E_INVALID, f"data must be a contiguous 16-bit device tensor with at least {n} elements")
+    _check(lib().mnv_rows_sgd_step(_ptr(data), master.data_ptr(), acc.data_ptr(), int(n_rows), int(data_dim), float(lr_colour), float(lr_sigma),
+                                   C.c_void_p(stream)))
 
 
 def render_voxels_accel_batch(accel: int, cams, opt: RenderOptions, tile=None, part=None, rgba=None, rgba8=None,

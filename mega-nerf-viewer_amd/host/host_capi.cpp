@@ -211,6 +211,28 @@ int mnv_n3tree_make_view_lod(mnv_n3tree *t, const mnv_lod_view *views, int32_t n
     });
 }
 
+int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets, const mnv_render_options *opt,
+                   const mnv_fit_params *params, int64_t *se_q32_out) {
+    if (!t || !cams || !targets || !opt || !params) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit: null argument");
+    if (n_cams < 1) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit: no camera");
+    return guarded([&] {
+        const std::vector<int64_t> se = t->tree.fit(std::vector<mnv_camera>(cams, cams + n_cams), std::vector<const float *>(targets, targets + n_cams), *opt, *params);
+        if (se_q32_out) std::copy(se.begin(), se.end(), se_q32_out);
+        return MNV_OK;
+    });
+}
+
+int mnv_n3tree_fit_to_tree(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt,
+                           const mnv_fit_params *params, int64_t *se_q32_out) {
+    if (!t || !teacher || !cams || !opt || !params) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit_to_tree: null argument");
+    if (n_cams < 1) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit_to_tree: no camera");
+    return guarded([&] {
+        const std::vector<int64_t> se = t->tree.fit_to(teacher->tree, std::vector<mnv_camera>(cams, cams + n_cams), *opt, *params);
+        if (se_q32_out) std::copy(se.begin(), se.end(), se_q32_out);
+        return MNV_OK;
+    });
+}
+
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim) {
     viewer::DataFormat f;
     f.parse(str ? str : "");
@@ -517,6 +539,15 @@ int mnv_renderer_set_view_lod(mnv_renderer *r, const mnv_lod_view *views, int32_
     if (n_views < 0 || n_views > 4096) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_view_lod: n_views outside [0, 4096]");
     return guarded([&] {
         r->rend.set_view_lod(n_views ? std::vector<mnv_lod_view>(views, views + n_views) : std::vector<mnv_lod_view>(), pixels, min_depth, max_depth);
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_set_lod_fit(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, const mnv_fit_params *params) {
+    if (!r || !params || (n_cams > 0 && !cams)) return mnv::set_error(MNV_E_INVALID, "null argument");
+    if (n_cams < 0) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_lod_fit: negative camera count");
+    return guarded([&] {
+        r->rend.set_lod_fit(n_cams ? std::vector<mnv_camera>(cams, cams + n_cams) : std::vector<mnv_camera>(), *params);
         return MNV_OK;
     });
 }

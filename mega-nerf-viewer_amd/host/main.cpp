@@ -55,6 +55,13 @@
 //                    first; focal length max(fx, fy)); nothing is cut above depth --lod_min (default 1), nothing kept below --lod_max
 //                    (default 23).  Prints the kept chunks per depth; --save_lod OUT.npz writes the tree.  Refused with --lod, --gpus,
 //                    --use_splitting and --use_guided_sampling.
+//   --lod_fit ITERS  with --lod or --lod_pixels: fit the level of detail to the full tree before it is marched or written
+//                    (VolumeRenderer::set_lod_fit, N3Tree::fit_to: mnv_rays_grad + mnv_rows_sgd_step, ITERS full-batch gradient steps) at
+//                    the poses of this run -- the --frames / --orbit loop stepped on a copy of the camera, as --lod_pixels does -- and print
+//                    the PSNR of the fitted rays before every step.  --fit_lr_colour X / --fit_lr_sigma Y: the learning rates (defaults
+//                    1 and 20: the rates at which the numpy restatement's loss falls at every step on the test suite's fit scene, where
+//                    a leaf of the cut covers a few pixels of a frame; the gradient of a row is a SUM over the rays through its voxel,
+//                    so larger frames want smaller rates).  At most 2^24 pixels over the poses.
 //   --target PREFIX  score frame f against PREFIX_%04d.ppm (the P6 files --out writes) on the device (VolumeRenderer::set_target,
 //                    mnv_frame_metrics with MNV_METRIC_QUANTISED: the file --out would write against the file that was read) and print
 //                    "frame F: psnr ..." when the frame is collected, then the means over the frames.  --ssim adds SSIM (11 x 11 Gaussian
@@ -152,6 +159,8 @@ void usage() {
               "                  [--lod D [--save_lod OUT.npz]]   march (and write) the tree truncated at depth D, interior rows mipped from their children\n"
               "                  [--lod_pixels P [--lod_min D] [--lod_max D] [--save_lod OUT.npz]]   march (and write) the tree cut where a voxel covers\n"
               "                   less than P pixels from every pose of this run\n"
+              "                  [--lod_fit ITERS [--fit_lr_colour X] [--fit_lr_sigma Y]]   with --lod / --lod_pixels: fit that tree's rows to the full\n"
+              "                   tree's frames at the poses of this run first (ITERS gradient steps)\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
               "                   0 = excluded): PSNR and, with --ssim, SSIM per frame and their means; not with --gpus.  Out of scope: pose\n"
               "                   lists (poses stay --orbit or the API) and LPIPS (it needs a network this repository does not have)\n"
@@ -638,6 +647,11 @@ int main(int argc, char **argv) {
         if (args.has("lod_pixels") && (lod_min < 1 || lod_max < lod_min)) throw std::runtime_error("--lod_pixels: need 1 <= --lod_min <= --lod_max");
         if (args.has("lod_pixels") && (args.has("lod") || args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
             throw std::runtime_error("--lod_pixels renders a cut copy of the tree on one GPU: it cannot be combined with --lod, --gpus, --use_splitting or --use_guided_sampling");
+        const long lod_fit = args.l("lod_fit", 0);
+        const float fit_lr_colour = args.f("fit_lr_colour", 1.f), fit_lr_sigma = args.f("fit_lr_sigma", 20.f);
+        if (args.has("lod_fit") && lod_fit < 1) throw std::runtime_error("--lod_fit takes an iteration count of at least 1");
+        if ((args.has("lod_fit") || args.has("fit_lr_colour") || args.has("fit_lr_sigma")) && !((args.has("lod") || args.has("lod_pixels")) && args.has("lod_fit")))
+            throw std::runtime_error("--lod_fit needs --lod or --lod_pixels; --fit_lr_colour and --fit_lr_sigma need --lod_fit");
         if (args.has("lod") && (args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
             throw std::runtime_error("--lod renders a truncated copy of the tree on one GPU: it cannot be combined with --gpus, --use_splitting or --use_guided_sampling");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
@@ -692,11 +706,33 @@ int main(int argc, char **argv) {
         rend.aa_samples = (int)args.l("aa", 1);
         rend.aa_filter = aa_filter == "box" ? MNV_AA_BOX : MNV_AA_TENT;
         rend.projection = projection == "ortho" ? MNV_PROJ_ORTHO : projection == "equirect" ? MNV_PROJ_EQUIRECT : MNV_PROJ_PINHOLE;
+        // --lod_fit: the camera of every pose this run renders (the frame loop below, stepped on a copy of the camera), and the fit of a cut
+        std::vector<mnv_camera> fit_cams;
+        const mnv_fit_params fit_params{(int32_t)lod_fit, fit_lr_colour, fit_lr_sigma, 0};
+        if (lod_fit > 0) {
+            viewer::Camera walk = rend.camera;
+            for (long f = 0; f < std::max<long>(frames, 1) && fit_cams.size() < 4096; ++f) {
+                walk._update();
+                fit_cams.push_back(walk.c_abi());
+                if (orbit == 0.0) break;  // (every frame has the same pose)
+                orbit_step(walk, orbit);
+            }
+            rend.set_lod_fit(fit_cams, fit_params);
+        }
+        auto fit_cut = [&](viewer::N3Tree &cut) {
+            if (lod_fit < 1) return;
+            const std::vector<int64_t> se = cut.fit_to(tree, fit_cams, *rend.options.c_abi(), fit_params);
+            std::printf("lod_fit: %zu pose(s), lr_colour %g, lr_sigma %g; mean squared error of the fitted rays before each step (x 1e6):", fit_cams.size(),
+                        (double)fit_lr_colour, (double)fit_lr_sigma);
+            for (int64_t q : se) std::printf(" %.3f", (double)q / 4294967296.0 / (3.0 * (double)width * height * (double)fit_cams.size()) * 1e6);
+            std::printf("\n");
+        };
         if (lod > 0) {
             if (tree.N <= 0) throw std::runtime_error("--lod needs a tree (N > 0)");
             rend.set_lod((int)lod);
             if (args.has("save_lod")) {
                 const std::unique_ptr<viewer::N3Tree> cut = tree.make_lod((int)lod);
+                fit_cut(*cut);
                 cut->save_npz(args.get("save_lod", ""));
                 std::printf("save_lod: depth %ld, %d of %d chunks -> %s\n", lod, cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
             }
@@ -719,6 +755,7 @@ int main(int argc, char **argv) {
             for (int d = 1; d < 24 && kept[d] > 0; ++d) std::printf(" %lld", (long long)kept[d]);
             std::printf("\n");
             if (args.has("save_lod")) {
+                fit_cut(*cut);
                 cut->save_npz(args.get("save_lod", ""));
                 std::printf("save_lod: %d of %d chunks -> %s\n", cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
             }

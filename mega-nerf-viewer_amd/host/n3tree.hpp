@@ -120,6 +120,16 @@ struct N3Tree {
     void make_view_lod_into(N3Tree &out, const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23,
                             void *hip_stream = nullptr, int64_t *kept_at_depth = nullptr) const;
 
+    // Optimise this tree's rows (on the device) against one device float target frame [height][width][4] per camera, full batch:
+    // params.iterations times { for every camera mnv_generate_rays + mnv_rays_grad, then one mnv_rows_sgd_step } on a float32 master copy
+    // of the rows (include/mnv.h, mnv_n3tree_fit).  The structure does not change.  At the end the accel is rebuilt and the host arrays
+    // are refreshed.  Returns the se_q32 of every iteration's rays before its step.  Waits for the stream.
+    std::vector<int64_t> fit(const std::vector<mnv_camera> &cams, const std::vector<const float *> &targets, const mnv_render_options &opt,
+                             const mnv_fit_params &params, void *hip_stream = nullptr);
+    // fit against the frames of `teacher` (on the device with its accel) at the cameras: a level of detail fitted to its full tree.
+    std::vector<int64_t> fit_to(const N3Tree &teacher, const std::vector<mnv_camera> &cams, const mnv_render_options &opt, const mnv_fit_params &params,
+                                void *hip_stream = nullptr);
+
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;
 

@@ -197,6 +197,12 @@ struct VolumeRenderer::Impl {
     std::unique_ptr<N3Tree> view_lod_tree;
     int view_lod_gen = 0, wire_view_gen = 0;
     int view_lod_token() const { return view_lod_views.empty() ? 0 : view_lod_gen; }
+    // set_lod_fit: the cameras and parameters every level of detail is fitted with when it is built (no iterations: off)
+    std::vector<mnv_camera> lod_fit_cams;
+    mnv_fit_params lod_fit{};
+    void fit_lod(N3Tree &cut, const RenderOptions &o) {
+        if (lod_fit.iterations > 0 && !lod_fit_cams.empty()) cut.fit_to(*tree, lod_fit_cams, *o.c_abi(), lod_fit, stream);
+    }
     N3Tree &march_tree() const { return lod_tree ? *lod_tree : *tree; }
     void drop_lod_trees() {  // (frames in flight may march them)
         if (!lod_trees.empty() || view_lod_tree) sync_all();
@@ -620,6 +626,16 @@ void VolumeRenderer::set_view_lod(const std::vector<mnv_lod_view> &views, float 
 }
 bool VolumeRenderer::view_lod() const { return !impl_->view_lod_views.empty(); }
 
+void VolumeRenderer::set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params &params) {
+    if (params.iterations < 0) throw StatusError(MNV_E_INVALID, "set_lod_fit: negative iteration count");
+    if (!std::isfinite(params.lr_colour) || !std::isfinite(params.lr_sigma) || params.lr_colour < 0.f || params.lr_sigma < 0.f)
+        throw StatusError(MNV_E_INVALID, "set_lod_fit: the learning rates must be finite and not negative");
+    Impl &I = *impl_;
+    I.drop_lod_trees();  // (trees fitted otherwise, or not at all, go: the next frame builds its tree again)
+    I.lod_fit_cams = cams;
+    I.lod_fit = params;
+}
+
 void VolumeRenderer::clear() {
     impl_->drop_lod_trees();
     impl_->tree = nullptr;
@@ -813,6 +829,7 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
             I.sync_all();
             I.lod_trees.push_back({I.lod, I.tree->make_lod(I.lod, I.stream)});
             I.lod_tree = I.lod_trees.back().tree.get();
+            I.fit_lod(*I.lod_tree, options);
         }
     }
     if (!I.view_lod_views.empty() && P.kind != FramePlan::BACKGROUND) {  // set_view_lod: the same with the one tree of the current views
@@ -821,6 +838,7 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
         if (!I.view_lod_tree) {
             I.sync_all();
             I.view_lod_tree = I.tree->make_view_lod(I.view_lod_views, I.view_lod_pixels, I.view_lod_min, I.view_lod_max, I.stream);
+            I.fit_lod(*I.view_lod_tree, options);
         }
         I.lod_tree = I.view_lod_tree.get();
     }

@@ -169,6 +169,11 @@ struct VolumeRenderer {
     // focal length that is not finite, focal_px <= 0, pixels negative or not finite, min_depth < 1, max_depth < min_depth.
     void set_view_lod(const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23);
     bool view_lod() const;
+    // Fit the level of detail to the full tree (N3Tree::fit_to; mnv_n3tree_fit_to_tree).  params.iterations == 0 or an empty list (the
+    // default): nothing changes.  Otherwise every tree set_lod / set_view_lod builds from now on is fitted, right after it is built, to the
+    // frames of the tree that was set at the listed cameras; trees built before are dropped, so the next frame builds and fits anew.
+    // Refused wherever set_lod is (render() says so).  Refused here: negative iterations, learning rates that are not finite or negative.
+    void set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params &params);
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
