@@ -1244,6 +1244,65 @@ int mnv_rows_master_init(const uint16_t *data /* device [n] */, int64_t n, float
 int mnv_rows_sgd_step(uint16_t *data, float *master, int64_t *acc /* device [n_rows][data_dim] each */, int64_t n_rows, int32_t data_dim,
                       float lr_colour, float lr_sigma, void *hip_stream);
 
+/* ------------------------------------------------ culling a tree to a pose set: the largest weight per leaf, then a bottom-up cull
+ * A batch renderer knows its poses in advance.  Leaves no listed ray weights above zero -- occluded ones, those behind an early stop, the
+ * inside of a thick shell -- still cost rows and accel.  The octree family's step for this (PlenOctree extraction / compression): record per
+ * leaf the largest compositing weight any ray gave it, drop the leaves under a threshold, collapse the chunks that became all-empty.
+ * mnv_rays_visibility is the first half, mnv_tree_cull the second; mnv_tree_cut on (child, data_out) with keep_out compacts the result.
+ *
+ * mnv_rays_visibility (asynchronous on hip_stream) works on the tree VIEW's own device arrays, like mnv_rays_grad; origins / dirs / tmax /
+ * width / height as there.  wmax: device uint32 [capacity * 8], a word per voxel; sums: device mnv_vis_sums, 8-byte aligned.  The kernel
+ * takes the MAXIMUM into wmax and ADDS into sums: calls accumulate, the caller clears both once; a word of 0 means "never weighted".
+ * Contract: the rays are marched exactly as mnv_rays_grad's forward marches them, which is mnv_render_rays_accel's march: the same set-up,
+ * descent, delta_t, att_s = expf(-d_s sigma), w_s = T_s * (1.f - att_s), T_{s+1} = T_s * att_s (names as above), the same early stop -- the
+ * sample that ends the ray counts -- and the same skipped rays: a descent that leaves the tree (more than 23 levels, a link outside
+ * [1, capacity)), more than 2^20 steps, a step that does not advance.  A skipped ray adds nothing to wmax.  For every dense sample of the
+ * other rays with w_s > 0:  wmax[v_s] = max(wmax[v_s], bits(w_s)), compared as unsigned integers.  Non-negative binary32 values order as
+ * their bit patterns, so the words depend on neither ray order, launch shape nor atomic order.  A NaN or non-positive w_s writes nothing.
+ * No row column but sigma is read: there is no colour, no SH basis (rot_dirs and basis_minmax do not enter) and no target.
+ * Sums: n_rays (the rays that were not skipped, misses included), n_stopped, n_samples (their dense samples), n_skipped.
+ * MNV_E_UNSUPPORTED, before any launch: options.render_depth, N != 2, rows other than RGBA and SH 1 / 4 / 9 / 16 / 25.
+ * MNV_E_INVALID, before any launch: a null tree / array / options / wmax / sums, width or height < 1, width * height > 2^22, capacity < 1, a
+ *   data_dim too small for the row format, misaligned arrays, step_size not finite or <= 0.
+ *
+ * mnv_tree_cull.  wmax: device uint32 [capacity * 8]; weight_thresh finite and >= 0; data_out: device [capacity][8][data_dim], 16-byte
+ * aligned; keep_out: device uint8 [capacity]; kept_at_depth: HOST int64 [24] as mnv_tree_select_cut's; counts: HOST.  Waits for hip_stream
+ * (it hands counts back).  N == 2, any data_dim from 2 to 1024, either row format.  The input tree is never written.
+ * Contract:
+ *   A leaf voxel v (child == 0) of a chunk reached from the root is SEEN iff uint_as_float(wmax[v]) > weight_thresh: strictly greater; a
+ *   NaN pattern is not seen, nor is a negative one.  A seen leaf's row is copied bit for bit; a leaf that is not seen gets a row of 0x0000.
+ *   A chunk is DEAD iff each of its eight voxels is a leaf that is not seen or an interior voxel whose child chunk is dead.  The voxel above
+ *   a dead chunk k gets a row of 0x0000 and keep_out[k] = 0; the voxel above a live chunk keeps its row bit for bit and keep_out[k] = 1.
+ *   The root chunk is always kept (keep_out[0] = 1), even when everything under it died.  Chunks the walk does not reach get keep 0 and
+ *   their rows are copied, as mnv_tree_mip_rows treats them.  A chunk under a dead chunk is dead: the set is parent-closed by construction.
+ *   So mnv_tree_cut on a view whose data is data_out, with keep_out and new_capacity = the sum of kept_at_depth, yields the culled tree; the
+ *   voxel above a dead chunk becomes an empty leaf.
+ *   counts: leaves_seen; leaves_culled: the leaves not seen whose density was h(sigma) > 0 before (h as mnv_tree_mip_rows has it);
+ *   dead_chunks (reached chunks with keep 0).  Level order inside the walk depends on the schedule and decides no output byte; no atomic
+ *   operation decides one (the counts are sums of integers).
+ * What this does to frames.  For options with sigma_thresh >= 0 and stop_thresh >= 2^-24, after mnv_rays_visibility over a ray list and
+ * mnv_tree_cull at weight_thresh == 0, the arrays (child, data_out), NOT cut, give every listed ray the pixel the source tree gives it,
+ * bit for bit (through mnv_render_rays_accel, mnv_rays_grad or another mnv_rays_visibility).  A culled leaf took either no dense sample or
+ * only samples with w_s == 0 from every listed ray; with T_s >= stop_thresh >= 2^-24 that means 1.f - att_s == 0, att_s == 1 exactly: T was
+ * unchanged by the sample and every colour term it added was w_s / den = +0 (or c * w_s = +-0 for RGBA rows, added to a sum that started at
+ * +0) -- for rows of finite values; a non-finite colour coefficient in a culled leaf made a NaN term that the cull removes.  After the cull the leaf's sigma is +0, which is not above sigma_thresh: the sample is not taken, and the step sequence -- which does
+ * not depend on sigma -- is the same.    After the CUT the march crosses a collapsed region in fewer, larger steps, each of
+ * which adds step_size, so later sample lengths shift: frames of the cut tree are close to the source's, not equal, as on any coarser tree.
+ * MNV_E_INVALID: a null argument, weight_thresh negative or not finite, a child link outside [1, capacity), a chunk reached twice,
+ * overlapping or misaligned arrays, host arrays.  MNV_E_UNSUPPORTED: N != 2, more than 23 levels, data_dim above 1024. */
+typedef struct mnv_vis_sums {
+    int64_t n_rays, n_stopped, n_samples, n_skipped, reserved[4];
+} mnv_vis_sums;
+typedef struct mnv_cull_counts {
+    int64_t leaves_seen, leaves_culled, dead_chunks, reserved;
+} mnv_cull_counts;
+int mnv_rays_visibility(const mnv_tree_view *device_tree, const float *origins, const float *dirs /* device [height][width][3] */,
+                        const float *tmax /* device [height][width] or NULL */, int32_t width, int32_t height, const mnv_render_options *opt,
+                        uint32_t *wmax /* device [capacity * 8] */, mnv_vis_sums *sums /* device */, void *hip_stream);
+int mnv_tree_cull(const mnv_tree_view *device_tree, const uint32_t *wmax, float weight_thresh, uint16_t *data_out,
+                  uint8_t *keep_out /* device [capacity] */, int64_t kept_at_depth[24] /* HOST */, mnv_cull_counts *counts /* HOST */,
+                  void *hip_stream);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -1280,6 +1339,13 @@ int mnv_n3tree_make_lod(mnv_n3tree *t, int32_t max_depth, mnv_n3tree **out);
  * not on the device; otherwise the codes of the three calls. */
 int mnv_n3tree_make_view_lod(mnv_n3tree *t, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth,
                              int64_t *kept_at_depth, mnv_n3tree **out);
+/* N3Tree::make_culled: a tree that is on the device without what the pinhole frames of n_cams cameras cannot see.  wmax is cleared; per
+ * camera mnv_generate_rays(MNV_PROJ_PINHOLE, the whole image) then mnv_rays_visibility; then mnv_tree_cull at weight_thresh and
+ * mnv_tree_cut, as a NEW tree exactly as mnv_n3tree_make_lod makes one (arrays, accel, host arrays downloaded; `t` is not changed).
+ * kept_at_depth: int64 [24] or NULL, the kept chunks per depth; counts: or NULL.  Runs on the null stream and waits for it.
+ * MNV_E_INVALID: a tree that is not on the device, no camera, a camera without pixels or of more than 2^22; otherwise the codes of the calls. */
+int mnv_n3tree_make_culled(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt, float weight_thresh,
+                           int64_t *kept_at_depth, mnv_cull_counts *counts, mnv_n3tree **out);
 /* N3Tree::fit: optimise the rows of a tree that is on the device against target frames, full batch.  Per iteration: for each camera,
  * mnv_generate_rays(MNV_PROJ_PINHOLE, the whole image) then mnv_rays_grad against targets[i] (a DEVICE float [height][width][4] frame of that
  * camera's size; alpha 0 excludes a pixel), all into one accumulator; then one mnv_rows_sgd_step.  The float32 master copy is made at the
@@ -1430,6 +1496,14 @@ int mnv_renderer_set_lod(mnv_renderer *r, int32_t max_depth);
  * options.use_splitting, options.use_guided_sampling, several ranks, or mnv_renderer_set_lod with a depth above 0.  MNV_E_INVALID here:
  * n_views outside [0, 4096], views NULL with n_views > 0, and what mnv_tree_select_cut refuses in views, pixels, min_depth, max_depth. */
 int mnv_renderer_set_view_lod(mnv_renderer *r, const mnv_lod_view *views, int32_t n_views, float pixels, int32_t min_depth, int32_t max_depth);
+/* Culling to a pose set.  n_cams == 0 (the default; cams may be NULL): render() is what it is without this call (byte for byte).  With
+ * n_cams >= 1 the frames march the tree of mnv_n3tree_make_culled(cams, the renderer's options, weight_thresh) instead of the tree that was
+ * set, in the frame kinds mnv_renderer_set_lod serves; the tree is built at the first frame that needs it, kept until the cameras, the
+ * threshold or the march options (step_size, sigma_thresh, stop_thresh, render_bbox) change, and dropped where that call's trees are.
+ * mnv_renderer_render refuses (MNV_E_INVALID) the combinations that call lists, and this one together with mnv_renderer_set_lod(D > 0) or
+ * mnv_renderer_set_view_lod.  MNV_E_INVALID here: n_cams < 0, cams NULL with n_cams > 0, weight_thresh negative or not finite, a camera
+ * without pixels or of more than 2^22. */
+int mnv_renderer_set_cull(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, float weight_thresh);
 /* VolumeRenderer::set_lod_fit (n_cams == 0 or params->iterations == 0, the default, = off: every frame is what it is without this call, byte
  * for byte).  Otherwise every tree mnv_renderer_set_lod / mnv_renderer_set_view_lod builds from now on is fitted, right after it is built,
  * to the frames of the tree that was set at the listed cameras (mnv_n3tree_fit_to_tree with `params`); trees built before are dropped.  The

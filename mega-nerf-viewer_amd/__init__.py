@@ -155,6 +155,17 @@ class FitParams(C.Structure):
 FIT_SUMS = ("n_rays", "n_stopped", "n_samples", "n_skipped", "se_q32")   # the first five int64 words of mnv_fit_sums (8 in all)
 
 
+VIS_SUMS = ("n_rays", "n_stopped", "n_samples", "n_skipped")   # the first four int64 words of mnv_vis_sums (8 in all)
+
+
+class CullCounts(C.Structure):
+    """mnv_cull_counts"""
+    _fields_ = [("leaves_seen", C.c_int64), ("leaves_culled", C.c_int64), ("dead_chunks", C.c_int64), ("reserved", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_[:3]}
+
+
 class MetricSums(C.Structure):
     """mnv_metric_sums: the five int64 words mnv_frame_metrics leaves in device memory."""
     _fields_ = [("n_px", C.c_int64), ("se_q32", C.c_int64), ("n_win", C.c_int64), ("ssim_q32", C.c_int64), ("reserved", C.c_int64)]
@@ -423,12 +434,18 @@ _SIGNATURES = {
     "mnv_n3tree_make_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
     "mnv_renderer_set_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32]),
     "mnv_renderer_set_lod_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FitParams)]),
+    "mnv_renderer_set_cull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]),
     "mnv_rays_grad": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RenderOptions), C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "mnv_rows_master_init": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mnv_rows_sgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
     "mnv_n3tree_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(FitParams), C.c_void_p]),
     "mnv_n3tree_fit_to_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RenderOptions), C.POINTER(FitParams), C.c_void_p]),
+    "mnv_rays_visibility": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RenderOptions), C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "mnv_tree_cull": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(CullCounts), C.c_void_p]),
+    "mnv_n3tree_make_culled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RenderOptions), C.c_float, C.POINTER(C.c_int64), C.POINTER(CullCounts),
+                                         C.POINTER(C.c_void_p)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -755,6 +772,19 @@ class N3Tree:
                                               kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
         out = N3Tree(h.value)
         return (out, kept) if return_counts else out
+
+    def make_culled(self, cams, opt: RenderOptions, weight_thresh: float = 0.0):
+        """N3Tree::make_culled: a new tree on the device, as make_lod's, without what the pinhole frames of `cams` cannot see: leaves no ray
+        of those frames weights above weight_thresh are emptied, chunks left all-empty collapse into an empty leaf (rays_visibility per
+        camera, tree_cull, tree_cut).  -> (tree, kept_at_depth int64 [24], counts dict).  Needs move_to_device."""
+        n = len(cams)
+        if n < 1:
+            raise MnvError(MNV_E_INVALID, "at least one camera")
+        arr = (CameraStruct * n)(*[c.c for c in cams])
+        h, kept, counts = C.c_void_p(), np.zeros(24, np.int64), CullCounts()
+        _check(lib().mnv_n3tree_make_culled(self._h, arr, n, C.byref(opt), float(weight_thresh), kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(counts),
+                                            C.byref(h)))
+        return N3Tree(h.value), kept, counts.as_dict()
 
     def fit(self, cams, targets, opt: RenderOptions, iterations: int, lr_colour: float, lr_sigma: float) -> np.ndarray:
         """N3Tree::fit: `iterations` full-batch gradient steps on this tree's rows (on the device) against `targets`, one float32 device
@@ -1361,6 +1391,15 @@ class Renderer:
         _check(lib().mnv_renderer_set_view_lod(self._h, table.ctypes.data if table.shape[0] else None, int(table.shape[0]), float(pixels),
                                                int(min_depth), int(max_depth)))
 
+    def set_cull(self, cams=(), weight_thresh: float = 0.0) -> None:
+        """VolumeRenderer::set_cull: every frame marches N3Tree.make_culled(cams, options, weight_thresh) of the tree that was set (built at
+        the first frame that needs it, kept until the cameras, the threshold or the march options change); an empty list (the default)
+        is the full tree, unchanged.  What render() refuses with a culled tree (use_splitting, use_guided_sampling, ranks, set_lod above
+        0, set_view_lod) raises there, with MNV_E_INVALID."""
+        cams = list(cams)
+        arr = (CameraStruct * max(len(cams), 1))(*[c.c for c in cams])
+        _check(lib().mnv_renderer_set_cull(self._h, arr if cams else None, len(cams), float(weight_thresh)))
+
     def set_lod_fit(self, cams=(), iterations: int = 0, lr_colour: float = 0.0, lr_sigma: float = 0.0) -> None:
         """VolumeRenderer::set_lod_fit: every tree set_lod / set_view_lod builds from now on is fitted to the full tree at `cams`
         (N3Tree.fit_to) right after it is built; no camera or no iteration (the default) switches it off."""
@@ -1926,6 +1965,36 @@ def rays_grad(view: TreeView, origins, dirs, target, opt: RenderOptions, acc, su
     with _timed(stream):
         _check(lib().mnv_rays_grad(C.byref(view), origins.data_ptr(), dirs.data_ptr(), target.data_ptr(), _ptr(tmax), width, height, C.byref(opt), _ptr(rgba),
                                    acc.data_ptr(), sums.data_ptr(), C.c_void_p(stream)))
+
+
+def rays_visibility(view: TreeView, origins, dirs, opt: RenderOptions, wmax, sums, tmax=None, stream: int = 0) -> None:
+    """mnv_rays_visibility (asynchronous on `stream`): marches the rays (as rays_grad takes them) through the DEVICE tree view and takes, per
+    leaf voxel, the maximum of the compositing weights T * (1 - att) its dense samples got into wmax (int32 / uint32 device tensor
+    [capacity * 8]: binary32 bit patterns, 0 = never weighted) and adds the ray counts into sums (int64 [8], VIS_SUMS names the first four);
+    both are the caller's to zero, calls accumulate."""
+    import torch
+
+    _check_rays("origins", origins)
+    _check_rays("dirs", dirs, tuple(origins.shape))
+    height, width = (1, int(origins.shape[0])) if origins.dim() == 2 else (int(origins.shape[0]), int(origins.shape[1]))
+    if wmax is None or not wmax.is_cuda or not wmax.is_contiguous() or wmax.element_size() != 4 or wmax.numel() < view.capacity * 8:
+        raise MnvError(MNV_E_INVALID, f"wmax must be a contiguous 32-bit device tensor with at least {view.capacity * 8} elements")
+    _check_dev("sums", sums, torch.int64, 8)
+    if tmax is not None:
+        _check_dev("tmax", tmax, torch.float32, width * height)
+    with _timed(stream):
+        _check(lib().mnv_rays_visibility(C.byref(view), origins.data_ptr(), dirs.data_ptr(), _ptr(tmax), width, height, C.byref(opt), wmax.data_ptr(),
+                                         sums.data_ptr(), C.c_void_p(stream)))
+
+
+def tree_cull(tree_view: TreeView, wmax, weight_thresh: float, data_out, keep_out, stream: int = 0):
+    """mnv_tree_cull: the rows of a device tree view with every leaf whose word of wmax (rays_visibility's array) is not above weight_thresh
+    zeroed, into data_out (16-bit device tensor [capacity, 8, data_dim], never the tree's own array), and which chunks stay into keep_out
+    (uint8 device tensor [capacity]) -- tree_cut's input.  -> (kept_at_depth int64 [24], counts dict).  Waits for `stream`."""
+    kept, counts = np.zeros(24, np.int64), CullCounts()
+    _check(lib().mnv_tree_cull(C.byref(tree_view), _ptr(wmax), float(weight_thresh), _ptr(data_out), _ptr(keep_out), kept.ctypes.data_as(C.POINTER(C.c_int64)),
+                               C.byref(counts), C.c_void_p(stream)))
+    return kept, counts.as_dict()
 
 
 def rows_master_init(data, master=None, stream: int = 0):

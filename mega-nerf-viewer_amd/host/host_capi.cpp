@@ -211,6 +211,24 @@ int mnv_n3tree_make_view_lod(mnv_n3tree *t, const mnv_lod_view *views, int32_t n
     });
 }
 
+int mnv_n3tree_make_culled(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt, float weight_thresh, int64_t *kept_at_depth,
+                           mnv_cull_counts *counts, mnv_n3tree **out) {
+    if (!t || !out || !cams || !opt) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_make_culled: null argument");
+    *out = nullptr;
+    if (n_cams < 1) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_make_culled: no camera");
+    return guarded([&] {
+        auto *h = new mnv_n3tree();
+        try {
+            t->tree.make_culled_into(h->tree, std::vector<mnv_camera>(cams, cams + n_cams), *opt, weight_thresh, nullptr, kept_at_depth, counts);
+        } catch (...) {
+            delete h;
+            throw;
+        }
+        *out = h;
+        return MNV_OK;
+    });
+}
+
 int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets, const mnv_render_options *opt,
                    const mnv_fit_params *params, int64_t *se_q32_out) {
     if (!t || !cams || !targets || !opt || !params) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit: null argument");
@@ -539,6 +557,15 @@ int mnv_renderer_set_view_lod(mnv_renderer *r, const mnv_lod_view *views, int32_
     if (n_views < 0 || n_views > 4096) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_view_lod: n_views outside [0, 4096]");
     return guarded([&] {
         r->rend.set_view_lod(n_views ? std::vector<mnv_lod_view>(views, views + n_views) : std::vector<mnv_lod_view>(), pixels, min_depth, max_depth);
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_set_cull(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, float weight_thresh) {
+    if (!r || (n_cams > 0 && !cams)) return mnv::set_error(MNV_E_INVALID, "null argument");
+    if (n_cams < 0) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_cull: negative camera count");
+    return guarded([&] {
+        r->rend.set_cull(n_cams ? std::vector<mnv_camera>(cams, cams + n_cams) : std::vector<mnv_camera>(), weight_thresh);
         return MNV_OK;
     });
 }

@@ -55,6 +55,11 @@
 //                    first; focal length max(fx, fy)); nothing is cut above depth --lod_min (default 1), nothing kept below --lod_max
 //                    (default 23).  Prints the kept chunks per depth; --save_lod OUT.npz writes the tree.  Refused with --lod, --gpus,
 //                    --use_splitting and --use_guided_sampling.
+//   --cull W         the frames march the tree without what the poses of this run cannot see (VolumeRenderer::set_cull,
+//                    N3Tree::make_culled: leaves no ray of those frames weights above W are emptied, chunks left all-empty collapse);
+//                    the poses are the --frames / --orbit loop stepped on a copy of the camera, as --lod_pixels does.  Prints the chunks
+//                    per depth before and after and the counts; --save_lod OUT.npz writes the tree.  Refused with --lod, --lod_pixels,
+//                    --lod_fit, --gpus, --use_splitting and --use_guided_sampling.
 //   --lod_fit ITERS  with --lod or --lod_pixels: fit the level of detail to the full tree before it is marched or written
 //                    (VolumeRenderer::set_lod_fit, N3Tree::fit_to: mnv_rays_grad + mnv_rows_sgd_step, ITERS full-batch gradient steps) at
 //                    the poses of this run -- the --frames / --orbit loop stepped on a copy of the camera, as --lod_pixels does -- and print
@@ -159,6 +164,7 @@ void usage() {
               "                  [--lod D [--save_lod OUT.npz]]   march (and write) the tree truncated at depth D, interior rows mipped from their children\n"
               "                  [--lod_pixels P [--lod_min D] [--lod_max D] [--save_lod OUT.npz]]   march (and write) the tree cut where a voxel covers\n"
               "                   less than P pixels from every pose of this run\n"
+              "                  [--cull W [--save_lod OUT.npz]]   march (and write) the tree without what this run's poses cannot see (weights <= W)\n"
               "                  [--lod_fit ITERS [--fit_lr_colour X] [--fit_lr_sigma Y]]   with --lod / --lod_pixels: fit that tree's rows to the full\n"
               "                   tree's frames at the poses of this run first (ITERS gradient steps)\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
@@ -639,7 +645,11 @@ int main(int argc, char **argv) {
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
         const long lod = args.l("lod", 0);
         if (args.has("lod") && lod < 1) throw std::runtime_error("--lod takes a depth of at least 1");
-        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels")) throw std::runtime_error("--save_lod needs --lod or --lod_pixels");
+        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull")) throw std::runtime_error("--save_lod needs --lod, --lod_pixels or --cull");
+        const float cull_thresh = args.f("cull", 0.f);
+        if (args.has("cull") && (!std::isfinite(cull_thresh) || cull_thresh < 0.f)) throw std::runtime_error("--cull takes a finite weight threshold, 0 or more");
+        if (args.has("cull") && (args.has("lod") || args.has("lod_pixels") || args.has("lod_fit") || args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
+            throw std::runtime_error("--cull renders a culled copy of the tree on one GPU: it cannot be combined with --lod, --lod_pixels, --lod_fit, --gpus, --use_splitting or --use_guided_sampling");
         const float lod_pixels = args.f("lod_pixels", 0.f);
         const long lod_min = args.l("lod_min", 1), lod_max = args.l("lod_max", 23);
         if (args.has("lod_pixels") && (!std::isfinite(lod_pixels) || lod_pixels < 0.f)) throw std::runtime_error("--lod_pixels takes a finite size in pixels, 0 or more");
@@ -756,6 +766,47 @@ int main(int argc, char **argv) {
             std::printf("\n");
             if (args.has("save_lod")) {
                 fit_cut(*cut);
+                cut->save_npz(args.get("save_lod", ""));
+                std::printf("save_lod: %d of %d chunks -> %s\n", cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
+            }
+        }
+        if (args.has("cull")) {
+            if (tree.N <= 0) throw std::runtime_error("--cull needs a tree (N > 0)");
+            // the camera of every pose this run renders: the frame loop below, stepped on a copy of the camera
+            std::vector<mnv_camera> cams;
+            viewer::Camera walk = rend.camera;
+            for (long f = 0; f < std::max<long>(frames, 1) && cams.size() < 4096; ++f) {
+                walk._update();
+                cams.push_back(walk.c_abi());
+                if (orbit == 0.0) break;  // (every frame has the same pose)
+                orbit_step(walk, orbit);
+            }
+            if (orbit != 0.0 && frames > 4096) throw std::runtime_error("--cull serves at most 4096 poses (--frames)");
+            rend.set_cull(cams, cull_thresh);
+            int64_t kept[24];
+            mnv_cull_counts cc;
+            mnv_render_options march = *rend.options.c_abi();
+            march.render_depth = false;
+            const std::unique_ptr<viewer::N3Tree> cut = tree.make_culled(cams, march, cull_thresh, nullptr, kept, &cc);
+            // the chunks per depth before: a walk over the host links
+            int64_t before[24] = {0};
+            std::vector<std::pair<int32_t, int>> todo{{0, 1}};
+            while (!todo.empty()) {
+                const auto [c, d] = todo.back();
+                todo.pop_back();
+                if (d < 24) ++before[d];
+                for (int j = 0; j < 8; ++j) {
+                    const int32_t ch = tree.child[(size_t)c * 8 + j];
+                    if (ch != 0) todo.push_back({c + ch, d + 1});
+                }
+            }
+            std::printf("cull: weight_thresh %g, %zu pose(s), %d of %d chunks, chunks per depth before:", (double)cull_thresh, cams.size(), cut->capacity, tree.capacity);
+            for (int d = 1; d < 24 && before[d] > 0; ++d) std::printf(" %lld", (long long)before[d]);
+            std::printf(", kept per depth:");
+            for (int d = 1; d < 24 && kept[d] > 0; ++d) std::printf(" %lld", (long long)kept[d]);
+            std::printf("; leaves seen %lld, non-empty leaves culled %lld, dead chunks %lld\n", (long long)cc.leaves_seen, (long long)cc.leaves_culled,
+                        (long long)cc.dead_chunks);
+            if (args.has("save_lod")) {
                 cut->save_npz(args.get("save_lod", ""));
                 std::printf("save_lod: %d of %d chunks -> %s\n", cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
             }

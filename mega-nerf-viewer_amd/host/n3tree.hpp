@@ -120,6 +120,15 @@ struct N3Tree {
     void make_view_lod_into(N3Tree &out, const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23,
                             void *hip_stream = nullptr, int64_t *kept_at_depth = nullptr) const;
 
+    // This tree without what the pinhole frames of `cams` cannot see (include/mnv.h, "culling a tree to a pose set"): wmax cleared, then per
+    // camera mnv_generate_rays + mnv_rays_visibility, then mnv_tree_cull at weight_thresh and mnv_tree_cut.  The result is what make_lod's
+    // is: a new tree on the device with this tree's accel / parent / sample counts where it has them, host arrays downloaded.  This tree is
+    // not changed.  kept_at_depth: int64 [24] or null; counts: or null.  Needs move_to_device; waits for the stream.
+    std::unique_ptr<N3Tree> make_culled(const std::vector<mnv_camera> &cams, const mnv_render_options &opt, float weight_thresh, void *hip_stream = nullptr,
+                                        int64_t *kept_at_depth = nullptr, mnv_cull_counts *counts = nullptr) const;
+    void make_culled_into(N3Tree &out, const std::vector<mnv_camera> &cams, const mnv_render_options &opt, float weight_thresh, void *hip_stream = nullptr,
+                          int64_t *kept_at_depth = nullptr, mnv_cull_counts *counts = nullptr) const;
+
     // Optimise this tree's rows (on the device) against one device float target frame [height][width][4] per camera, full batch:
     // params.iterations times { for every camera mnv_generate_rays + mnv_rays_grad, then one mnv_rows_sgd_step } on a float32 master copy
     // of the rows (include/mnv.h, mnv_n3tree_fit).  The structure does not change.  At the end the accel is rebuilt and the host arrays
@@ -142,7 +151,7 @@ struct N3Tree {
 private:
     int N2_ = 0, N3_ = 0;
     void check_sizes();
-    // the common end of make_lod_into / make_view_lod_into: `o` becomes a device tree of new_cap chunks that `cut` fills
+    // the common end of make_lod_into / make_view_lod_into / make_culled_into: `o` becomes a device tree of new_cap chunks that `cut` fills
     // (child, data, parent, sample counts or null), with host arrays and, where this tree has one, an accel
     void compact_into(N3Tree &o, int64_t new_cap, const std::function<void(int32_t *, uint16_t *, int32_t *, int16_t *)> &cut, void *hip_stream) const;
 };

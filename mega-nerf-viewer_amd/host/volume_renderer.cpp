@@ -197,6 +197,19 @@ struct VolumeRenderer::Impl {
     std::unique_ptr<N3Tree> view_lod_tree;
     int view_lod_gen = 0, wire_view_gen = 0;
     int view_lod_token() const { return view_lod_views.empty() ? 0 : view_lod_gen; }
+    // set_cull: the cameras (empty: off) and the threshold of the culled tree, the tree built for them with the march options it was built
+    // under (until cameras, threshold or those options change, or the trees above go), and a number that changes with every call
+    std::vector<mnv_camera> cull_cams;
+    float cull_thresh = 0.f;
+    std::unique_ptr<N3Tree> cull_tree;
+    mnv_render_options cull_opt{};
+    int cull_gen = 0, wire_cull_gen = 0;
+    int cull_token() const { return cull_cams.empty() ? 0 : cull_gen; }
+    // the options the visibility march depends on (render_depth changes no weight and is switched off for it)
+    static bool same_march(const mnv_render_options &a, const mnv_render_options &b) {
+        return a.step_size == b.step_size && a.sigma_thresh == b.sigma_thresh && a.stop_thresh == b.stop_thresh &&
+               std::memcmp(a.render_bbox, b.render_bbox, sizeof(a.render_bbox)) == 0;
+    }
     // set_lod_fit: the cameras and parameters every level of detail is fitted with when it is built (no iterations: off)
     std::vector<mnv_camera> lod_fit_cams;
     mnv_fit_params lod_fit{};
@@ -205,9 +218,10 @@ struct VolumeRenderer::Impl {
     }
     N3Tree &march_tree() const { return lod_tree ? *lod_tree : *tree; }
     void drop_lod_trees() {  // (frames in flight may march them)
-        if (!lod_trees.empty() || view_lod_tree) sync_all();
+        if (!lod_trees.empty() || view_lod_tree || cull_tree) sync_all();
         lod_trees.clear();
         view_lod_tree.reset();
+        cull_tree.reset();
         lod_tree = nullptr;
     }
     // what draws this frame's inputs (set by render()): the grid, the visible meshes of VolumeRenderer::meshes, or both
@@ -626,6 +640,25 @@ void VolumeRenderer::set_view_lod(const std::vector<mnv_lod_view> &views, float 
 }
 bool VolumeRenderer::view_lod() const { return !impl_->view_lod_views.empty(); }
 
+void VolumeRenderer::set_cull(const std::vector<mnv_camera> &cams, float weight_thresh) {
+    Impl &I = *impl_;
+    if (!cams.empty()) {
+        if (!std::isfinite(weight_thresh) || weight_thresh < 0.f) throw StatusError(MNV_E_INVALID, "set_cull: weight_thresh must be finite and not negative");
+        for (const mnv_camera &c : cams)
+            if (c.width < 1 || c.height < 1 || (int64_t)c.width * c.height > ((int64_t)1 << 22))
+                throw StatusError(MNV_E_INVALID, "set_cull: a camera needs 1 .. 2^22 pixels");
+    }
+    if (I.cull_tree) {  // (frames in flight may march it)
+        I.sync_all();
+        I.cull_tree.reset();
+        I.lod_tree = nullptr;
+    }
+    I.cull_cams = cams;
+    I.cull_thresh = weight_thresh;
+    ++I.cull_gen;
+}
+bool VolumeRenderer::cull() const { return !impl_->cull_cams.empty(); }
+
 void VolumeRenderer::set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params &params) {
     if (params.iterations < 0) throw StatusError(MNV_E_INVALID, "set_lod_fit: negative iteration count");
     if (!std::isfinite(params.lr_colour) || !std::isfinite(params.lr_sigma) || params.lr_colour < 0.f || params.lr_sigma < 0.f)
@@ -742,7 +775,7 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
                           tree->data_format.basis_dim == 9 || tree->data_format.basis_dim == 16);
     const bool out_dim_differs = tree && model_on && I.mlp_desc.out_dim != tree->data_dim + 1;
     const bool inputs_set = I.inputs.tmax_px || I.inputs.rgba8_init;
-    const bool lod = tree && I.lod > 0, view_lod = tree && !I.view_lod_views.empty();
+    const bool lod = tree && I.lod > 0, view_lod = tree && !I.view_lod_views.empty(), cull = tree && !I.cull_cams.empty();
     bool mesh_visible = false;
     for (const mnv_mesh *m : meshes) mesh_visible = mesh_visible || (m && mnv_mesh_visible(m));
     const bool projected = projection != MNV_PROJ_PINHOLE, aa = !projected && aa_samples != 1, ranks = !projected && !aa && I.comm;
@@ -765,6 +798,10 @@ VolumeRenderer::FramePlan VolumeRenderer::plan() const {
          "set_view_lod: frames of a cut tree cannot edit or vote on the tree (use_splitting / use_guided_sampling)"},
         {view_lod && I.comm, true, "set_view_lod is for one rank: it cannot be combined with set_ranks"},
         {view_lod && lod, true, "set_view_lod and set_lod choose the tree a frame marches: only one of them can be on"},
+        {cull && (options.use_splitting || options.use_guided_sampling), true,
+         "set_cull: frames of a culled tree cannot edit or vote on the tree (use_splitting / use_guided_sampling)"},
+        {cull && I.comm, true, "set_cull is for one rank: it cannot be combined with set_ranks"},
+        {cull && (lod || view_lod), true, "set_cull and set_lod / set_view_lod choose the tree a frame marches: only one of them can be on"},
         {projected && projection != MNV_PROJ_ORTHO && projection != MNV_PROJ_EQUIRECT, true, "projection: unknown projection"},
         {projected && inputs_set, true, "projection: set_frame_inputs holds images of a pinhole camera; it cannot be combined with another projection"},
         {projected && I.comm, true, "projection: orthographic / equirectangular frames are for one rank (set_ranks)"},
@@ -842,6 +879,23 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
         }
         I.lod_tree = I.view_lod_tree.get();
     }
+    if (!I.cull_cams.empty() && P.kind != FramePlan::BACKGROUND) {  // set_cull: the same with the one tree of the current cameras
+        if (I.lod_version != I.tree_version) I.drop_lod_trees();
+        I.lod_version = I.tree_version;
+        mnv_render_options march = *options.c_abi();
+        march.render_depth = false;
+        if (I.cull_tree && !Impl::same_march(march, I.cull_opt)) {  // built under other march options: frames in flight may march it
+            I.sync_all();
+            I.cull_tree.reset();
+            ++I.cull_gen;
+        }
+        if (!I.cull_tree) {
+            I.sync_all();
+            I.cull_tree = I.tree->make_culled(I.cull_cams, march, I.cull_thresh, I.stream);
+            I.cull_opt = march;
+        }
+        I.lod_tree = I.cull_tree.get();
+    }
     if (P.kind == FramePlan::PROJECTED) {  // (draws no inputs; anti-aliasing buffers of earlier frames stay until the next pinhole frame)
         if (projection == MNV_PROJ_EQUIRECT && (!I.equirect_dev || I.equirect_w != I.width || I.equirect_h != I.height)) {
             I.sync_all();  // frames in flight read the old table
@@ -865,7 +919,7 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
         if (m && mnv_mesh_visible(m)) I.pass_meshes.push_back(m);
     if (!I.pass_meshes.empty()) I.can_reuse_results = false;  // (a mesh may have moved: the samples of the last guided frame were limited by it)
     if (P.show_grid && (!I.wire || I.wire_depth != options.grid_max_depth || I.wire_version != I.tree_version || I.wire_lod != I.lod ||
-                        I.wire_view_gen != I.view_lod_token())) {
+                        I.wire_view_gen != I.view_lod_token() || I.wire_cull_gen != I.cull_token())) {
         I.sync_all();  // frames in flight read the old edge list; slot 0's stream holds the tree edits the new one must see
         const mnv_tree_view dv = I.march_tree().device_view();
         const int rc = I.wire ? mnv_wireframe_update(I.wire, &dv, options.grid_max_depth, I.stream)
@@ -875,6 +929,7 @@ void VolumeRenderer::update_shared(const FramePlan &P) {
         I.wire_version = I.tree_version;
         I.wire_lod = I.lod;
         I.wire_view_gen = I.view_lod_token();
+        I.wire_cull_gen = I.cull_token();
         I.can_reuse_results = false;  // the samples of the last guided frame were limited by the previous grid
     }
     if (P.kind == FramePlan::AA && (aa_samples != I.aa_k || aa_filter != I.aa_filter)) {

@@ -169,6 +169,16 @@ struct VolumeRenderer {
     // focal length that is not finite, focal_px <= 0, pixels negative or not finite, min_depth < 1, max_depth < min_depth.
     void set_view_lod(const std::vector<mnv_lod_view> &views, float pixels, int min_depth = 1, int max_depth = 23);
     bool view_lod() const;
+    // Culling to a pose set.  An empty list (the default): render() is what it is without this call.  Otherwise every frame marches
+    // N3Tree::make_culled(cameras, options, weight_thresh) of the tree that was set: the tree without the leaves no ray of the listed
+    // cameras' frames weights above weight_thresh, chunks left all-empty collapsed.  The CALLER names the poses, as with set_view_lod; a
+    // frame from another pose shows what the listed ones left.  Same frame kinds as set_lod; the tree is built at the first frame that
+    // needs it, kept until the cameras, the threshold or the march options (step_size, sigma_thresh, stop_thresh, render_bbox) change, and
+    // dropped where set_lod's trees are.  Refused by render() (StatusError, MNV_E_INVALID) with options.use_splitting,
+    // options.use_guided_sampling, set_ranks, and set_lod(D > 0) or set_view_lod at the same time.  Refused here: a threshold that is
+    // negative or not finite, a camera without pixels or of more than 2^22.
+    void set_cull(const std::vector<mnv_camera> &cameras, float weight_thresh = 0.f);
+    bool cull() const;
     // Fit the level of detail to the full tree (N3Tree::fit_to; mnv_n3tree_fit_to_tree).  params.iterations == 0 or an empty list (the
     // default): nothing changes.  Otherwise every tree set_lod / set_view_lod builds from now on is fitted, right after it is built, to the
     // frames of the tree that was set at the listed cameras; trees built before are dropped, so the next frame builds and fits anew.
