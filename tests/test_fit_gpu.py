@@ -2,7 +2,10 @@
 restatement of the contract (tests/fit_ref.py): the forward of mnv_rays_grad is mnv_render_rays_accel's bit for bit; the accumulator words
 and the sums equal the restatement word for word -- with a basis mask, rotated view directions, ray limits and excluded rays -- in any ray
 order and image layout and under full contention; both row kernels are exact; fit_to reproduces the restatement's loss sequence and rows;
-the loss falls at every step; refusals come before any launch.  No tolerance anywhere."""
+the loss falls at every step; refusals come before any launch.  The edge cases: SH16 / SH25 rows (the whole wavefront per sample, a second
+trip over the columns), scales that differ per axis, skipped rays with the clamp and NaN terms, links that leave the tree, padded rows with
+eight lanes per sample, more tiles than workgroups, ragged tiles.  The descent's limit of 23 levels is reached by no test: no ray list was
+found for which the restatement reports a ray broken by it.  No tolerance anywhere."""
 import numpy as np
 import pytest
 
@@ -21,7 +24,7 @@ def _dev(torch, a):
 
 def _grad(mnv, torch, tree, opt, o, d, target, tmax=None, acc=None, want_rgba=True):
     """mnv_rays_grad on host arrays -> (rgba or None, acc int64 [capacity * 8, data_dim], sums dict); acc: a device tensor to add into"""
-    v = tree.device_view()
+    v = tree if isinstance(tree, mnv.TreeView) else tree.device_view()
     n = int(np.prod(o.shape[:-1]))
     if acc is None:
         acc = torch.zeros((v.capacity * 8, v.data_dim), dtype=torch.int64, device="cuda")
@@ -41,13 +44,13 @@ def truth(mnv):
 
     def get(name):
         if name not in cache:
-            tree = cases.make_tree(mnv, fit_cases.TREES[name])
+            tree = cases.make_tree(mnv, fit_cases.tree_spec(name))
             T = fit_ref.tree_of(mnv, tree)
             opt = fit_cases.make_options(mnv, name)
             L = fit_cases.ray_list(mnv, name)
-            rgba, acc, sums, _ = fit_ref.rays_grad(T, opt, L["o"], L["d"], L["target"], L["tmax"])
+            rgba, acc, sums, fw = fit_ref.rays_grad(T, opt, L["o"], L["d"], L["target"], L["tmax"])
             tree.move_to_device()
-            cache[name] = dict(tree=tree, T=T, opt=opt, L=L, rgba=rgba, acc=acc, sums=sums)
+            cache[name] = dict(tree=tree, T=T, opt=opt, L=L, rgba=rgba, acc=acc, sums=sums, fw=fw)
         return cache[name]
 
     return get
@@ -105,6 +108,152 @@ def test_full_contention_on_a_depth_one_tree(mnv, torch_gpu, truth):
     assert np.bincount(np.concatenate([b["vox"] for b in fw["batches"]])).max() >= 1000
     _, acc, sums = _grad(mnv, torch, t["tree"], t["opt"], o, d, target, want_rgba=False)
     assert np.array_equal(acc, want) and sums == want_sums
+
+
+# ---- the edge cases (fit_cases.EDGE_NAMES and the inputs built next to them): wide rows, scales that differ per axis, skipped rays, links
+# that leave the tree, padded rows, more tiles than workgroups, ragged tiles.  tests/test_fit_ref.py says what each input contains.
+
+@pytest.mark.parametrize("name", fit_cases.EDGE_NAMES)
+def test_edge_cases_equal_the_restatement_word_for_word(mnv, torch_gpu, truth, name):
+    torch = torch_gpu
+    t = truth(name)
+    L = t["L"]
+    rgba, acc, sums = _grad(mnv, torch, t["tree"], t["opt"], L["o"], L["d"], L["target"], L["tmax"])
+    want = torch.full((L["o"].shape[0], 4), float("nan"), dtype=torch.float32, device="cuda")
+    mnv.render_rays_accel(t["tree"].accel, _dev(torch, L["o"]), _dev(torch, L["d"]), t["opt"], rgba=want, tmax=_dev(torch, L["tmax"]))
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(rgba), bits(want.cpu().numpy())) and np.array_equal(bits(rgba), bits(t["rgba"]))
+    assert sums == t["sums"] and t["sums"]["n_samples"] >= 500
+    bad = acc != t["acc"]
+    assert not bad.any(), f"{int(bad.sum())} of {int((t['acc'] != 0).sum())} non-zero words differ; first at {np.argwhere(bad)[:3].tolist()}"
+    # the same rays as a 20 x 32 image
+    rgba, acc, sums = _grad(mnv, torch, t["tree"], t["opt"], L["o"].reshape(20, 32, 3), L["d"].reshape(20, 32, 3), L["target"].reshape(20, 32, 4),
+                            L["tmax"].reshape(20, 32))
+    assert np.array_equal(acc, t["acc"]) and sums == t["sums"] and np.array_equal(bits(rgba), bits(t["rgba"]))
+
+
+@pytest.mark.parametrize("name", ["sh4_d4_aniso", "sh25_d3"])
+def test_skipped_rays_the_clamp_and_nan_terms(mnv, torch_gpu, truth, name):
+    """targets far outside [0, 1], infinite and NaN (fit_cases.skip_targets): rays with a non-finite g are skipped and still get their
+    pixel, terms beyond +-32 saturate, NaN terms read 0"""
+    t = truth(name)
+    L = t["L"]
+    tg = fit_cases.skip_targets(L["target"])
+    want, want_sums = fit_ref.backward(t["T"], t["opt"], t["fw"], tg)
+    assert want_sums["n_skipped"] >= 10 and (np.abs(want) >= 2 ** 37).any()
+    rgba, acc, sums = _grad(mnv, torch_gpu, t["tree"], t["opt"], L["o"], L["d"], tg, L["tmax"])
+    assert sums == want_sums
+    bad = acc != want
+    assert not bad.any(), f"{int(bad.sum())} words differ; first at {np.argwhere(bad)[:3].tolist()}"
+    assert np.array_equal(bits(rgba), bits(t["rgba"]))
+
+
+def test_nan_terms_read_zero(mnv, torch_gpu, truth):
+    """fit_cases.nan_terms: RGBA rows with colours up to 64 against targets of +-3e38: g is finite, products overflow to infinities of
+    opposite sign, the density term is NaN and adds nothing (tests/test_fit_ref.py counts the NaN terms of this input)"""
+    torch = torch_gpu
+    t = truth("rgba_d4")
+    L = t["L"]
+    U, tg = fit_cases.nan_terms(t["T"], L["target"])
+    want_rgba, want, want_sums, _ = fit_ref.rays_grad(U, t["opt"], L["o"], L["d"], tg, L["tmax"])
+    assert want_sums["n_skipped"] == 0 and (np.abs(want) >= 2 ** 37).any()
+    v, data_t, child_t = fit_cases.hand_view(mnv, torch, U)
+    rgba, acc, sums = _grad(mnv, torch, v, t["opt"], L["o"], L["d"], tg, L["tmax"])
+    assert sums == want_sums and np.array_equal(acc, want) and np.array_equal(bits(rgba), bits(want_rgba))
+
+
+def test_links_that_leave_the_tree_skip_their_rays(mnv, torch_gpu, truth):
+    """fit_cases.broken_links: links to chunk 0, to chunks at and above the view's capacity (all inside the allocated arrays): the rays
+    that meet one are skipped, the others' words are the restatement's"""
+    torch = torch_gpu
+    t = truth(fit_cases.BROKEN["tree"])
+    T, L = fit_cases.broken_links(t["T"], t["L"])
+    want_rgba, want, want_sums, fw = fit_ref.rays_grad(T, t["opt"], L["o"], L["d"], L["target"], L["tmax"])
+    assert want_sums["n_skipped"] >= 20 and want.shape[0] == fit_cases.BROKEN["capacity"] * 8
+    v, data_t, child_t = fit_cases.hand_view(mnv, torch, T)
+    assert v.capacity == fit_cases.BROKEN["capacity"] and child_t.numel() == t["T"]["capacity"] * 8 > v.capacity * 8
+    acc = torch.zeros((child_t.numel(), T["data_dim"]), dtype=torch.int64, device="cuda")       # rows for every allocated chunk
+    rgba, acc, sums = _grad(mnv, torch, v, t["opt"], L["o"], L["d"], L["target"], L["tmax"], acc=acc)
+    assert sums == want_sums
+    assert np.array_equal(acc[:want.shape[0]], want) and not acc[want.shape[0]:].any()
+    assert np.array_equal(bits(rgba), bits(want_rgba))
+
+
+def test_padded_rows_and_the_scatter_group_of_eight(mnv, torch_gpu, truth):
+    """SH1 rows of data_dim 7 (fit_cases.padded_rows): eight lanes per sample, the padding columns 3 .. 5 get no word; then a step on them"""
+    torch = torch_gpu
+    t = truth("sh1_d4")
+    L = t["L"]
+    P = fit_cases.padded_rows(t["T"])
+    want_rgba, want, want_sums, _ = fit_ref.rays_grad(P, t["opt"], L["o"], L["d"], L["target"], L["tmax"])
+    v, data_t, child_t = fit_cases.hand_view(mnv, torch, P)
+    acc_t = torch.zeros((P["capacity"] * 8, 7), dtype=torch.int64, device="cuda")
+    rgba, acc, sums = _grad(mnv, torch, v, t["opt"], L["o"], L["d"], L["target"], L["tmax"], acc=acc_t)
+    assert sums == want_sums and np.array_equal(acc, want) and np.array_equal(bits(rgba), bits(want_rgba))
+    assert not acc[:, 3:6].any() and acc[:, :3].any() and acc[:, 6].any()
+    master = mnv.rows_master_init(data_t)
+    mnv.rows_sgd_step(data_t, master, acc_t, 7, 1.0, 20.0)
+    torch.cuda.synchronize()
+    want_d, want_m, want_a = P["data"].copy(), fit_ref.master_init(P["data"]), want.copy()
+    fit_ref.sgd_step(want_d, want_m, want_a, 1.0, 20.0)
+    got_d = data_t.cpu().numpy().view(np.uint16)
+    assert np.array_equal(got_d, want_d) and np.array_equal(bits(master.cpu().numpy()), bits(want_m)) and not acc_t.cpu().numpy().any()
+    # rows change only where acc had words: the rewrite of a touched row's other columns is binary16(master), the finite value it held
+    changed = got_d != P["data"]
+    assert changed.any() and not changed[want == 0].any() and not changed[:, 3:6].any()
+
+
+@pytest.mark.parametrize("name", ["sh9_d4", "sh25_d3"])
+def test_more_tiles_than_workgroups(mnv, torch_gpu, truth, name):
+    """420 copies of the case's 640 rays and its first 37 again: 268,837 rays in 4201 flat tiles, more than the 4096 workgroups of the
+    launch, so workgroups walk on to a second tile, the last of which has 37 rays; and the 268,800 as a 32 x 8400 image (4 x 1050 = 4200
+    tiles of 8 x 8).  The words are integers: 420 x the restatement's words of the list plus those of its first 37 rays, whatever
+    workgroup adds them.  Headroom: the busiest word takes fewer than 640 x 420 = 2.7e5 terms of at most 2^37 each, far below 2^62; the
+    ray count is below the call's limit of 2^22."""
+    torch = torch_gpu
+    t = truth(name)
+    L = t["L"]
+    copies, tail = 420, 37
+    many = {k: np.concatenate([np.tile(a, (copies,) + (1,) * (a.ndim - 1)), a[:tail]]) for k, a in L.items()}
+    assert many["o"].shape[0] == 268837 and (268837 + 63) // 64 == 4201
+    _, acc_tail, sums_tail, _ = fit_ref.rays_grad(t["T"], t["opt"], L["o"][:tail], L["d"][:tail], L["target"][:tail], L["tmax"][:tail])
+    assert sums_tail["n_samples"] > 0 and sums_tail["n_rays"] < tail
+    rgba, acc, sums = _grad(mnv, torch, t["tree"], t["opt"], many["o"], many["d"], many["target"], many["tmax"])
+    assert sums == {k: copies * t["sums"][k] + sums_tail[k] for k in sums}
+    assert np.array_equal(acc, copies * t["acc"] + acc_tail)
+    assert np.array_equal(bits(rgba), bits(np.concatenate([np.tile(t["rgba"], (copies, 1)), t["rgba"][:tail]])))
+    n = copies * 640
+    rgba, acc, sums = _grad(mnv, torch, t["tree"], t["opt"], many["o"][:n].reshape(8400, 32, 3), many["d"][:n].reshape(8400, 32, 3),
+                            many["target"][:n].reshape(8400, 32, 4), many["tmax"][:n].reshape(8400, 32))
+    assert sums == {k: copies * x for k, x in t["sums"].items()} and np.array_equal(acc, copies * t["acc"])
+    assert np.array_equal(bits(rgba), bits(np.tile(t["rgba"], (copies, 1))))
+
+
+@pytest.mark.parametrize("shape", [(13, 7), (7, 13), (65,)], ids=["7x13", "13x7", "flat65"])
+def test_ragged_tiles_write_nothing_beside_their_rays(mnv, torch_gpu, truth, shape):
+    """images narrower than a tile and of no multiple of 8 (7 wide x 13 high, 13 x 7), a flat list that ends one ray into its second tile:
+    the restatement's words on top of what acc held, pixels for the listed rays and not one float behind them"""
+    torch = torch_gpu
+    t = truth("sh9_d4")
+    n = int(np.prod(shape))
+    L = {k: a[:n] for k, a in t["L"].items()}
+    want_rgba, want, want_sums, _ = fit_ref.rays_grad(t["T"], t["opt"], L["o"], L["d"], L["target"], L["tmax"])
+    assert want_sums["n_samples"] >= 20 and np.count_nonzero(want) >= 20
+    v = t["tree"].device_view()
+    before = np.random.default_rng(n).integers(-(1 << 40), 1 << 40, size=want.shape)
+    acc = _dev(torch, before)
+    guard = shape[-1]                                                                  # one more row of pixels
+    rgba = torch.full((n + guard, 4), float("nan"), dtype=torch.float32, device="cuda")
+    sums = torch.zeros(8, dtype=torch.int64, device="cuda")
+    o, d, tg = (_dev(torch, L[k].reshape(shape + (c,))) for k, c in (("o", 3), ("d", 3), ("target", 4)))
+    mnv.rays_grad(v, o, d, tg, t["opt"], acc, sums, rgba=rgba, tmax=_dev(torch, L["tmax"].reshape(shape)))
+    torch.cuda.synchronize()
+    got, nan = rgba.cpu().numpy(), torch.full((guard, 4), float("nan"), dtype=torch.float32).numpy()
+    assert np.array_equal(bits(got[:n]), bits(want_rgba)) and np.array_equal(bits(got[n:]), bits(nan))
+    assert dict(zip(fit_ref.FIT_SUMS, sums.cpu().numpy()[:5].tolist())) == want_sums and not sums.cpu().numpy()[5:].any()
+    got_acc = acc.cpu().numpy()
+    assert np.array_equal(got_acc - before, want)
+    assert np.array_equal(got_acc[~want.any(axis=1)], before[~want.any(axis=1)])        # rows of voxels no ray reached keep their words
 
 
 def test_row_kernels_are_exact(mnv, torch_gpu):

@@ -2,7 +2,9 @@
 every test ray; (b) the contract's formulas, evaluated in binary64 on the recorded sample geometry, are the derivative of the binary64
 loss (central differences, whole gradient vectors by relative L2 norm); (c) the binary32 contract words stay within a measured bound of
 that binary64 gradient; (d) the cases contain what they are meant to: early stops, hits that do not stop, misses, degenerate rays, leaves
-at several depths, a voxel fed by 64 rays and more.  tests/test_fit_gpu.py holds the device against the same restatement."""
+at several depths, a voxel fed by 64 rays and more; (e) the same four for the edge cases of tests/fit_cases.py -- SH16 / SH25 rows, scales
+that differ per axis -- and what the inputs of the edge tests contain: skipped rays, saturated terms, broken links, padded rows.
+tests/test_fit_gpu.py holds the device against the same restatement."""
 import numpy as np
 import pytest
 
@@ -20,6 +22,10 @@ FD_BOUND = 1e-6
 # 1.39e-7 (sh1_d4; the others 1.0e-8 .. 1.17e-7) -- binary32 rounding of a few dozen operations per term (2^-24 = 6e-8 each) plus the
 # 2^-33 of the fixed-point rounding.  Rounding differs per scene, hence 4 x the maximum.
 F32_BOUND = 4 * 1.39e-7
+# (c) for fit_cases.EDGE_NAMES, measured here with their own options: 1.86e-7 (sh16_d3_aniso), 1.63e-7 (sh25_d3), 3.07e-8 (sh4_d4_aniso).
+# The wide rows sum 16 and 25 products per channel before the sigmoid, hence more rounding per term than the six above; the same margin
+# for the same reason.
+EDGE_F32_BOUND = 4 * 1.86e-7
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +35,7 @@ def truth(mnv):
 
     def get(name):
         if name not in cache:
-            tree = cases.make_tree(mnv, fit_cases.TREES[name])
+            tree = cases.make_tree(mnv, fit_cases.tree_spec(name))
             T = fit_ref.tree_of(mnv, tree)
             opt = fit_cases.make_options(mnv, name)
             L = fit_cases.ray_list(mnv, name)
@@ -40,7 +46,7 @@ def truth(mnv):
     return get
 
 
-@pytest.mark.parametrize("name", fit_cases.NAMES)
+@pytest.mark.parametrize("name", fit_cases.NAMES + fit_cases.EDGE_NAMES)
 def test_forward_equals_the_oracle(mnv, orc, truth, name):
     t = truth(name)
     L = t["L"]
@@ -70,7 +76,7 @@ def _fd_ray(t, i):
     return an, (loss[0] - loss[1]) / (2.0 * h)
 
 
-@pytest.mark.parametrize("name", fit_cases.NAMES)
+@pytest.mark.parametrize("name", fit_cases.NAMES + fit_cases.EDGE_NAMES)
 def test_contract_formulas_are_the_derivative(truth, name):
     t = truth(name)
     fw = t["fw"]
@@ -93,6 +99,89 @@ def test_float32_words_against_the_float64_gradient(truth, name):
     err = np.linalg.norm(g32 - g64) / np.linalg.norm(g64)
     print(f"{name}: |grad| = {np.linalg.norm(g64):.4g}, relative L2 distance of the binary32 words = {err:.3g}")
     assert err < F32_BOUND
+
+
+@pytest.mark.parametrize("name", fit_cases.EDGE_NAMES)
+def test_float32_words_against_the_float64_gradient_on_the_edge_cases(truth, name):
+    t = truth(name)
+    g64 = fit_ref.gradient64(t["T"], t["opt"], t["fw"], t["L"]["target"])
+    g32 = t["acc"].astype(np.float64) / fit_ref.Q32
+    err = np.linalg.norm(g32 - g64) / np.linalg.norm(g64)
+    print(f"{name}: |grad| = {np.linalg.norm(g64):.4g}, relative L2 distance of the binary32 words = {err:.3g}")
+    assert err < EDGE_F32_BOUND
+
+
+def test_edge_cases_contain_what_they_are_meant_to(truth):
+    for name in fit_cases.EDGE_NAMES:
+        t = truth(name)
+        fw, L, s, T = t["fw"], t["L"], t["sums"], t["T"]
+        inc = L["target"][:, 3] != 0
+        assert s["n_stopped"] >= 5, name                                              # early-stopped rays
+        assert int((inc & ~fw["stopped"] & (fw["n_dense"] > 0)).sum()) >= 5, name       # hits that do not stop
+        assert s["n_skipped"] == 0 and s["n_rays"] == int(inc.sum()) and s["n_samples"] >= 500
+        n_ds = np.unique(fw["R"]["delta_scale"][fw["in_bbox"]]).size
+        print(f"{name}: sums {s}, {n_ds} distinct delta_scale, {np.count_nonzero(t['acc'])} non-zero words")
+        if name.endswith("_aniso"):
+            assert n_ds >= 300, name                                                   # delta_scale varies with the direction
+        assert T["data_dim"] == {"sh16_d3_aniso": 49, "sh25_d3": 76, "sh4_d4_aniso": 13}[name]
+        if name == "sh25_d3":                                                          # the second trip of the column loop has work to do
+            assert np.count_nonzero(t["acc"][:, 64:75]) >= 500 and t["acc"][:, 75].any()
+            assert all(t["acc"][:, c].any() for c in range(76))
+        if name == "sh16_d3_aniso":                                                    # masked coefficients get no term, every other column does
+            masked = np.r_[[k * 16 + j for k in range(3) for j in (0, 1, 12, 13, 14, 15)]]
+            assert not t["acc"][:, masked].any()
+            assert all(t["acc"][:, c].any() for c in range(49) if c not in masked)
+
+
+def test_edge_inputs_contain_what_they_are_meant_to(mnv, truth, monkeypatch):
+    """the skipped rays, the clamp and the NaN terms; links that leave the tree; padded rows: what the restatement says of the inputs that
+    tests/test_fit_gpu.py and tests/test_visibility_gpu.py hold the device to"""
+    import visibility_ref
+
+    clamp32 = fit_ref.q32
+    for name in ("sh4_d4_aniso", "sh25_d3"):
+        t = truth(name)
+        tg = fit_cases.skip_targets(t["L"]["target"])
+        acc, s = fit_ref.backward(t["T"], t["opt"], t["fw"], tg)
+        n_sat = int((np.abs(acc) >= 2 ** 37).sum())
+        print(f"{name}: {s}, {n_sat} words at +-2^37")
+        assert s["n_skipped"] >= 10 and n_sat >= 1 and s["n_rays"] > 500, name
+        assert s["se_q32"] >= 10 * 2 ** 37                                            # the squared error saturates the same way
+        # terms do meet the clamp: a wider clamp would give other words (a word of 2^37 could also be a sum of smaller terms)
+        monkeypatch.setattr(fit_ref, "q32", lambda x: np.where(np.abs(x) > 32, np.sign(x) * 2 ** 38, clamp32(x)).astype(np.int64))
+        wide, _ = fit_ref.backward(t["T"], t["opt"], t["fw"], tg)
+        monkeypatch.undo()
+        assert (wide != acc).any() and np.array_equal(fit_ref.backward(t["T"], t["opt"], t["fw"], tg)[0], acc)
+    # NaN terms: none of the targets above makes one (SH colours stay in [0, 1]); fit_cases.nan_terms does, on RGBA rows with large
+    # colours.  Counted where they reach q32; a q32 that read a NaN as anything but 0 would give other words.
+    t = truth("rgba_d4")
+    U, tg = fit_cases.nan_terms(t["T"], t["L"]["target"])
+    fw = fit_ref.forward(U, t["opt"], t["L"]["o"], t["L"]["d"], t["L"]["tmax"])
+    n_nan = []
+    monkeypatch.setattr(fit_ref, "q32", lambda x: (n_nan.append(int(np.isnan(x).sum())), clamp32(x))[1])
+    acc, s = fit_ref.backward(U, t["opt"], fw, tg)
+    monkeypatch.setattr(fit_ref, "q32", lambda x: np.where(np.isnan(x), 1 << 32, clamp32(x)).astype(np.int64))
+    other, _ = fit_ref.backward(U, t["opt"], fw, tg)
+    monkeypatch.undo()
+    print(f"nan_terms: {sum(n_nan)} NaN terms, {s}")
+    assert sum(n_nan) >= 10 and s["n_skipped"] == 0 and (other != acc).any() and np.array_equal(other[:, :3], acc[:, :3])
+    # links: rays break at the links to chunk 0, at the capacity and -- the inside rays -- at chunk 151 itself, the first one outside
+    t = truth(fit_cases.BROKEN["tree"])
+    T, L = fit_cases.broken_links(t["T"], t["L"])
+    _, _, s, fw = fit_ref.rays_grad(T, t["opt"], L["o"], L["d"], L["target"], L["tmax"])
+    n_in = fit_cases.BROKEN["inside"]
+    print(f"links: {int(fw['broken'].sum())} rays broken, {s}")
+    assert s["n_skipped"] >= 20 + n_in and fw["broken"][-n_in:].all() and 200 < s["n_rays"] and s["n_samples"] > 200
+    one_more = fit_ref.forward(dict(T, capacity=T["capacity"] + 1), t["opt"], L["o"], L["d"], L["tmax"])
+    assert int((fw["broken"] & ~one_more["broken"]).sum()) >= 20                       # (>= capacity, not > capacity, is what breaks those)
+    _, vs, _ = visibility_ref.rays_visibility(T, t["opt"], L["o"], L["d"], L["tmax"])
+    assert vs["n_skipped"] == int(fw["broken"].sum()) >= s["n_skipped"]
+    # padded rows: the padding columns get no word, the others the words of the unpadded tree
+    t = truth("sh1_d4")
+    P = fit_cases.padded_rows(t["T"])
+    rgba, acc, s, _ = fit_ref.rays_grad(P, t["opt"], t["L"]["o"], t["L"]["d"], t["L"]["target"], t["L"]["tmax"])
+    assert s == t["sums"] and np.array_equal(bits(rgba), bits(t["rgba"]))
+    assert not acc[:, 3:6].any() and np.array_equal(acc[:, [0, 1, 2, 6]], t["acc"]) and t["acc"].any()
 
 
 def test_cases_contain_what_they_are_meant_to(truth):

@@ -1,7 +1,8 @@
 """Culling on the device (csrc/mnv_visibility.hip: mnv_rays_visibility, mnv_tree_cull; N3Tree.make_culled) against tests/visibility_ref.py,
 the numpy restatement of the contract in include/mnv.h: the words of wmax and the sums equal the restatement word for word in any ray
-order, image layout, split over calls, under full contention and on top of earlier contents; mnv_tree_cull equals it byte for byte on
-hand-made words (NaN patterns, ties, renumbered trees, unreached chunks, chains); the cut tree's frames equal the oracle's three ways; at
+order, image layout, split over calls, under full contention and on top of earlier contents -- also on trees whose scale differs per axis,
+with links that leave the tree, with more tiles than workgroups and with ragged tiles (the edge cases of tests/fit_cases.py);
+mnv_tree_cull equals it byte for byte on hand-made words (NaN patterns, ties, renumbered trees, unreached chunks, chains); the cut tree's frames equal the oracle's three ways; at
 threshold 0 the culled rows change no listed ray; refusals come before any launch.  No tolerance but the one measured bound on the cut
 tree's frames (tests/test_visibility_ref.py)."""
 import ctypes as C
@@ -111,6 +112,69 @@ def test_4096_copies_of_one_ray_onto_the_same_words(mnv, torch_gpu, truth):
     want, want_sums, _ = ref.rays_visibility(t["T"], t["opt"], o[:1], d[:1], tmax[:1])
     wmax, sums = _vis(mnv, torch_gpu, t["tree"].device_view(), t["opt"], o, d, tmax)
     assert np.array_equal(wmax, want) and sums == {k: 4096 * x for k, x in want_sums.items()} and np.count_nonzero(want) >= 3
+
+
+# ---- the edge cases of tests/fit_cases.py: scales that differ per axis, wide rows, links that leave the tree, more tiles than workgroups,
+# ragged tiles.  tests/test_fit_ref.py and tests/test_visibility_ref.py say what each input contains.
+
+@pytest.mark.parametrize("name", fit_cases.EDGE_NAMES)
+def test_edge_cases_equal_the_restatement_word_for_word(mnv, torch_gpu, truth, name):
+    t = truth(name)
+    Lr, v = t["L"], t["tree"].device_view()
+    wmax, sums = _vis(mnv, torch_gpu, v, t["opt"], Lr["o"], Lr["d"], Lr["tmax"])
+    assert sums == t["sums"] and t["sums"]["n_samples"] >= 500 and np.count_nonzero(t["wmax"]) >= 40
+    bad = np.nonzero(wmax != t["wmax"])[0]
+    assert bad.size == 0, f"{bad.size} of {int((t['wmax'] != 0).sum())} non-zero words differ; first at {bad[:4].tolist()}"
+    wmax, sums = _vis(mnv, torch_gpu, v, t["opt"], Lr["o"].reshape(20, 32, 3), Lr["d"].reshape(20, 32, 3), Lr["tmax"].reshape(20, 32))
+    assert np.array_equal(wmax, t["wmax"]) and sums == t["sums"]
+
+
+def test_links_that_leave_the_tree_skip_their_rays(mnv, torch_gpu, truth):
+    """fit_cases.broken_links: links to chunk 0, to chunks at and above the view's capacity (all inside the allocated arrays) -- chunk 151,
+    the first one outside, among them: a ray that meets one adds nothing, the others' words are the restatement's"""
+    torch = torch_gpu
+    t = truth(fit_cases.BROKEN["tree"])
+    T, Lr = fit_cases.broken_links(t["T"], t["L"])
+    want, want_sums, fw = ref.rays_visibility(T, t["opt"], Lr["o"], Lr["d"], Lr["tmax"])
+    n_in = fit_cases.BROKEN["inside"]
+    assert want_sums["n_skipped"] >= 20 + n_in and fw["broken"][-n_in:].all() and np.count_nonzero(want) >= 100
+    v, data_t, child_t = fit_cases.hand_view(mnv, torch, T)
+    assert v.capacity == fit_cases.BROKEN["capacity"] and child_t.numel() > v.capacity * 8
+    words = torch.zeros((child_t.numel(),), dtype=torch.int32, device="cuda")          # a word for every allocated voxel
+    wmax, sums = _vis(mnv, torch, v, t["opt"], Lr["o"], Lr["d"], Lr["tmax"], wmax=words)
+    assert sums == want_sums
+    assert np.array_equal(wmax[:want.size], want) and not wmax[want.size:].any()
+
+
+@pytest.mark.parametrize("name", ["sh9_d4", "sh25_d3"])
+def test_more_tiles_than_workgroups(mnv, torch_gpu, truth, name):
+    """420 copies of the case's 640 rays and its first 37 again: 268,837 rays in 4201 flat tiles, more than the 4096 workgroups of the
+    launch, so workgroups walk on to a second tile, the last of which has 37 rays; and the 268,800 as a 32 x 8400 image (4200 tiles of
+    8 x 8).  The words are maxima: unchanged.  The sums multiply."""
+    t = truth(name)
+    Lr, v = t["L"], t["tree"].device_view()
+    copies, tail = 420, 37
+    o, d, tmax = (np.concatenate([np.tile(a, (copies,) + (1,) * (a.ndim - 1)), a[:tail]]) for a in (Lr["o"], Lr["d"], Lr["tmax"]))
+    assert o.shape[0] == 268837
+    _, sums_tail, _ = ref.rays_visibility(t["T"], t["opt"], Lr["o"][:tail], Lr["d"][:tail], Lr["tmax"][:tail])
+    assert sums_tail["n_samples"] > 0
+    wmax, sums = _vis(mnv, torch_gpu, v, t["opt"], o, d, tmax)
+    assert np.array_equal(wmax, t["wmax"]) and sums == {k: copies * t["sums"][k] + sums_tail[k] for k in sums}
+    n = copies * 640
+    wmax, sums = _vis(mnv, torch_gpu, v, t["opt"], o[:n].reshape(8400, 32, 3), d[:n].reshape(8400, 32, 3), tmax[:n].reshape(8400, 32))
+    assert np.array_equal(wmax, t["wmax"]) and sums == {k: copies * x for k, x in t["sums"].items()}
+
+
+@pytest.mark.parametrize("shape", [(13, 7), (7, 13), (65,)], ids=["7x13", "13x7", "flat65"])
+def test_ragged_tiles(mnv, torch_gpu, truth, shape):
+    """images narrower than a tile and of no multiple of 8 (7 wide x 13 high, 13 x 7), a flat list that ends one ray into its second tile"""
+    t = truth("sh9_d4")
+    n = int(np.prod(shape))
+    o, d, tmax = t["L"]["o"][:n], t["L"]["d"][:n], t["L"]["tmax"][:n]
+    want, want_sums, _ = ref.rays_visibility(t["T"], t["opt"], o, d, tmax)
+    assert want_sums["n_rays"] == n and want_sums["n_samples"] >= 20
+    wmax, sums = _vis(mnv, torch_gpu, t["tree"].device_view(), t["opt"], o.reshape(shape + (3,)), d.reshape(shape + (3,)), tmax.reshape(shape))
+    assert np.array_equal(wmax, want) and sums == want_sums
 
 
 # ---------------------------------------------------------------------------------------------------- mnv_tree_cull

@@ -37,7 +37,7 @@ def scene(mnv, name):
     """(tree, options, ray list dict(o, d, tmax)) of a case"""
     if name == "wall":
         return vc.wall_tree(mnv), mnv.RenderOptions.defaults(), vc.wall_ray_list(mnv)
-    return cases.make_tree(mnv, fit_cases.TREES[name]), fit_cases.make_options(mnv, name), fit_cases.ray_list(mnv, name)
+    return cases.make_tree(mnv, fit_cases.tree_spec(name)), fit_cases.make_options(mnv, name), fit_cases.ray_list(mnv, name)
 
 
 @pytest.fixture(scope="module")
@@ -73,7 +73,7 @@ def _oracle_rays_of(name, n):
     return np.arange(n) if name == "wall" else np.r_[0:n_frame, n_frame + 4:n]
 
 
-@pytest.mark.parametrize("name", vc.NAMES + ["wall"])
+@pytest.mark.parametrize("name", vc.NAMES + ["wall"] + fit_cases.EDGE_NAMES)
 def test_the_weights_are_the_oracles(mnv, orc, truth, name):
     t = truth(name)
     T, L = t["T"], t["L"]
@@ -98,6 +98,21 @@ def test_the_weights_are_the_oracles(mnv, orc, truth, name):
     want, _ = rays_ref.oracle_rays(orc, orc.tree_from_view(host.host_view()), L["o"][sel], L["d"][sel], opt, None if L["tmax"] is None else L["tmax"][sel])
     assert np.array_equal(bits(fw1["rgba"][sel]), bits(want))             # ... and the oracle's pixel
     assert t["sums"]["n_skipped"] == 0 and t["sums"]["n_rays"] == L["o"].shape[0] and t["sums"]["n_samples"] == sum(b["ray"].size for b in t["fw"]["batches"])
+
+
+@pytest.mark.parametrize("name", fit_cases.EDGE_NAMES)
+def test_the_forward_is_the_fitting_restatements_on_the_edge_cases(mnv, truth, name):
+    """wide rows, scales that differ per axis: the march under the weights is fit_ref's own, which tests/test_fit_ref.py holds against the
+    oracle on these cases, and the words are the maxima of its weights"""
+    t = truth(name)
+    L = t["L"]
+    fw = fit_ref.forward(t["T"], t["opt"], L["o"], L["d"], L["tmax"])
+    assert np.array_equal(bits(fw["rgba"]), bits(t["fw"]["rgba"])) and len(fw["batches"]) == len(t["fw"]["batches"])
+    want = np.zeros(t["T"]["capacity"] * 8, np.float32)
+    for b in fw["batches"]:
+        np.maximum.at(want, b["vox"], b["w"])
+    assert np.array_equal(t["wmax"], want.view(np.uint32)) and np.count_nonzero(want) >= 40
+    assert t["sums"] == dict(n_rays=L["o"].shape[0], n_stopped=int(fw["stopped"].sum()), n_samples=int(fw["n_dense"].sum()), n_skipped=0)
 
 
 def test_the_comparison_with_the_threshold_is_strict(truth):
