@@ -1303,6 +1303,78 @@ int mnv_tree_cull(const mnv_tree_view *device_tree, const uint32_t *wmax, float 
                   uint8_t *keep_out /* device [capacity] */, int64_t kept_at_depth[24] /* HOST */, mnv_cull_counts *counts /* HOST */,
                   void *hip_stream);
 
+/* ------------------------------------------------ a tree from a coloured point cloud
+ * Everything above works on a tree that exists.  mnv_point_tree_* make one from points (a photogrammetry or lidar cloud): occupancy at one
+ * depth D, the chunks above it, a mean colour per occupied voxel and one density for all of them, as an ordinary tree in the reference's
+ * arrays -- the start mnv_n3tree_fit refines.  N == 2; depths as above (the root chunk's voxels have depth 1).
+ *
+ * Use: create, add any number of times (device arrays), finish (HOST stats; their chunk counts size the outputs), write.  add after finish
+ * is allowed, the next finish answers for all points so far; write before finish, or after an add that no finish followed, is
+ * MNV_E_INVALID.  add and finish wait for hip_stream (they read counts back to size their lists); write is asynchronous on it.  Two handles
+ * share nothing.
+ *
+ * Contract (binary32 where floats appear, one operation at a time in the stated order, no contraction, subnormals kept; everything after
+ * the voxel of a point is integer arithmetic, so no float sum and no atomic order decides an output byte).
+ *   Voxel of a point p.  q_k = offset[k] + scale[k] * p[k] (the product, then the sum: mnv_tree_select_cut's rule).  The point is DROPPED,
+ *     and counted in stats.dropped, when a p[k] or q_k is not finite or a q_k lies outside [0, 1) (q_k == 1.0f is outside).  Otherwise
+ *     i_k = (int)floorf(q_k * 2^D) (the product is exact) and the voxel's code is the 3 D-bit Morton word of (i_x, i_y, i_z) with x the most
+ *     significant bit of each triple: the digit of level l (bits 3 (D - l) .. 3 (D - l) + 2) is j = 4 x + 2 y + z, as everywhere in the tree.
+ *   Accumulation.  Per distinct code a count n and the sums S_c of the three 8-bit colour channels (64 bits each) over the accepted points
+ *     of ALL add calls.  The result depends on the multiset of accepted points alone: not on their order, the split into calls, a launch
+ *     shape or an atomic's turn.  More than 2^32 - 1 accepted points is MNV_E_UNSUPPORTED (the add that passes it changes nothing).
+ *   Occupancy and structure.  A depth-D voxel is occupied iff n >= min_points.  A chunk of depth d exists iff it is the root or an occupied
+ *     voxel lies under the depth-(d - 1) voxel above it.  Chunks are numbered breadth first: the root is 0, then depth 2, 3 .. D, within a
+ *     depth ascending by the code of the voxel above.  capacity = the number of chunks = the sum of stats.chunks_at_depth.
+ *     child[c][j] = index(child chunk) - c where that chunk exists, 0 otherwise (every entry of depth D is 0).  parent[c] = index(parent
+ *     chunk) * 8 + j of the voxel above, -1 for the root (mnv_tree_truncate's rule).  sample_counts is 8 everywhere (the loader's value).
+ *     counts[c][j] = n of every depth-D voxel of an existing chunk, those below min_points included, 0 elsewhere.
+ *   Rows.  All 0x0000, except the rows of occupied depth-D voxels: column data_dim - 1 is half(sigma) (to nearest even, once); per colour
+ *     channel c the mean m = (2 S_c + n) / (2 n) in integer arithmetic (round half up, 0 .. 255) picks table[m] of
+ *     mnv_points_colour_table, which goes to column c (MNV_FORMAT_RGBA, data_dim 4) or to the DC coefficient c * basis_dim
+ *     (MNV_FORMAT_SH, data_dim 3 * basis_dim + 1; the higher coefficients stay 0).
+ *   mnv_points_colour_table (HOST, no device needed; create uploads the same table, no device transcendental is involved):
+ *     RGBA: table[v] = half(v / 255.f).  SH: table[v] = half((float)(log(x / (1 - x)) / 0.28209479177387814)) computed in double, with
+ *     x = clamp(v / 255, 1/512, 511/512): the inverse of the march's sigmoid of C0 * coefficient.
+ *   No occupied voxel: capacity 1, the root chunk is all leaves with zero rows (with D == 1 the root's voxels are the depth-D voxels:
+ *     counts holds theirs).
+ * Outputs of write (device): child_out int32 [capacity][8]; data_out [capacity][8][data_dim], 16-byte aligned; parent_out int32 [capacity]
+ * or NULL; sample_counts_out int16 [capacity][8] or NULL; counts_out uint32 [capacity][8] or NULL.
+ * Memory.  A handle keeps 40 bytes per distinct voxel (code, count, three sums), after finish 8 bytes per chunk, and a grow-only scratch:
+ * 24 bytes per element of the largest sort (keys and payloads, twice: the sort runs between the two halves), 48 per 512 elements and the
+ * sort's histograms -- within 32 bytes per element --, where the elements of an add are its points (at most 2^27 at a time:
+ * a longer add is sorted in pieces) and the distinct voxels held so far, which are sorted with them; while an add runs the old and the new
+ * record list exist together (40 bytes per distinct voxel each).  finish holds 8 bytes per distinct voxel more while it runs.
+ * MNV_E_INVALID: a null argument (rgb included); depth outside 1 .. 21; min_points == 0; a sigma that is not finite and positive; a scale
+ * that is not finite and positive, an offset that is not finite; n < 0; misaligned data_out; host pointers.  MNV_E_UNSUPPORTED: a format
+ * or basis_dim outside {RGBA, SH with 1, 4, 9, 16, 25}; more than 2^31 - 1 chunks, or points and distinct voxels in one sort.  Arguments
+ * are checked before a device is touched; create on a machine without one is MNV_E_NO_DEVICE. */
+typedef struct mnv_points_params {
+    float offset[3], scale[3];   /* world -> unit cube, as mnv_tree_view has them */
+    int32_t depth;               /* D: the leaf voxels' depth, 1 .. 21 */
+    int32_t format, basis_dim;   /* MNV_FORMAT_RGBA, or MNV_FORMAT_SH with basis_dim in {1, 4, 9, 16, 25} */
+    uint32_t min_points;         /* a depth-D voxel is occupied iff its count >= min_points; >= 1 */
+    float sigma;                 /* density written to occupied voxels; finite, > 0 */
+} mnv_points_params;
+typedef struct mnv_points_stats {
+    int64_t accepted, dropped;   /* points inside / outside the cube (or not finite), over all add calls */
+    int64_t distinct_voxels;     /* depth-D voxels holding >= 1 point */
+    int64_t occupied_voxels;     /* ... holding >= min_points */
+    int64_t chunks_at_depth[24]; /* entry d = chunks of depth d (entry 0 unused, 0); their sum is the capacity */
+} mnv_points_stats;
+typedef struct mnv_point_tree mnv_point_tree;
+int mnv_point_tree_create(const mnv_points_params *p, mnv_point_tree **out);
+int mnv_point_tree_add(mnv_point_tree *t, const float *xyz /* device [n][3] */, const uint8_t *rgb /* device [n][3] */, int64_t n, void *hip_stream);
+int mnv_point_tree_finish(mnv_point_tree *t, mnv_points_stats *stats /* HOST */, void *hip_stream);
+int mnv_point_tree_write(const mnv_point_tree *t, int32_t *child_out, uint16_t *data_out, int32_t *parent_out /* or NULL */,
+                         int16_t *sample_counts_out /* or NULL */, uint32_t *counts_out /* or NULL, [capacity][8] */, void *hip_stream);
+void mnv_point_tree_destroy(mnv_point_tree *t);
+int mnv_points_colour_table(int32_t format, int32_t basis_dim, uint16_t out[256] /* HOST */);
+/* The smallest cube around the box [lo, hi] as an offset and a scale (HOST): ext_k = hi[k] - lo[k], L = max_k ext_k (1 when that is 0),
+ * s = 1.f / L, scale[k] = s for the three axes, offset[k] = 0.5f - s * (0.5f * (lo[k] + hi[k])): the box's centre maps to 0.5.  A point on
+ * an upper face of the box along its longest axis maps to q == 1 and would be dropped: callers that want every point inside widen the box
+ * first.  MNV_E_INVALID: a null argument, a bound that is not finite, hi[k] < lo[k]. */
+int mnv_points_bounds_to_cube(const float lo[3], const float hi[3], float offset[3], float scale[3]);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -1366,6 +1438,12 @@ int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const 
  * (mnv_n3tree_make_lod of the teacher) fitted this way is the use. */
 int mnv_n3tree_fit_to_tree(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt,
                            const mnv_fit_params *params, int64_t *se_q32_out);
+/* N3Tree::from_points: mnv_point_tree_create, one add of the n device points, finish and write into a NEW tree on the device -- data, child,
+ * parent, sample counts and the packed accel -- with the params' offset / scale / row format (basis_dim -1 for RGBA); its host arrays are
+ * downloaded, so mnv_n3tree_save_npz, mnv_n3tree_make_lod, mnv_n3tree_fit and mnv_extract_surface work on it at once.  stats: HOST or NULL.
+ * n == 0 gives the one-chunk empty tree.  Waits for hip_stream.  Free with mnv_n3tree_free.  The codes of the four calls. */
+int mnv_n3tree_from_points(const mnv_points_params *p, const float *xyz /* device [n][3] */, const uint8_t *rgb /* device [n][3] */, int64_t n,
+                           void *hip_stream, mnv_points_stats *stats, mnv_n3tree **out);
 /* DataFormat::parse / to_string (src/data_format.cpp:5-41) */
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim);
 int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size_t buflen);

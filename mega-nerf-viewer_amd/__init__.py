@@ -232,6 +232,26 @@ class SurfaceStats(C.Structure):
 EXTRACT_COLOUR, EXTRACT_ALL_BRICKS = 1, 2
 
 
+class PointsParams(C.Structure):
+    """mnv_points_params"""
+    _fields_ = [("offset", C.c_float * 3), ("scale", C.c_float * 3), ("depth", C.c_int32), ("format", C.c_int32), ("basis_dim", C.c_int32),
+                ("min_points", C.c_uint32), ("sigma", C.c_float)]
+
+
+class PointsStats(C.Structure):
+    """mnv_points_stats"""
+    _fields_ = [("accepted", C.c_int64), ("dropped", C.c_int64), ("distinct_voxels", C.c_int64), ("occupied_voxels", C.c_int64),
+                ("chunks_at_depth", C.c_int64 * 24)]
+
+    @property
+    def capacity(self) -> int:
+        return int(sum(self.chunks_at_depth))
+
+    def as_dict(self):
+        return dict(accepted=self.accepted, dropped=self.dropped, distinct_voxels=self.distinct_voxels, occupied_voxels=self.occupied_voxels,
+                    chunks_at_depth=list(self.chunks_at_depth), capacity=self.capacity)
+
+
 # every symbol include/mnv.h declares (tests/test_capi_symbols.py checks the export list)
 _SIGNATURES = {
     "mnv_version": (C.c_int, []),
@@ -446,6 +466,14 @@ _SIGNATURES = {
     "mnv_tree_cull": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(CullCounts), C.c_void_p]),
     "mnv_n3tree_make_culled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RenderOptions), C.c_float, C.POINTER(C.c_int64), C.POINTER(CullCounts),
                                          C.POINTER(C.c_void_p)]),
+    "mnv_point_tree_create": (C.c_int, [C.POINTER(PointsParams), C.POINTER(C.c_void_p)]),
+    "mnv_point_tree_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mnv_point_tree_finish": (C.c_int, [C.c_void_p, C.POINTER(PointsStats), C.c_void_p]),
+    "mnv_point_tree_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_point_tree_destroy": (None, [C.c_void_p]),
+    "mnv_points_colour_table": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "mnv_points_bounds_to_cube": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_n3tree_from_points": (C.c_int, [C.POINTER(PointsParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(PointsStats), C.POINTER(C.c_void_p)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -507,6 +535,9 @@ _PROBE_SIGNATURES = {
     "mnv_hook_probe_setup_ray": (C.c_int, [C.POINTER(ProbeFrame), C.POINTER(ProbeCamBlock), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_void_p]),
     "mnv_hook_probe_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # csrc/mnv_points_probe.hip: rocprim::radix_sort_pairs alone, the yardstick of tools/points_bench.py
+    "mnv_hook_points_sort_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 _hooks_lib: Optional[C.CDLL] = None
@@ -711,6 +742,45 @@ class N3Tree:
         h = C.c_void_p()
         _check(lib().mnv_synth_terrain_tree(C.byref(p), C.byref(h)))
         return cls(h.value)
+
+    @classmethod
+    def from_points(cls, xyz, rgb=None, depth: int = 8, sigma: float = 100.0, min_points: int = 1, data_format: str = "RGBA", cube=None,
+                    return_stats: bool = False, stream: int = 0):
+        """N3Tree::from_points: a tree from a coloured point cloud, on the device with parent, sample counts and the accel, host arrays
+        filled (include/mnv.h, "a tree from a coloured point cloud").  xyz: float32 [n, 3], rgb: uint8 [n, 3] or None (white), as numpy
+        arrays or torch device tensors.  cube: (offset[3], scale[3]) of the world -> unit cube map, or None for the smallest cube around
+        the cloud's finite points, widened by 2^-12 of its edge so that no point sits on its upper faces.  return_stats: also the
+        PointsStats."""
+        import torch
+
+        def dev(a, dtype, what):
+            if a is None:
+                return None
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if dtype == torch.float32 else np.uint8))
+            if t.dtype != dtype or t.dim() != 2 or t.shape[1] != 3:
+                raise MnvError(MNV_E_INVALID, f"{what} must be [n, 3] of {dtype}")
+            return t.contiguous().cuda()
+
+        xyz_t = dev(xyz, torch.float32, "xyz")
+        n = int(xyz_t.shape[0])
+        rgb_t = dev(rgb, torch.uint8, "rgb") if rgb is not None else torch.full((n, 3), 255, dtype=torch.uint8, device=xyz_t.device)
+        if int(rgb_t.shape[0]) != n:
+            raise MnvError(MNV_E_INVALID, "one colour per point")
+        if cube is None:
+            good = xyz_t[torch.isfinite(xyz_t).all(dim=1)]
+            if good.shape[0] == 0:
+                lo = hi = np.zeros(3, np.float32)
+            else:
+                lo, hi = good.min(dim=0).values.cpu().numpy(), good.max(dim=0).values.cpu().numpy()
+            pad = np.float32(max(float((hi - lo).max()), 0.0) / 4096.0) or np.float32(0.5)
+            cube = points_bounds_to_cube(lo - pad, hi + pad)
+        fmt, basis = parse_data_format(data_format)
+        p = PointsParams(_f3(cube[0]), _f3(cube[1]), int(depth), fmt, basis, int(min_points), float(sigma))
+        h, st = C.c_void_p(), PointsStats()
+        _check(lib().mnv_n3tree_from_points(C.byref(p), xyz_t.data_ptr() if n else None, rgb_t.data_ptr() if n else None, n, C.c_void_p(stream), C.byref(st),
+                                            C.byref(h)))
+        out = cls(h.value)
+        return (out, st) if return_stats else out
 
     def host_view(self) -> TreeView:
         v = TreeView()
@@ -1774,6 +1844,55 @@ def tree_cut(tree_view: TreeView, keep, new_capacity: int, child_out, data_out, 
     new_capacity chunks, as tree_truncate's; `keep` (uint8 device tensor [capacity]) must be parent-closed (tree_select_cut's is)."""
     _check(lib().mnv_tree_cut(C.byref(tree_view), _ptr(keep), int(new_capacity), _ptr(child_out), _ptr(data_out), _ptr(parent_out),
                               _ptr(sample_counts_out), C.c_void_p(stream)))
+
+
+def points_colour_table(data_format: str = "RGBA") -> np.ndarray:
+    """mnv_points_colour_table: the binary16 bits an 8-bit colour mean becomes in a row of `data_format` (uint16 [256]); host only."""
+    fmt, basis = parse_data_format(data_format)
+    out = np.zeros(256, np.uint16)
+    _check(lib().mnv_points_colour_table(fmt, basis, out.ctypes.data))
+    return out
+
+
+def points_bounds_to_cube(lo, hi):
+    """mnv_points_bounds_to_cube: (offset float32 [3], scale float32 [3]) of the smallest cube around the box [lo, hi], centre at 0.5."""
+    lo, hi = np.ascontiguousarray(lo, np.float32), np.ascontiguousarray(hi, np.float32)
+    offset, scale = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _check(lib().mnv_points_bounds_to_cube(lo.ctypes.data, hi.ctypes.data, offset.ctypes.data, scale.ctypes.data))
+    return offset, scale
+
+
+class PointTree:
+    """mnv_point_tree: points -> occupancy, structure, first colours (include/mnv.h, "a tree from a coloured point cloud").  add any number
+    of times (float32 [n, 3] / uint8 [n, 3] device tensors), finish() -> PointsStats, then write() into device tensors of stats.capacity chunks."""
+
+    def __init__(self, offset, scale, depth: int, sigma: float, min_points: int = 1, data_format: str = "RGBA"):
+        fmt, basis = parse_data_format(data_format)
+        self.params = PointsParams(_f3(offset), _f3(scale), int(depth), fmt, basis, int(min_points), float(sigma))
+        self.data_dim = 4 if fmt == FORMAT_RGBA else 3 * basis + 1
+        self._h = C.c_void_p()
+        _check(lib().mnv_point_tree_create(C.byref(self.params), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().mnv_point_tree_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def add(self, xyz, rgb, n=None, stream: int = 0) -> None:
+        n = int(xyz.shape[0]) if n is None else int(n)
+        _check(lib().mnv_point_tree_add(self._h, _ptr(xyz), _ptr(rgb), n, C.c_void_p(stream)))
+
+    def finish(self, stream: int = 0) -> PointsStats:
+        st = PointsStats()
+        _check(lib().mnv_point_tree_finish(self._h, C.byref(st), C.c_void_p(stream)))
+        return st
+
+    def write(self, child_out, data_out, parent_out=None, sample_counts_out=None, counts_out=None, stream: int = 0) -> None:
+        _check(lib().mnv_point_tree_write(self._h, _ptr(child_out), _ptr(data_out), _ptr(parent_out), _ptr(sample_counts_out), _ptr(counts_out),
+                                          C.c_void_p(stream)))
 
 
 MAX_BATCH = 64

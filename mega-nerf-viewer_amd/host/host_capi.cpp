@@ -229,6 +229,23 @@ int mnv_n3tree_make_culled(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams
     });
 }
 
+int mnv_n3tree_from_points(const mnv_points_params *p, const float *xyz, const uint8_t *rgb, int64_t n, void *hip_stream, mnv_points_stats *stats,
+                           mnv_n3tree **out) {
+    if (!p || !out) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_from_points: null argument");
+    *out = nullptr;
+    return guarded([&] {
+        auto *h = new mnv_n3tree();
+        try {
+            viewer::N3Tree::from_points_into(h->tree, *p, xyz, rgb, n, hip_stream, stats);
+        } catch (...) {
+            delete h;
+            throw;
+        }
+        *out = h;
+        return MNV_OK;
+    });
+}
+
 int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets, const mnv_render_options *opt,
                    const mnv_fit_params *params, int64_t *se_q32_out) {
     if (!t || !cams || !targets || !opt || !params) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit: null argument");

@@ -67,6 +67,15 @@
 //                    1 and 20: the rates at which the numpy restatement's loss falls at every step on the test suite's fit scene, where
 //                    a leaf of the cut covers a few pixels of a frame; the gradient of a row is a SUM over the rays through its voxel,
 //                    so larger frames want smaller rates).  At most 2^24 pixels over the poses.
+//   --points FILE    build the tree from a coloured point cloud in place of opening one (N3Tree::from_points: mnv_point_tree_create / add /
+//                    finish / write).  FILE is an .npz holding `points` (float32 [n][3]) and optionally `colors` (uint8 [n][3], default
+//                    255), or an .obj whose `v x y z [r g b]` lines are the points (float colours become (int)(c * 255 + 0.5), clamped).
+//                    --points_depth D (default 8) the leaf voxels' depth, --points_sigma S (default 100) their density, --points_min N
+//                    (default 1) the points a voxel needs, --points_format RGBA|SH1|SH4|SH9|SH16|SH25 (default RGBA) the rows,
+//                    --points_cube ox,oy,oz,sx,sy,sz the world -> unit cube map (default: the smallest cube around the cloud's finite
+//                    points, widened by 2^-12 of its edge).  Prints the stats with the chunks per depth: the depth at which the counts
+//                    stop growing eightfold is where the cloud stops filling voxels.  --save_lod OUT.npz writes the tree (the level of
+//                    detail of it when --lod, --lod_pixels or --cull is given too).  Refused with an input tree and with --gpus.
 //   --target PREFIX  score frame f against PREFIX_%04d.ppm (the P6 files --out writes) on the device (VolumeRenderer::set_target,
 //                    mnv_frame_metrics with MNV_METRIC_QUANTISED: the file --out would write against the file that was read) and print
 //                    "frame F: psnr ..." when the frame is collected, then the means over the frames.  --ssim adds SSIM (11 x 11 Gaussian
@@ -96,6 +105,7 @@
 #include <vector>
 
 #include "mesh.hpp"
+#include "npz.hpp"
 #include "volume_renderer.hpp"
 
 namespace {
@@ -167,6 +177,8 @@ void usage() {
               "                  [--cull W [--save_lod OUT.npz]]   march (and write) the tree without what this run's poses cannot see (weights <= W)\n"
               "                  [--lod_fit ITERS [--fit_lr_colour X] [--fit_lr_sigma Y]]   with --lod / --lod_pixels: fit that tree's rows to the full\n"
               "                   tree's frames at the poses of this run first (ITERS gradient steps)\n"
+              "                  [--points FILE.npz|FILE.obj [--points_depth D] [--points_sigma S] [--points_min N] [--points_format RGBA|SH9...]\n"
+              "                   [--points_cube ox,oy,oz,sx,sy,sz] [--save_lod OUT.npz]]   build the tree from a coloured point cloud (no npz_file then)\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
               "                   0 = excluded): PSNR and, with --ssim, SSIM per frame and their means; not with --gpus.  Out of scope: pose\n"
               "                   lists (poses stay --orbit or the API) and LPIPS (it needs a network this repository does not have)\n"
@@ -620,12 +632,89 @@ int run_distributed(const Args &args, int world) {
     return worst;
 }
 
+// --points: the cloud of an .npz or .obj file as a tree on the device
+void tree_from_points(const Args &args, viewer::N3Tree &tree) {
+    const std::string path = args.get("points", "");
+    auto ends_with = [&](const char *suffix) { return path.size() >= 4 && path.compare(path.size() - 4, 4, suffix) == 0; };
+    std::vector<float> xyz;
+    std::vector<uint8_t> rgb;
+    if (ends_with(".npz")) {
+        const viewer::npz::Archive z = viewer::npz::load(path);
+        const auto p = z.find("points");
+        if (p == z.end()) throw std::runtime_error("--points: " + path + " lacks the array 'points'");
+        const viewer::npz::Array &a = p->second;
+        if (a.kind != 'f' || a.word_size != 4 || a.fortran_order || a.shape.size() != 2 || a.shape[1] != 3) throw std::runtime_error("--points: 'points' must be float32 [n][3]");
+        xyz.assign(a.data<float>(), a.data<float>() + a.num_vals());
+        const auto c = z.find("colors");
+        if (c != z.end()) {
+            const viewer::npz::Array &b = c->second;
+            if (b.kind != 'u' || b.word_size != 1 || b.fortran_order || b.shape != a.shape) throw std::runtime_error("--points: 'colors' must be uint8 [n][3]");
+            rgb.assign(b.data<uint8_t>(), b.data<uint8_t>() + b.num_vals());
+        }
+    } else if (ends_with(".obj")) {
+        const viewer::Mesh m = viewer::Mesh::load_obj(path);
+        const size_t n = m.vert.size() / 9;
+        xyz.resize(n * 3);
+        rgb.resize(n * 3);
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) {
+                xyz[i * 3 + k] = m.vert[i * 9 + k];
+                const float v = m.vert[i * 9 + 3 + k] * 255.f + 0.5f;
+                rgb[i * 3 + k] = (uint8_t)(v >= 255.f ? 255 : v > 0.f ? (int)v : 0);
+            }
+    } else {
+        throw std::runtime_error("--points takes an .npz or an .obj file");
+    }
+    mnv_points_params p{};
+    viewer::DataFormat fmt;
+    fmt.parse(args.get("points_format", "RGBA"));
+    p.format = fmt.format == viewer::DataFormat::SH ? MNV_FORMAT_SH : MNV_FORMAT_RGBA;
+    p.basis_dim = fmt.basis_dim;
+    p.depth = (int32_t)args.l("points_depth", 8);
+    p.sigma = args.f("points_sigma", 100.f);
+    const long min_points = args.l("points_min", 1);
+    if (min_points < 1 || min_points > 0x7fffffffl) throw std::runtime_error("--points_min takes a count of at least 1");
+    p.min_points = (uint32_t)min_points;
+    if (args.has("points_cube")) {
+        const std::vector<float> cube = args.vec("points_cube", {});
+        if (cube.size() != 6) throw std::runtime_error("--points_cube takes ox,oy,oz,sx,sy,sz");
+        for (int k = 0; k < 3; ++k) p.offset[k] = cube[k], p.scale[k] = cube[3 + k];
+    } else {  // the smallest cube around the finite points, widened so that none sits on an upper face
+        float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};
+        bool any = false;
+        for (size_t i = 0; i + 2 < xyz.size(); i += 3) {
+            if (!std::isfinite(xyz[i]) || !std::isfinite(xyz[i + 1]) || !std::isfinite(xyz[i + 2])) continue;
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = any ? std::min(lo[k], xyz[i + k]) : xyz[i + k];
+                hi[k] = any ? std::max(hi[k], xyz[i + k]) : xyz[i + k];
+            }
+            any = true;
+        }
+        float pad = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]) / 4096.f;
+        if (!(pad > 0.f)) pad = 0.5f;
+        for (int k = 0; k < 3; ++k) lo[k] -= pad, hi[k] += pad;
+        mnv_ok(mnv_points_bounds_to_cube(lo, hi, p.offset, p.scale), "--points");
+    }
+    mnv_points_stats st{};
+    viewer::N3Tree::from_points_into(tree, p, xyz, rgb, nullptr, &st);
+    std::printf("points: %zu point(s), %lld accepted, %lld dropped; depth %d: %lld distinct voxel(s), %lld occupied (>= %u points); %d chunk(s), per depth:",
+                xyz.size() / 3, (long long)st.accepted, (long long)st.dropped, p.depth, (long long)st.distinct_voxels, (long long)st.occupied_voxels, p.min_points,
+                tree.capacity);
+    for (int d = 1; d < 24 && st.chunks_at_depth[d] > 0; ++d) std::printf(" %lld", (long long)st.chunks_at_depth[d]);
+    std::printf("; offset %.9g,%.9g,%.9g scale %.9g,%.9g,%.9g\n", p.offset[0], p.offset[1], p.offset[2], p.scale[0], p.scale[1], p.scale[2]);
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     try {
         const Args args = parse(argc, argv);
-        if (args.has("help") || args.file.empty()) {
+        if (args.has("points") && !args.file.empty())
+            throw std::runtime_error("--points builds the tree: it cannot be combined with an input tree (" + args.file + ")");
+        if (args.has("points") && args.has("gpus")) throw std::runtime_error("--points builds the tree on one GPU: it cannot be combined with --gpus");
+        for (const char *k : {"points_depth", "points_sigma", "points_min", "points_format", "points_cube"})
+            if (args.has(k) && !args.has("points")) throw std::runtime_error(std::string("--") + k + " needs --points");
+        if (args.has("help") || (args.file.empty() && !args.has("points"))) {
             usage();
             return args.has("help") ? 0 : 2;
         }
@@ -645,7 +734,8 @@ int main(int argc, char **argv) {
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
         const long lod = args.l("lod", 0);
         if (args.has("lod") && lod < 1) throw std::runtime_error("--lod takes a depth of at least 1");
-        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull")) throw std::runtime_error("--save_lod needs --lod, --lod_pixels or --cull");
+        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull") && !args.has("points"))
+            throw std::runtime_error("--save_lod needs --lod, --lod_pixels or --cull");
         const float cull_thresh = args.f("cull", 0.f);
         if (args.has("cull") && (!std::isfinite(cull_thresh) || cull_thresh < 0.f)) throw std::runtime_error("--cull takes a finite weight threshold, 0 or more");
         if (args.has("cull") && (args.has("lod") || args.has("lod_pixels") || args.has("lod_fit") || args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
@@ -667,7 +757,16 @@ int main(int argc, char **argv) {
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 
-        viewer::N3Tree tree(args.file);  // main.cpp:528
+        viewer::N3Tree tree;
+        if (args.has("points")) {
+            tree_from_points(args, tree);
+            if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull")) {
+                tree.save_npz(args.get("save_lod", ""));
+                std::printf("save_lod: %d chunks -> %s\n", tree.capacity, args.get("save_lod", "").c_str());
+            }
+        } else {
+            tree.open(args.file);  // main.cpp:528
+        }
         if (args.has("bounds_only") && tree.N > 0) {  // main.cpp:529-538: keep one empty root chunk
             tree.capacity = 1;
             tree.data.assign((size_t)8 * tree.data_dim, 0);

@@ -139,6 +139,20 @@ struct N3Tree {
     std::vector<int64_t> fit_to(const N3Tree &teacher, const std::vector<mnv_camera> &cams, const mnv_render_options &opt, const mnv_fit_params &params,
                                 void *hip_stream = nullptr);
 
+    // A tree from a coloured point cloud (include/mnv.h, "a tree from a coloured point cloud": mnv_point_tree_create / add / finish /
+    // write): occupancy at depth params.depth, the chunks above it, mean colours and one density, as a new tree on the device with parent,
+    // sample counts and the packed accel, host arrays downloaded -- what make_lod's result is, so save_npz, make_lod, fit and
+    // extract_surface work on it at once.  xyz_dev / rgb_dev: device arrays [n][3].  stats: or null.  Waits for the stream.
+    static std::unique_ptr<N3Tree> from_points(const mnv_points_params &params, const float *xyz_dev, const uint8_t *rgb_dev, int64_t n, void *hip_stream = nullptr,
+                                               mnv_points_stats *stats = nullptr);
+    // The same from host vectors (xyz: 3 floats per point; rgb: 3 bytes per point, or empty for white), uploaded in tiles through repeated add.
+    static std::unique_ptr<N3Tree> from_points(const mnv_points_params &params, const std::vector<float> &xyz, const std::vector<uint8_t> &rgb,
+                                               void *hip_stream = nullptr, mnv_points_stats *stats = nullptr);
+    static void from_points_into(N3Tree &out, const mnv_points_params &params, const float *xyz_dev, const uint8_t *rgb_dev, int64_t n, void *hip_stream = nullptr,
+                                 mnv_points_stats *stats = nullptr);
+    static void from_points_into(N3Tree &out, const mnv_points_params &params, const std::vector<float> &xyz, const std::vector<uint8_t> &rgb,
+                                 void *hip_stream = nullptr, mnv_points_stats *stats = nullptr);
+
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;
 
@@ -154,6 +168,8 @@ private:
     // the common end of make_lod_into / make_view_lod_into / make_culled_into: `o` becomes a device tree of new_cap chunks that `cut` fills
     // (child, data, parent, sample counts or null), with host arrays and, where this tree has one, an accel
     void compact_into(N3Tree &o, int64_t new_cap, const std::function<void(int32_t *, uint16_t *, int32_t *, int16_t *)> &cut, void *hip_stream) const;
+    // the common end of the two from_points_into: finish, the device arrays, write, host arrays, accel
+    static void finish_points_into(N3Tree &o, const mnv_points_params &params, mnv_point_tree *handle, void *hip_stream, mnv_points_stats *stats);
 };
 
 }  // namespace viewer
