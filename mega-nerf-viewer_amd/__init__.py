@@ -584,6 +584,14 @@ def last_march_variant():
     return tuple(int(x) for x in out)
 
 
+def last_march_shape() -> int:
+    """Lookup shape of the march_accel_kernel instantiation that the test-hook build launched last (csrc/mnv_march_accel_kernel.h: 0 generic,
+    1 / 2 the fixed shape without / with brick records; -1 before the first launch).  As last_march_variant: the hooks build only."""
+    f = hooks_lib().mnv_hook_last_march_shape
+    f.restype, f.argtypes = C.c_int32, []
+    return int(f())
+
+
 def built_source_sha() -> str:
     """Hash of the sources the loaded libmnv.so was built from (mnv_source_sha)."""
     return lib().mnv_source_sha().decode()

@@ -14,7 +14,7 @@ static const char *const kKnobNames[KNOB_COUNT] = {
     "MNV_TILE_WLOG",      "MNV_QUEUES",           "MNV_LDS_LEVEL",      "MNV_BLOCKS_PER_CU",   "MNV_REFILL_MIN",     "MNV_ABLATE",
     "MNV_STATS",          "MNV_TIMELINE",         "MNV_GRID2_LEVEL",    "MNV_BRICK_LEVELS",    "MNV_F2_BLOCKS_PER_CU", "MNV_F2_SWITCH_MIN",
     "MNV_FUSED_BATCH_MIN", "MNV_VOTE_WIDE_KEYS",  "MNV_VOTE_FULL_SORT", "MNV_ASSEMBLE_NARROW", "MNV_REFRESH_DEBUG",  "MNV_SYNTH_TIMING",
-    "MNV_FOOTPRINT",      "MNV_SHADOW",
+    "MNV_FOOTPRINT",      "MNV_SHADOW",           "MNV_MARCH_SHAPE",
 };
 const char *knob_str(Knob k) { return k >= 0 && k < KNOB_COUNT ? std::getenv(kKnobNames[k]) : nullptr; }
 int knob_int(Knob k, int dflt) {
@@ -30,12 +30,15 @@ void note_march_variant(int basis, int mode, bool brick, bool rays) {
     g_last_march_variant.store(0x80000000u | (uint32_t)((basis + 1) & 0xff) | (uint32_t)(mode & 0xff) << 8 | (uint32_t)brick << 16 | (uint32_t)rays << 17,
                                std::memory_order_relaxed);
 }
+static std::atomic<int> g_last_march_shape{-1};
+void note_march_shape(int shape) { g_last_march_shape.store(shape, std::memory_order_relaxed); }
 #else
 long long ref_table_min_rays() { return 1 << 16; }
 const char *knob_str(Knob) { return nullptr; }
 int knob_int(Knob, int dflt) { return dflt; }
 bool knob_set(Knob) { return false; }
 void note_march_variant(int, int, bool, bool) {}
+void note_march_shape(int) {}
 #endif
 
 }  // namespace mnv
@@ -50,4 +53,5 @@ extern "C" void mnv_hook_last_march_variant(int32_t out4[4]) {
     out4[2] = any ? (int32_t)(w >> 16 & 1) : -1;
     out4[3] = any ? (int32_t)(w >> 17 & 1) : -1;
 }
+extern "C" int32_t mnv_hook_last_march_shape() { return (int32_t)mnv::g_last_march_shape.load(std::memory_order_relaxed); }
 #endif

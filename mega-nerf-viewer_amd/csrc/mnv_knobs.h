@@ -27,6 +27,7 @@ enum Knob {
     KNOB_SYNTH_TIMING,     // the synthetic-tree generators print their phases
     KNOB_FOOTPRINT,        // string: file for the unique 128-byte lines the accel's launches touched, per array (written when the accel is destroyed)
     KNOB_SHADOW,           // allocate the copies the -DMNV_SHADOW_MASK variants of the march read (16 nodes, 32 rows, 64 bricks)
+    KNOB_MARCH_SHAPE,      // 0: every march launch takes the generic lookup shape (mnv_march_launch.h)
     KNOB_COUNT
 };
 
@@ -43,5 +44,8 @@ const char *knob_str(Knob k);
 // build; the test-hook build keeps the last one in one atomic word, which mnv_hook_last_march_variant(int32_t out4[4]) reads back as
 // {basis, mode, brick, rays} ({-2, -1, -1, -1} before the first launch) -- tests/test_march_matrix_gpu.py pins the launcher's rule with it.
 void note_march_variant(int basis, int mode, bool brick, bool rays);
+// ... and the lookup shape of that instantiation (mnv_march_accel_kernel.h: 0 generic, 1 / 2 fixed without / with brick records); the
+// test-hook build reads it back with mnv_hook_last_march_shape() (-1 before the first launch)
+void note_march_shape(int shape);
 
 }  // namespace mnv

@@ -31,14 +31,29 @@
 
 namespace mnv {
 
-// One step of the march on integer cell coordinates.  pos in [0, 1-1e-6] is scaled by 2^Lq
-// (Lq = deepest voxel depth of the tree, <= 23: the product is exact and < 2^24) and truncated;
-// bit (Lq - d) of each coordinate is the child index at depth d, and the cell numbers of the two
-// lookup grids are plain shifts.  The in-leaf coordinates are fract(pos * 2^depth), which equals the
+// Lookup shape of an instantiation: what the step knows about the lookup arrays at compile time.  kShapeGeneric reads the level of the LDS
+// grid (K.lds_level), the level of the second grid (A.grid2_level) and whether there are brick records (A.recs) at run time: every shift of
+// the step is then a scalar register, and the kernel has none to spare (below).  The two fixed shapes are the lookup that accel_build gives,
+// under the default knobs, every tree of depth >= 10 whose packed arrays earn a level-9 grid -- LDS grid at level 3, second grid at level 9
+// with inline cell words -- without / with brick records (depth 10 / deeper): their shifts are immediates and the record block is compiled
+// out / in.  launch_march_kernel (mnv_march_launch.h) picks the shape of a launch.
+enum : int { kShapeGeneric = 0, kShapeL3G9 = 1, kShapeL3G9Recs = 2 };
+constexpr int kShapeLdsLevel = 3, kShapeGrid2Level = 9;
+
+// One step of the march on integer cell coordinates.  pos in [0, 1-1e-6] is scaled by 2^Lq and truncated (Lq <= 23: the product is exact
+// in binary32 and < 2^23); bit (Lq - d) of each coordinate is the child index at depth d, and the cell numbers of the two lookup grids are
+// plain shifts by Lq - level.  The generic instantiations take Lq = the tree's deepest voxel depth (mnv_accel_build refuses trees beyond
+// 23), the fixed shapes Lq = 23 whatever the tree: for every depth d <= D <= 23
+//     floor(floor(pos * 2^23) / 2^(23 - d)) = floor(pos * 2^d) = floor(floor(pos * 2^D) / 2^(D - d)),
+// so every cell number, child bit and node-walk bit is the number the tree's own scale gives (tests/test_march_coord_scale_host.py; the
+// arrays, the accel build and the fused guided kernels know that scale only), and the shifts depend on the levels of the two grids alone:
+// compile-time constants.  (The constant scale in the generic instantiations too was measured: no gain, LAB_NOTEBOOK round 8.)
+// The in-leaf coordinates are fract(pos * 2^depth), which equals the
 // reference's iterated x*2 - floor(x*2) bit for bit (all three operations are exact in binary32).
 template <int BASIS, int BLOCK, int MODE /* 0 plain, 1 statistics, 2 refinement trackers, 3 trackers + emitted samples instead of colour, 4 plain with fast colour math, 5 depth image (render_depth) */,
           bool BRICK = false /* the levels below the second lookup grid come from inline cell words (A.grid2i) and brick records (A.recs) instead of node loads */,
-          bool RAYS = false /* the rays are the caller's (K.ray_origins / K.ray_dirs, indexed like the pixels) instead of a camera's: MODE 0 and 5 only (mnv_accel_march_rays.hip) */>
+          bool RAYS = false /* the rays are the caller's (K.ray_origins / K.ray_dirs, indexed like the pixels) instead of a camera's: MODE 0 and 5 only (mnv_accel_march_rays.hip) */,
+          int SHAPE = kShapeGeneric /* lookup shape (above); the fixed ones exist for the plain colour frames of the brick unit: BRICK, !RAYS, MODE 0 / 4 */>
 // A/B knobs (tools/build_variant.sh): explicit register budgets on top of the launch bounds
 #if defined(MNV_NUM_VGPR) && defined(MNV_NUM_SGPR)
 #define MNV_EXTRA_KERNEL_ATTR __attribute__((amdgpu_num_vgpr(MNV_NUM_VGPR), amdgpu_num_sgpr(MNV_NUM_SGPR)))
@@ -71,7 +86,9 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
     const FrameParams &P = K.P;
     const AccelView &A = K.A;
 
-    const int LL = K.lds_level;
+    static_assert(SHAPE == kShapeGeneric || (BRICK && !RAYS && (MODE == 0 || MODE == 4)), "fixed lookup shapes: plain colour frames on inline cell words only");
+    constexpr bool FIXED = SHAPE != kShapeGeneric;
+    const int LL = FIXED ? kShapeLdsLevel : K.lds_level;
     const int cells = 1 << (3 * LL);
     if (threadIdx.x < 32) s_exp[threadIdx.x] = kExp2fTab[threadIdx.x];
     if (LL == A.grid_level) {
@@ -95,10 +112,11 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
-    const int Lq = A.max_depth;
-    const float qscale = __uint_as_float((uint32_t)(127 + Lq) << 23);  // 2^Lq
-    const int sh1 = Lq - LL;                                            // q >> sh1 = LDS cell
-    const int L2 = A.grid2_level;                                       // 0: no second grid
+    // scale of the integer cell coordinates: 2^23 in a fixed shape, the tree's own in the generic instantiations (same cells: above)
+    const int Lq = FIXED ? 23 : A.max_depth;
+    const float qscale = FIXED ? 8388608.f : __uint_as_float((uint32_t)(127 + Lq) << 23);  // 2^Lq
+    const int sh1 = Lq - LL;             // q >> sh1 = LDS cell
+    const int L2 = FIXED ? kShapeGrid2Level : A.grid2_level;  // 0: no second grid
     const int sh2 = Lq - L2;
     const int shg = Lq - A.grid_level;
     float *my_ray = s_ray + threadIdx.x;             // [k * BLOCK]
@@ -458,7 +476,8 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                                     src = 2;
                                 }
                             }
-                            if (!(word & kLeafBit) && A.recs != nullptr) {
+                            // (whether the tree has brick records is known at compile time in a fixed shape)
+                            if (SHAPE != kShapeL3G9 && !(word & kLeafBit) && (SHAPE == kShapeL3G9Recs || A.recs != nullptr)) {
                                 probe.count(kCountNodeLoad, true);
                                 uint32_t s1 = __builtin_amdgcn_ubfe(q[0], (uint32_t)(sh2 - 1), 1u), s2 = __builtin_amdgcn_ubfe(q[0], (uint32_t)(sh2 - 2), 1u);
                                 s1 = (s1 << 1) | __builtin_amdgcn_ubfe(q[1], (uint32_t)(sh2 - 1), 1u);
