@@ -97,6 +97,8 @@ void report_diagnostics(const mnv_accel *a) {
             for (int i = 0; i < 6; ++i)
                 fprintf(stderr, "[mnv stats] %-13s wave-level %llu lane-level %llu (%.1f lanes)\n", names[i], h[2 * i], h[2 * i + 1],
                         h[2 * i] ? (double)h[2 * i + 1] / (double)h[2 * i] : 0.0);
+            // the colour block's two exponential paths (kCountExpUniform, kCountExpGeneral), a line of their own
+            fprintf(stderr, "[mnv exp paths] uniform wave-level %llu lane-level %llu, general wave-level %llu lane-level %llu\n", h[12], h[13], h[14], h[15]);
         }
     }
     if (d.timeline && knob_str(KNOB_TIMELINE)) {

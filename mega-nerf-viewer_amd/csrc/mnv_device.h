@@ -133,6 +133,34 @@ __device__ __forceinline__ float exact_expf(float x, const uint64_t *tab) {
     return (float)y;
 }
 
+// The main path of exact_expf alone, for an argument the caller has already tested: valid for ((bits(x) >> 20) & 0x7ff) < 0x42b (|x| < 88),
+// where exact_expf takes no special case and runs these very statements -- the same bits by construction
+// (tests/test_expf_core_gpu.py: all 2^32 inputs).  Beyond that range the result is meaningless (never a fault: the table index is masked).
+// A wavefront that tests the largest of several arguments once runs their chains without control flow between them.
+// (the caller's test, on the argument's bits with the sign cleared -- or on the largest such word of several arguments: exact_expf's
+// `abstop >= 0x42b` is `magnitude bits >= 0x42b00000`; every NaN and infinity is out of range)
+__device__ __forceinline__ bool exact_expf_core_in_range(uint32_t abs_bits) { return abs_bits < 0x42b00000u; }
+__device__ __forceinline__ float exact_expf_core(float x, const uint64_t *tab) {
+    constexpr double N = 32.0;
+    constexpr double InvLn2N = 0x1.71547652b82fep+0 * N;
+    constexpr double SHIFT = 0x1.8p+52;
+    constexpr double C0 = 0x1.c6af84b912394p-5 / N / N / N;
+    constexpr double C1 = 0x1.ebfce50fac4f3p-3 / N / N;
+    constexpr double C2 = 0x1.62e42ff0c52d6p-1 / N;
+    const double xd = (double)x;
+    double z = InvLn2N * xd;
+    double kd = z + SHIFT;
+    const uint64_t ki = (uint64_t)__double_as_longlong(kd);
+    kd -= SHIFT;
+    const double r = z - kd;
+    uint64_t t = tab[ki & 31u];
+    t += ki << 47;
+    const double s = __longlong_as_double((long long)t);
+    double y = expf_poly(r, C0, C1, C2);
+    y = y * s;
+    return (float)y;
+}
+
 // expf as exact_expf, without branches: the main path runs on a clamped argument (nothing overflows on the way) and the special cases
 // (|x| >= 88) are selected afterwards, in exact_expf's order.  Same bits for every input; several of these in a row have no control
 // flow between them, so the compiler interleaves their binary64 chains.

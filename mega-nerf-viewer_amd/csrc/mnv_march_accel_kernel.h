@@ -701,19 +701,61 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                     }
                     probe.template phase_end<kPhaseRow>();  // the rows have arrived
                     auto half_at = [&](int hidx) -> uint32_t { return (hidx & 1) ? (rw[hidx >> 1] >> 16) : (rw[hidx >> 1] & 0xffffu); };
-                    if constexpr (BRICK) settle(half_at(3 * BASIS));
-                    float b[NB];
+                    if constexpr (BRICK && !RAYS && MODE != 4) {
+                        // The sample's four exponentials -- opacity and three sigmoids -- behind ONE range test for the wavefront: exact_expf
+                        // tests |x| >= 88 in a divergent region of its own, four of them per sample with the scalar scaffolding of four
+                        // (about a third of the launch's scalar instructions).  All four arguments first, then the largest magnitude of the
+                        // dense lanes: in range (nearly always) the four main paths run as one block without control flow, exact_expf_core,
+                        // the same statements on the same arguments; otherwise exact_expf as before (|x| >= 88 is legal input).
+                        float b[NB];
 #pragma unroll
-                    for (int k = 0; k < NB; ++k) b[k] = my_ray[k * BLOCK];
-                    auto chan = [&](int c) -> float {
-                        // binary16 coefficient times binary32 basis straight from the raw row words (half_mul: no conversion instruction)
-                        const float tmp = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, c * BASIS);
-                        return colour_sigmoid<MODE == 4>(weight, tmp, s_exp);
-                    };
-                    if (dense) {  // (a candidate may have turned out not to be dense)
-                        o0 += chan(0);
-                        o1 += chan(1);
-                        o2 += chan(2);
+                        for (int k = 0; k < NB; ++k) b[k] = my_ray[k * BLOCK];
+                        const float sg = cand ? half_bits_to_float((uint16_t)half_at(3 * BASIS)) : sigma_held;
+                        if (!(sg > P.sigma_thresh)) dense = false;  // (settle: a candidate may turn out not to be dense)
+                        const float a0 = -delta_t * my_ray[NB * BLOCK] * sg;
+                        const float t0 = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, 0);
+                        const float t1 = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, BASIS);
+                        const float t2 = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, 2 * BASIS);
+                        constexpr uint32_t kAbs = 0x7fffffffu;
+                        const uint32_t m = max(max(__float_as_uint(a0) & kAbs, __float_as_uint(t0) & kAbs), max(__float_as_uint(t1) & kAbs, __float_as_uint(t2) & kAbs));
+                        float e0, e1, e2;
+                        // (measured and not kept, LAB_NOTEBOOK round 9: __builtin_expect here, which makes the uniform block the fall-through, and
+                        // the four table reads issued ahead of the first use -- neither moved the batched launch)
+                        const bool all_in_range = __ballot(dense && !exact_expf_core_in_range(m)) == 0;
+                        if (all_in_range) {
+                            probe.count(kCountExpUniform, dense);
+                            att = exact_expf_core(a0, s_exp);
+                            e0 = exact_expf_core(-t0, s_exp);
+                            e1 = exact_expf_core(-t1, s_exp);
+                            e2 = exact_expf_core(-t2, s_exp);
+                        } else {
+                            probe.count(kCountExpGeneral, dense);
+                            att = exact_expf(a0, s_exp);
+                            e0 = exact_expf(-t0, s_exp);
+                            e1 = exact_expf(-t1, s_exp);
+                            e2 = exact_expf(-t2, s_exp);
+                        }
+                        if (dense) {
+                            weight = T * (1.f - att);
+                            o0 += weight / (1.f + e0);
+                            o1 += weight / (1.f + e1);
+                            o2 += weight / (1.f + e2);
+                        }
+                    } else {
+                        if constexpr (BRICK) settle(half_at(3 * BASIS));
+                        float b[NB];
+#pragma unroll
+                        for (int k = 0; k < NB; ++k) b[k] = my_ray[k * BLOCK];
+                        auto chan = [&](int c) -> float {
+                            // binary16 coefficient times binary32 basis straight from the raw row words (half_mul: no conversion instruction)
+                            const float tmp = sh_channel_mix<BASIS>(b, [&](int j) -> uint32_t { return rw[j]; }, c * BASIS);
+                            return colour_sigmoid<MODE == 4>(weight, tmp, s_exp);
+                        };
+                        if (dense) {  // (a candidate may have turned out not to be dense)
+                            o0 += chan(0);
+                            o1 += chan(1);
+                            o2 += chan(2);
+                        }
                     }
                 }
             } else {

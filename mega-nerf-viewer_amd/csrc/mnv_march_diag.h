@@ -27,7 +27,12 @@ __device__ __forceinline__ void shadow_load(const uint2 *p) {
 }
 
 // counters of MNV_STATS (slot of the wave-level count in K.diag.stats; the lane-level count follows it) and the report's names for them
-enum MarchCount { kCountOuterIter = 0, kCountRefill = 2, kCountMarchStep = 4, kCountNodeLoad = 6, kCountDense = 8, kCountColourPass = 10 };
+// (kCountExpUniform / kCountExpGeneral: dense iterations of the per-lane SH block whose four exponentials ran as one block behind the
+// wavefront's range test / through exact_expf because a dense lane held an argument of |x| >= 88; the report's "[mnv exp paths]" line)
+enum MarchCount {
+    kCountOuterIter = 0, kCountRefill = 2, kCountMarchStep = 4, kCountNodeLoad = 6, kCountDense = 8, kCountColourPass = 10,
+    kCountExpUniform = 12, kCountExpGeneral = 14
+};
 // regions of the MNV_FOOTPRINT bitmap (K.diag.line_base)
 enum MarchRegion { kLinesGrid2 = 0, kLinesRecs = 1, kLinesNodes = 2, kLinesRows = 3, kLinesGrid2Vox = 4, kLinesGridVox = 5 };
 // phases of a wavefront's step (MNV_STATS=2)

@@ -23,7 +23,11 @@ constexpr int kSetupRow = 41;                          // floats per mnv_hook_pr
 
 unsigned grid_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
+// which 0 exact_expf, 1 exact_expf_select, 2 exact_expf_core (meaningful only where 3 says so), 3 the range test the march kernel puts in
+// front of exact_expf_core, on the argument's magnitude bits: 1.0 in range, 0.0 out of it
 __device__ __forceinline__ float expf_variant(float x, int which, const uint64_t *tab) {
+    if (which == 3) return mnv::exact_expf_core_in_range(__float_as_uint(x) & 0x7fffffffu) ? 1.f : 0.f;
+    if (which == 2) return mnv::exact_expf_core(x, tab);
     return which ? mnv::exact_expf_select(x, tab) : mnv::exact_expf(x, tab);
 }
 
@@ -199,7 +203,7 @@ int64_t mnv_hook_live_bytes(int which) {
 }
 
 int mnv_hook_probe_expf(const float *x, int64_t n, int which, float *out, void *hip_stream) {
-    if (n < 0 || (n > 0 && (!x || !out)) || which < 0 || which > 1) return set_error(MNV_E_INVALID, "mnv_hook_probe_expf: bad arguments");
+    if (n < 0 || (n > 0 && (!x || !out)) || which < 0 || which > 3) return set_error(MNV_E_INVALID, "mnv_hook_probe_expf: bad arguments");
     if (n == 0) return MNV_OK;
     hipLaunchKernelGGL(probe_expf_kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)hip_stream, x, n, which, out);
     return check_hip(hipGetLastError(), "probe_expf_kernel");
@@ -207,7 +211,7 @@ int mnv_hook_probe_expf(const float *x, int64_t n, int which, float *out, void *
 
 // digests [n_blocks][2] uint64: block first_block + b covers the bit patterns [(first_block + b) << 20, (first_block + b + 1) << 20)
 int mnv_hook_probe_expf_digest(uint32_t first_block, uint32_t n_blocks, int which, uint64_t *digests, void *hip_stream) {
-    if (!digests || which < 0 || which > 1 || n_blocks > 4096u || first_block > 4096u - n_blocks)
+    if (!digests || which < 0 || which > 3 || n_blocks > 4096u || first_block > 4096u - n_blocks)
         return set_error(MNV_E_INVALID, "mnv_hook_probe_expf_digest: bad arguments");
     if (n_blocks == 0) return MNV_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
