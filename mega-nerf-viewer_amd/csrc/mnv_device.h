@@ -153,9 +153,13 @@ __device__ __forceinline__ float exact_expf_core(float x, const uint64_t *tab) {
     const uint64_t ki = (uint64_t)__double_as_longlong(kd);
     kd -= SHIFT;
     const double r = z - kd;
-    uint64_t t = tab[ki & 31u];
-    t += ki << 47;
-    const double s = __longlong_as_double((long long)t);
+    // t += ki << 47 on the high dword alone: the low 32 bits of ki << 47 are zero, so the 64-bit sum carries neither into nor out of the
+    // low dword, and its high dword is hi(t) + (uint32_t)(ki << 15) modulo 2^32 -- one 32-bit add for a shift, a zero and a 64-bit add
+    // (on the two dwords as a vector: from `(uint64_t)hi << 32 | lo` the compiler builds the 64-bit add again, with three moves around it)
+    typedef uint32_t dwords __attribute__((ext_vector_type(2)));
+    dwords t = __builtin_bit_cast(dwords, tab[ki & 31u]);
+    t.y += (uint32_t)ki << 15;
+    const double s = __builtin_bit_cast(double, t);
     double y = expf_poly(r, C0, C1, C2);
     y = y * s;
     return (float)y;
@@ -300,9 +304,17 @@ struct RaySetup {
 // renderer_kernel.cu:30-38 (screen2worlddir), :272-275, :282-283 (rodrigues),
 // rt_core.cuh:182-209.  BASIS: number of SH basis functions kept in registers
 // (1 for DC-only / RGBA).
-template <int BASIS>
+// FRESH: the frame-constant binary64 terms below -- (double)render_bbox[i] +- 1e-6 and 1.0 - (double)rot_cos -- are formed where they are
+// used, from values that an empty volatile asm hides from loop-invariant code motion.  Without it a kernel that sets rays up inside its
+// march loop computes those seven doubles once, in front of the loop, and carries fourteen vector registers (or their spill slots) through
+// every march step for the sake of one set-up per ray (march_accel_kernel, INNER).  Same operations on the same values: the same bits.
+template <int BASIS, bool FRESH = false>
 __device__ __forceinline__ void setup_ray(const FrameParams &P, const CamBlock &C, int ix, int iy,
                                           RaySetup<(BASIS > 0 ? BASIS : 1)> &r, float t_max = 1e9f) {
+    auto fresh = [](float x) -> float {
+        if constexpr (FRESH) asm volatile("" : "+s"(x));
+        return x;
+    };
     const float xyz0 = (ix + 0.5f - C.cx) / C.fx;
     const float xyz1 = -(iy + 0.5f - C.cy) / C.fy;
     const float xyz2 = -1.0f;
@@ -327,7 +339,7 @@ __device__ __forceinline__ void setup_ray(const FrameParams &P, const CamBlock &
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             vdir[i] = (float)((double)(vdir[i] * P.rot_cos + cross[i] * P.rot_sin) +
-                              (double)(k[i] * dot) * (1.0 - (double)P.rot_cos));
+                              (double)(k[i] * dot) * (1.0 - (double)fresh(P.rot_cos)));
         }
     }
 
@@ -348,8 +360,8 @@ __device__ __forceinline__ void setup_ray(const FrameParams &P, const CamBlock &
         r.dir[i] = dir[i];
         r.invdir[i] = (float)(1.0 / ((double)dir[i] + 1e-9));  // :189
         const double inv = (double)r.invdir[i];
-        const float t1 = (float)(((double)P.render_bbox[i] + 1e-6 - (double)C.cen[i]) * inv);
-        const float t2 = (float)(((double)P.render_bbox[i + 3] - 1e-6 - (double)C.cen[i]) * inv);
+        const float t1 = (float)(((double)fresh(P.render_bbox[i]) + 1e-6 - (double)C.cen[i]) * inv);
+        const float t2 = (float)(((double)fresh(P.render_bbox[i + 3]) - 1e-6 - (double)C.cen[i]) * inv);
         tmin = fmaxf(tmin, fminf(t1, t2));
         tmax = fminf(tmax, fmaxf(t1, t2));
     }

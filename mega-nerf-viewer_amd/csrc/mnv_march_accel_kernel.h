@@ -272,6 +272,19 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
     MarchProbe<MODE, RAYS, BLOCK> probe(K, lane);
     probe.wave_begin();
 
+    // Shape of the loop.  One iteration is: refill (when enough lanes idle), else the end-of-tile bookkeeping (when no lane is alive), else
+    // one step and its colour block.  Written as ONE loop with two `continue`s and a `break`, the compiler's structuriser makes it a state
+    // machine with several back edges into one latch, and the latch's phis are register copies in every iteration: o0..o2, T, t and fin
+    // computed into temporaries and moved back (LAB_NOTEBOOK round 10).  INNER: the plain colour frames on inline cell words repeat the step
+    // and the colour block in a loop of their own for as long as the outer iteration would come straight back to them -- some lane alive
+    // and too few idle for a refill (or nothing left to refill from) -- the very condition the outer loop tests, so a wavefront's steps,
+    // refills, queue atomics and stores come in the order they had, and the inner loop ends when its lanes do (every live lane's t grows
+    // by at least step_size).  Without INNER the `while` is `while (false)` and the loop is the one it was, listing included.
+    // The inner loop's condition is ONE ballot and one scalar compare: all 64 lanes of a wavefront are active at loop level (BLOCK is a
+    // multiple of 64 and every branch around the loops is wave-uniform), so the idle lanes number 64 - popcount(live), and
+    //     live != 0 && (drained || 64 - popcount(live) < refill_min)   is   popcount(live) > (drained ? 0 : max(64 - refill_min, 0)),
+    // a bound (stay_above) that is fixed before the inner loop starts: neither K.refill_min nor `drained` is read inside it.
+    constexpr bool INNER = BRICK && !RAYS && (MODE == 0 || MODE == 4);
     for (;;) {
         const uint64_t idle = __ballot(!alive);
         const int n_idle = __popcll(idle);
@@ -344,7 +357,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                             cen1 = cen[1];
                             cen2 = cen[2];
                         } else {
-                            setup_ray<(BASIS > 0 ? BASIS : 0)>(P, *Cp, P.x0 + bx, P.y0 + by, r, frame_tmax(P, pix));
+                            setup_ray<(BASIS > 0 ? BASIS : 0), INNER>(P, *Cp, P.x0 + bx, P.y0 + by, r, frame_tmax(P, pix));  // (INNER: no frame constants carried through the march)
                         }
                         if constexpr (BASIS == 0)
                             r.basis[0] = (0 < P.basis_min || 0 > P.basis_max) ? 0.f : (float)0.28209479177387814;
@@ -389,6 +402,9 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
             continue;
         }
         // ---- one march step (rt_core.cuh:220-323) for every live lane
+        [[maybe_unused]] const int stay_above = (!INNER || drained) ? 0 : max(64 - (int)K.refill_min, 0);
+        [[maybe_unused]] uint64_t live = 0;
+        do {  // (INNER: the step and the colour block again, as long as the next outer iteration would do nothing else -- see INNER)
         bool dense = false;
         [[maybe_unused]] bool cand = false;  // BRICK: the leaf came out of a brick record with code 3 (sigma not known yet)
         [[maybe_unused]] float sigma_held = 0.f;  // BRICK: sigma of a dense leaf that did not come out of a record
@@ -422,8 +438,16 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
             }
         };
         probe.step_begin();
+        // INNER: a ray that has reached its end leaves before the step, so the step sits under ONE predicate (alive, which now implies
+        // t < tmax) and the defaults above are set once; the other instantiations keep the two nesting levels (and their listings)
+        if constexpr (INNER) {
+            if (alive && !(t < tmax)) {
+                fin = 1;
+                alive = false;
+            }
+        }
         if (alive) {
-            if (!(t < tmax)) {
+            if (!INNER && !(t < tmax)) {
                 // loop exit, rt_core.cuh:325-330: the pixel is finished in flush_finished()
                 fin = 1;
                 alive = false;
@@ -533,6 +557,7 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
                     tu = fminf(tu, fmaxf(t1, t2));
                 }
                 delta_t = tu * inv_cube + P.step_size;
+                if constexpr (INNER) t += delta_t;  // (the colour frames read t nowhere behind this point: in place, under the step's predicate)
                 const float sigma = half_bits_to_float((uint16_t)word);
                 const bool is_dense = sigma > P.sigma_thresh && !probe.ablate(2);
                 bool need_vox = is_dense;
@@ -782,8 +807,10 @@ __global__ __launch_bounds__(BLOCK, (MODE == 2 || MODE == 3) ? MNV_TRACK_WAVES :
         if constexpr (BRICK && MODE == 2) {
             if (dense_mask == 0) track_update();
         }
-        t += delta_t;  // 0 for lanes that did not step
+        if constexpr (!INNER) t += delta_t;  // 0 for lanes that did not step
         probe.template phase_end<kPhaseColour>();  // (iterations without a dense lane: the ballot and the transmittance update)
+        if constexpr (INNER) live = __ballot(alive);
+        } while (INNER && __popcll(live) > stay_above);
     }
     probe.wave_end();
 }
