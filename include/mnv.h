@@ -1375,6 +1375,85 @@ int mnv_points_colour_table(int32_t format, int32_t basis_dim, uint16_t out[256]
  * first.  MNV_E_INVALID: a null argument, a bound that is not finite, hi[k] < lo[k]. */
 int mnv_points_bounds_to_cube(const float lo[3], const float hi[3], float offset[3], float scale[3]);
 
+/* ------------------------------------------------ merging two trees: one tree placed into a voxel of another
+ * A scene that arrives as tiles (one octree per spatial cell, a point cloud per survey block, a finer tree for one block of a baked scene)
+ * becomes ONE tree: the union of the two structures with a stated rule for the rows, numbered in the canonical breadth-first order of
+ * mnv_point_tree_write -- so merging with the one-chunk empty tree is also the call that puts an arbitrary tree into that order.  More than
+ * two trees are folded, one merge after the other.  Trees whose cubes are not aligned octree voxels of each other are out of scope (that
+ * would be resampling), and interior rows are not re-mipped: call mnv_tree_mip_rows on the result.
+ *
+ * Use: plan (HOST stats; stats.capacity sizes the outputs), write any number of times, destroy.  plan waits for hip_stream (it reads one
+ * level size back per level, at most 23 times); write is asynchronous on it.  The handle keeps the two views' POINTERS: the input arrays
+ * must stay alive and unchanged until the last write has finished.  Two handles share nothing.
+ *
+ * Inputs.  Two device trees A (the base) and B: N == 2, equal data_dim, format and basis_dim, data_dim 2 .. 1024, depths as everywhere
+ * (the root chunk's voxels have depth 1); `parent` is not read; neither input is modified.  A and B may be the same tree.
+ * Placement.  An integer level k in 0 .. 22 and an integer corner (x, y, z) with 0 <= x, y, z < 2^k: B's cube is the depth-k voxel of A's
+ *   cube with that corner; k == 0 means the same cube.  B's offset and scale are not read: the placement is the integers
+ *   (mnv_tree_voxel_cube gives the transform a tile must be built with).  The result has A's offset and scale.
+ * Structure.  A union.  For a voxel (d, i) (depth, integer corner) of the merged cube a source HAS THE VOXEL EXACTLY when its own walk from
+ *   its root reaches a voxel at that depth and corner -- in B's coordinates the depth is d - k and the corner is i minus the placement
+ *   corner scaled by 2^(d-k); otherwise the voxel is COVERED by a shallower leaf of the source or, for B, lies outside B's cube (NONE).
+ *   A merged voxel is interior iff A has it exactly with child != 0, or B has it exactly with child != 0, or d <= k and it lies on the
+ *   path to B's cube: the path voxel of depth l has j_l = 4 x_l + 2 y_l + z_l with x_l = bit k - l of x; path voxels are interior even
+ *   where A is a leaf.  A merged chunk exists iff it is the root or the voxel above it is interior.
+ * Numbering.  Breadth first: the root is 0, then depths 2, 3 ..; within a depth ascending by the Morton code of the voxel above
+ *   (equivalently by (merged index of the parent chunk, j)): mnv_point_tree_write's numbering, with child, parent and capacity as that
+ *   call defines them.
+ * Sources of a voxel.  a_vox is the voxel id (chunk * 8 + j) of A's exact voxel there or of A's covering leaf (it always exists: A spans
+ *   the cube); b_vox the same for B, or none.
+ * Rows.  h() is the binary16 value as binary32 with bits that are not finite read as +0 (the mip contract's h), pos(bits) = h(bits) > 0,
+ *   sat_half() rounds a binary32 to binary16, to nearest even, once, subnormal results kept, and a result that would be infinite becomes
+ *   +-65504.  sigma is column data_dim - 1.
+ *     b_vox none, or !pos(sigma_b):                 A's row, bit for bit.
+ *     otherwise, MNV_MERGE_OVER:                    B's row, bit for bit.
+ *     otherwise, MNV_MERGE_ADD and !pos(sigma_a):   B's row, bit for bit.
+ *     otherwise, MNV_MERGE_ADD and pos(sigma_a):    wa = h(sigma_a), wb = h(sigma_b), W = wa + wb; sigma' = sat_half(W); every other
+ *       column c: sat_half(((wa * h(a_c)) + (wb * h(b_c))) / W).  (binary32, one operation at a time in that order, no contraction,
+ *       correctly rounded division; no value there is a binary32 subnormal or overflows.)
+ *   The same rule gives the rows of interior voxels from whatever the sources hold there.
+ * Sample counts (sample_counts_out or NULL).  The count of the source whose row was taken verbatim; clamp(ca + cb, -32768, 32767) for a
+ *   blended row; a source without a counts array counts 8.
+ * Provenance (src_a_out / src_b_out or NULL): int32 [capacity][8], a_vox and b_vox (-1: none) of every merged voxel -- what a caller needs
+ *   to carry float masters or counts of its own through the merge.
+ * Stats (HOST).  chunks_at_depth[d], capacity (their sum); rows_from_a / rows_from_b / rows_blended: the merged voxels by the line of the
+ *   row rule that applied (they sum to 8 capacity); pushed_a / pushed_b: the merged voxels whose a_vox / b_vox is a shallower covering leaf.
+ * Determinism.  No atomic operation and no launch shape decides an output byte (the stats are integer sums).
+ * Memory.  A handle keeps 17 bytes per chunk of capacity_a + capacity_b + k, the bound of the merged capacity (every merged chunk but the
+ *   root hangs under an interior voxel of A, an interior voxel of B or a path voxel); plan holds 8 bytes more per chunk of that bound and
+ *   the scan's scratch while it runs.
+ * Outputs of write (device): child_out int32 [capacity][8]; data_out [capacity][8][data_dim], 16-byte aligned; parent_out int32 [capacity]
+ * or NULL; sample_counts_out int16 [capacity][8] or NULL; src_a_out, src_b_out or NULL.  They must not overlap the inputs.
+ * MNV_E_INVALID: a null argument; mismatched row formats; a level outside 0 .. 22, a corner outside [0, 2^k), a mode that is neither;
+ * a followed link outside [1, capacity); more merged chunks than capacity_a + capacity_b + k (an input in which a chunk is reached twice);
+ * misaligned rows; host arrays.  MNV_E_UNSUPPORTED: N != 2, data_dim above 1024, an input of more than 2^27 chunks, a merged depth beyond
+ * 23, more than 2^31 - 1 merged chunks.  An input whose links form a cycle ends in one of the two codes (the level bound and the chunk
+ * bound), never in an endless walk.  Arguments are checked before a device is touched. */
+#define MNV_MERGE_OVER 0 /* where B holds density, B's row */
+#define MNV_MERGE_ADD 1  /* where both hold density, the density-weighted blend */
+typedef struct mnv_merge_params {
+    int32_t level, corner[3]; /* the placement k : (x, y, z) */
+    int32_t mode;             /* MNV_MERGE_OVER or MNV_MERGE_ADD */
+    int32_t reserved;         /* 0 */
+} mnv_merge_params;
+typedef struct mnv_merge_stats {
+    int64_t chunks_at_depth[24]; /* entry d = merged chunks of depth d (entry 0 unused, 0) */
+    int64_t capacity;            /* their sum */
+    int64_t rows_from_a, rows_from_b, rows_blended;
+    int64_t pushed_a, pushed_b;
+} mnv_merge_stats;
+typedef struct mnv_tree_merge mnv_tree_merge;
+int mnv_tree_merge_plan(const mnv_tree_view *a, const mnv_tree_view *b, const mnv_merge_params *p, mnv_tree_merge **out, mnv_merge_stats *stats /* HOST */,
+                        void *hip_stream);
+int mnv_tree_merge_write(const mnv_tree_merge *m, int32_t *child_out, uint16_t *data_out, int32_t *parent_out /* or NULL */,
+                         int16_t *sample_counts_out /* or NULL */, int32_t *src_a_out /* or NULL */, int32_t *src_b_out /* or NULL */, void *hip_stream);
+void mnv_tree_merge_destroy(mnv_tree_merge *m);
+/* The cube of the depth-`level` voxel with integer corner `corner` of the cube (offset, scale), as an offset and a scale (HOST): the
+ * transform a tile must be built with so that it merges at level : corner.  scale_out[k] = scale[k] * 2^level (exact),
+ * offset_out[k] = offset[k] * 2^level - corner[k]: the product, then the difference, each rounded once (binary32).  MNV_E_INVALID: a null
+ * argument, a level outside 0 .. 22, a corner outside [0, 2^level). */
+int mnv_tree_voxel_cube(const float offset[3], const float scale[3], int32_t level, const int32_t corner[3], float offset_out[3], float scale_out[3]);
+
 /* (Device times: every entry point launches on the caller's stream and records nothing itself -- bracket the call with two HIP events on that
  * stream, as bench.py does for roofline.achieved.) */
 
@@ -1444,6 +1523,11 @@ int mnv_n3tree_fit_to_tree(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_c
  * n == 0 gives the one-chunk empty tree.  Waits for hip_stream.  Free with mnv_n3tree_free.  The codes of the four calls. */
 int mnv_n3tree_from_points(const mnv_points_params *p, const float *xyz /* device [n][3] */, const uint8_t *rgb /* device [n][3] */, int64_t n,
                            void *hip_stream, mnv_points_stats *stats, mnv_n3tree **out);
+/* N3Tree::merge: mnv_tree_merge_plan and write of two trees that are on the device, `b` placed into `a` as `p` says, as a NEW tree exactly
+ * as mnv_n3tree_make_lod makes one (arrays, parent, sample counts where `a` has them, the accel where `a` has one, host arrays
+ * downloaded; offset, scale and row format of `a`; neither input is changed).  stats: HOST or NULL.  Runs on the null stream and waits
+ * for it.  MNV_E_INVALID: a tree that is not on the device; otherwise the codes of the two calls. */
+int mnv_n3tree_merge(mnv_n3tree *a, const mnv_n3tree *b, const mnv_merge_params *p, mnv_merge_stats *stats, mnv_n3tree **out);
 /* DataFormat::parse / to_string (src/data_format.cpp:5-41) */
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim);
 int mnv_data_format_to_string(int32_t format, int32_t basis_dim, char *buf, size_t buflen);

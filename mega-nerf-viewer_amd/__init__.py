@@ -252,6 +252,24 @@ class PointsStats(C.Structure):
                     chunks_at_depth=list(self.chunks_at_depth), capacity=self.capacity)
 
 
+MERGE_OVER, MERGE_ADD = 0, 1
+
+
+class MergeParams(C.Structure):
+    """mnv_merge_params"""
+    _fields_ = [("level", C.c_int32), ("corner", C.c_int32 * 3), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MergeStats(C.Structure):
+    """mnv_merge_stats"""
+    _fields_ = [("chunks_at_depth", C.c_int64 * 24), ("capacity", C.c_int64), ("rows_from_a", C.c_int64), ("rows_from_b", C.c_int64),
+                ("rows_blended", C.c_int64), ("pushed_a", C.c_int64), ("pushed_b", C.c_int64)]
+
+    def as_dict(self):
+        return dict(chunks_at_depth=list(self.chunks_at_depth), capacity=self.capacity, rows_from_a=self.rows_from_a, rows_from_b=self.rows_from_b,
+                    rows_blended=self.rows_blended, pushed_a=self.pushed_a, pushed_b=self.pushed_b)
+
+
 # every symbol include/mnv.h declares (tests/test_capi_symbols.py checks the export list)
 _SIGNATURES = {
     "mnv_version": (C.c_int, []),
@@ -474,6 +492,11 @@ _SIGNATURES = {
     "mnv_points_colour_table": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
     "mnv_points_bounds_to_cube": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mnv_n3tree_from_points": (C.c_int, [C.POINTER(PointsParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(PointsStats), C.POINTER(C.c_void_p)]),
+    "mnv_tree_merge_plan": (C.c_int, [C.POINTER(TreeView), C.POINTER(TreeView), C.POINTER(MergeParams), C.POINTER(C.c_void_p), C.POINTER(MergeStats), C.c_void_p]),
+    "mnv_tree_merge_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_tree_merge_destroy": (None, [C.c_void_p]),
+    "mnv_tree_voxel_cube": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_n3tree_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MergeParams), C.POINTER(MergeStats), C.POINTER(C.c_void_p)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -850,6 +873,22 @@ class N3Tree:
                                               kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
         out = N3Tree(h.value)
         return (out, kept) if return_counts else out
+
+    def merge(self, other: "N3Tree", level: int = 0, corner=(0, 0, 0), mode="over", return_stats: bool = False):
+        """N3Tree::merge: a new tree on the device, as make_lod's, that is this tree with `other` placed into its depth-`level` voxel with
+        integer corner `corner` (include/mnv.h, "merging two trees"): the union of the two structures in canonical breadth-first order;
+        mode "over": where `other` holds density its row; "add": where both do, the density-weighted blend.  Both trees need
+        move_to_device; neither is changed.  return_stats: also the MergeStats."""
+        p = merge_params(level, corner, mode)
+        h, st = C.c_void_p(), MergeStats()
+        _check(lib().mnv_n3tree_merge(self._h, other._h, C.byref(p), C.byref(st), C.byref(h)))
+        out = N3Tree(h.value)
+        return (out, st) if return_stats else out
+
+    def voxel_cube(self, level: int, corner):
+        """N3Tree::voxel_cube: (offset, scale) a tile must be built with so that it merges into this tree at level : corner."""
+        v = self.host_view()
+        return tree_voxel_cube(tuple(v.offset), tuple(v.scale), level, corner)
 
     def make_culled(self, cams, opt: RenderOptions, weight_thresh: float = 0.0):
         """N3Tree::make_culled: a new tree on the device, as make_lod's, without what the pinhole frames of `cams` cannot see: leaves no ray
@@ -1901,6 +1940,52 @@ class PointTree:
     def write(self, child_out, data_out, parent_out=None, sample_counts_out=None, counts_out=None, stream: int = 0) -> None:
         _check(lib().mnv_point_tree_write(self._h, _ptr(child_out), _ptr(data_out), _ptr(parent_out), _ptr(sample_counts_out), _ptr(counts_out),
                                           C.c_void_p(stream)))
+
+
+def merge_params(level: int = 0, corner=(0, 0, 0), mode="over") -> MergeParams:
+    """mnv_merge_params of a placement level : corner and a mode ("over", "add", or MERGE_OVER / MERGE_ADD)."""
+    if isinstance(mode, str):
+        if mode not in ("over", "add"):
+            raise MnvError(MNV_E_INVALID, "mode is 'over' or 'add'")
+        mode = MERGE_ADD if mode == "add" else MERGE_OVER
+    return MergeParams(int(level), (C.c_int32 * 3)(*[int(c) for c in corner]), int(mode), 0)
+
+
+def tree_voxel_cube(offset, scale, level: int, corner):
+    """mnv_tree_voxel_cube: (offset float32 [3], scale float32 [3]) of the depth-`level` voxel with integer corner `corner` of the cube
+    (offset, scale): scale * 2^level and offset * 2^level - corner.  Host only."""
+    o, s = np.ascontiguousarray(offset, np.float32), np.ascontiguousarray(scale, np.float32)
+    c = np.ascontiguousarray(corner, np.int32)
+    if o.shape != (3,) or s.shape != (3,) or c.shape != (3,):
+        raise MnvError(MNV_E_INVALID, "offset, scale and corner have three entries")
+    offset_out, scale_out = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _check(lib().mnv_tree_voxel_cube(o.ctypes.data, s.ctypes.data, int(level), c.ctypes.data, offset_out.ctypes.data, scale_out.ctypes.data))
+    return offset_out, scale_out
+
+
+class TreeMerge:
+    """mnv_tree_merge: the plan of merging device tree view `b` into `a` at level : corner (include/mnv.h, "merging two trees"); waits for
+    `stream`.  stats (MergeStats) sizes the outputs: write() fills device tensors of stats.capacity chunks, any number of times.  The two
+    views' arrays must stay alive and unchanged while the plan is used."""
+
+    def __init__(self, a: TreeView, b: TreeView, level: int = 0, corner=(0, 0, 0), mode="over", stream: int = 0):
+        self._h = C.c_void_p()
+        self.params = merge_params(level, corner, mode)
+        self.stats = MergeStats()
+        self.data_dim = int(a.data_dim)
+        _check(lib().mnv_tree_merge_plan(C.byref(a), C.byref(b), C.byref(self.params), C.byref(self._h), C.byref(self.stats), C.c_void_p(stream)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().mnv_tree_merge_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def write(self, child_out, data_out, parent_out=None, sample_counts_out=None, src_a_out=None, src_b_out=None, stream: int = 0) -> None:
+        _check(lib().mnv_tree_merge_write(self._h, _ptr(child_out), _ptr(data_out), _ptr(parent_out), _ptr(sample_counts_out), _ptr(src_a_out),
+                                          _ptr(src_b_out), C.c_void_p(stream)))
 
 
 MAX_BATCH = 64

@@ -246,6 +246,22 @@ int mnv_n3tree_from_points(const mnv_points_params *p, const float *xyz, const u
     });
 }
 
+int mnv_n3tree_merge(mnv_n3tree *a, const mnv_n3tree *b, const mnv_merge_params *p, mnv_merge_stats *stats, mnv_n3tree **out) {
+    if (!a || !b || !p || !out) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_merge: null argument");
+    *out = nullptr;
+    return guarded([&] {
+        auto *h = new mnv_n3tree();
+        try {
+            a->tree.merge_into(h->tree, b->tree, *p, nullptr, stats);
+        } catch (...) {
+            delete h;
+            throw;
+        }
+        *out = h;
+        return MNV_OK;
+    });
+}
+
 int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets, const mnv_render_options *opt,
                    const mnv_fit_params *params, int64_t *se_q32_out) {
     if (!t || !cams || !targets || !opt || !params) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit: null argument");

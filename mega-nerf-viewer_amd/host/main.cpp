@@ -67,6 +67,14 @@
 //                    1 and 20: the rates at which the numpy restatement's loss falls at every step on the test suite's fit scene, where
 //                    a leaf of the cut covers a few pixels of a frame; the gradient of a row is a SUM over the rays through its voxel,
 //                    so larger frames want smaller rates).  At most 2^24 pixels over the poses.
+//   --merge B.npz    place the tree of B.npz into the input tree before anything else is done with it (N3Tree::merge: mnv_tree_merge_plan /
+//                    write): the union of the two structures in canonical breadth-first order.  --merge_at k:x,y,z after it names the
+//                    voxel of the base tree that is B's cube (depth k, integer corner); without it k and the corner are derived from the
+//                    two trees' offsets and scales, which must match mnv_tree_voxel_cube bit for bit (no tolerance: otherwise the run
+//                    fails and names --merge_at).  --merge_mode over|add after it (default over): where B holds density its row / where
+//                    both do the density-weighted blend.  Repeatable: the merges fold left to right.  With --points the cloud's tree is
+//                    the base.  The merge happens before --lod, --lod_pixels, --cull and --lod_fit; --save_lod OUT.npz writes the merged
+//                    tree (the level of detail of it when one of those is given too).  Refused with --gpus and --use_splitting.
 //   --points FILE    build the tree from a coloured point cloud in place of opening one (N3Tree::from_points: mnv_point_tree_create / add /
 //                    finish / write).  FILE is an .npz holding `points` (float32 [n][3]) and optionally `colors` (uint8 [n][3], default
 //                    255), or an .obj whose `v x y z [r g b]` lines are the points (float colours become (int)(c * 255 + 0.5), clamped).
@@ -114,6 +122,7 @@ struct Args {
     std::map<std::string, std::string> kv;
     std::string file;
     std::vector<std::pair<std::string, std::string>> mesh_flags;  // --mesh and the --mesh_* flags after it, in command-line order
+    std::vector<std::pair<std::string, std::string>> merge_flags;  // --merge and the --merge_at / --merge_mode after it, in command-line order
     bool has(const std::string &k) const { return kv.count(k) != 0; }
     std::string get(const std::string &k, const std::string &d) const { return has(k) ? kv.at(k) : d; }
     float f(const std::string &k, float d) const { return has(k) ? std::strtof(kv.at(k).c_str(), nullptr) : d; }
@@ -156,6 +165,7 @@ Args parse(int argc, char **argv) {
             }
             a.kv[name] = is_flag && !has_val ? "1" : val;
             if (name.rfind("mesh", 0) == 0) a.mesh_flags.emplace_back(name, val);
+            if (name == "merge" || name == "merge_at" || name == "merge_mode") a.merge_flags.emplace_back(name, val);
         } else {
             a.file = t;
         }
@@ -177,6 +187,8 @@ void usage() {
               "                  [--cull W [--save_lod OUT.npz]]   march (and write) the tree without what this run's poses cannot see (weights <= W)\n"
               "                  [--lod_fit ITERS [--fit_lr_colour X] [--fit_lr_sigma Y]]   with --lod / --lod_pixels: fit that tree's rows to the full\n"
               "                   tree's frames at the poses of this run first (ITERS gradient steps)\n"
+              "                  [--merge B.npz [--merge_at k:x,y,z] [--merge_mode over|add]]... [--save_lod OUT.npz]   place B's tree into a voxel of the\n"
+              "                   input tree (default: the voxel its offset and scale name exactly); repeatable, folds left to right\n"
               "                  [--points FILE.npz|FILE.obj [--points_depth D] [--points_sigma S] [--points_min N] [--points_format RGBA|SH9...]\n"
               "                   [--points_cube ox,oy,oz,sx,sy,sz] [--save_lod OUT.npz]]   build the tree from a coloured point cloud (no npz_file then)\n"
               "                  [--target PREFIX [--target_mask PREFIX] [--ssim]]   score frame f against PREFIX_%04d.ppm (mask: PREFIX_%04d.pgm,\n"
@@ -704,6 +716,86 @@ void tree_from_points(const Args &args, viewer::N3Tree &tree) {
     std::printf("; offset %.9g,%.9g,%.9g scale %.9g,%.9g,%.9g\n", p.offset[0], p.offset[1], p.offset[2], p.scale[0], p.scale[1], p.scale[2]);
 }
 
+
+// --merge B [--merge_at k:x,y,z] [--merge_mode over|add], as often as given, in command-line order (checked before a device is touched)
+struct MergeSpec {
+    std::string path, mode = "over";
+    bool has_at = false;
+    mnv_merge_params p{};
+};
+
+std::vector<MergeSpec> merge_specs(const Args &args) {
+    std::vector<MergeSpec> specs;
+    for (const auto &kv : args.merge_flags) {
+        if (kv.first == "merge") {
+            specs.push_back(MergeSpec{});
+            specs.back().path = kv.second;
+            continue;
+        }
+        if (specs.empty()) throw std::runtime_error("--" + kv.first + " needs --merge in front of it: it applies to the --merge it follows");
+        MergeSpec &s = specs.back();
+        if (kv.first == "merge_at") {
+            long long k = -1, x = -1, y = -1, z = -1;
+            char end = 0;
+            if (std::sscanf(kv.second.c_str(), "%lld:%lld,%lld,%lld%c", &k, &x, &y, &z, &end) != 4 || k < 0 || k > 22 || x < 0 || y < 0 || z < 0 || x >= (1ll << k) ||
+                y >= (1ll << k) || z >= (1ll << k))
+                throw std::runtime_error("--merge_at takes k:x,y,z with k in 0 .. 22 and 0 <= x, y, z < 2^k");
+            s.has_at = true;
+            s.p.level = (int32_t)k, s.p.corner[0] = (int32_t)x, s.p.corner[1] = (int32_t)y, s.p.corner[2] = (int32_t)z;
+        } else {
+            if (kv.second != "over" && kv.second != "add") throw std::runtime_error("--merge_mode is over or add");
+            s.mode = kv.second;
+        }
+        s.p.mode = s.mode == "add" ? MNV_MERGE_ADD : MNV_MERGE_OVER;
+    }
+    return specs;
+}
+
+// --merge: every B placed into the tree so far, left to right; `tree` ends as the merged tree (on the device, host arrays filled)
+void merge_trees(const std::vector<MergeSpec> &specs, std::unique_ptr<viewer::N3Tree> &tree) {
+    if (tree->N <= 0) throw std::runtime_error("--merge needs a base tree (N > 0)");
+    for (const MergeSpec &s : specs) {
+        mnv_merge_params p = s.p;
+        viewer::N3Tree b;
+        b.open(s.path);
+        if (b.N <= 0) throw std::runtime_error("--merge: cannot open " + s.path);
+        if (!s.has_at) {  // the voxel of the base tree that B's offset and scale name exactly
+            bool found = false;
+            for (int k = 0; k <= 22 && !found; ++k) {
+                const float two = (float)(1 << k);
+                bool same = true;
+                for (int i = 0; i < 3; ++i) same = same && b.scale[i] == tree->scale[i] * two;
+                if (!same) continue;
+                int32_t corner[3];
+                bool inside = true;
+                for (int i = 0; i < 3; ++i) {
+                    const double r = std::nearbyint((double)(tree->offset[i] * two) - (double)b.offset[i]);
+                    inside = inside && r >= 0.0 && r < (double)two;
+                    corner[i] = inside ? (int32_t)r : 0;
+                }
+                if (!inside) continue;
+                float o[3], sc[3];
+                mnv_ok(mnv_tree_voxel_cube(tree->offset.data(), tree->scale.data(), k, corner, o, sc), "--merge");
+                if (std::memcmp(o, b.offset.data(), 12) != 0 || std::memcmp(sc, b.scale.data(), 12) != 0) continue;
+                p.level = k, p.corner[0] = corner[0], p.corner[1] = corner[1], p.corner[2] = corner[2];
+                found = true;
+            }
+            if (!found)
+                throw std::runtime_error("--merge: the cube of " + s.path + " is no voxel of the base tree's cube (offset and scale must match exactly): say where it goes with --merge_at k:x,y,z");
+        }
+        if (!tree->on_device()) tree->move_to_device(tree->capacity, true, true);
+        b.move_to_device(b.capacity, false, true);
+        mnv_merge_stats st{};
+        std::unique_ptr<viewer::N3Tree> merged = tree->merge(b, p, nullptr, &st);
+        std::printf("merge: %s at %d:%d,%d,%d (%s): %d + %d -> %lld chunk(s); rows from the base %lld, from the merged tree %lld, blended %lld; pushed down %lld + %lld; per depth:",
+                    s.path.c_str(), p.level, p.corner[0], p.corner[1], p.corner[2], s.mode.c_str(), tree->capacity, b.capacity, (long long)st.capacity, (long long)st.rows_from_a,
+                    (long long)st.rows_from_b, (long long)st.rows_blended, (long long)st.pushed_a, (long long)st.pushed_b);
+        for (int d = 1; d < 24 && st.chunks_at_depth[d]; ++d) std::printf(" %lld", (long long)st.chunks_at_depth[d]);
+        std::printf("\n");
+        tree = std::move(merged);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -714,6 +806,9 @@ int main(int argc, char **argv) {
         if (args.has("points") && args.has("gpus")) throw std::runtime_error("--points builds the tree on one GPU: it cannot be combined with --gpus");
         for (const char *k : {"points_depth", "points_sigma", "points_min", "points_format", "points_cube"})
             if (args.has(k) && !args.has("points")) throw std::runtime_error(std::string("--") + k + " needs --points");
+        const std::vector<MergeSpec> merges = merge_specs(args);
+        if (args.has("merge") && (args.has("gpus") || args.has("use_splitting")))
+            throw std::runtime_error("--merge merges on one GPU into a tree that is then fixed: it cannot be combined with --gpus or --use_splitting");
         if (args.has("help") || (args.file.empty() && !args.has("points"))) {
             usage();
             return args.has("help") ? 0 : 2;
@@ -734,7 +829,7 @@ int main(int argc, char **argv) {
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
         const long lod = args.l("lod", 0);
         if (args.has("lod") && lod < 1) throw std::runtime_error("--lod takes a depth of at least 1");
-        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull") && !args.has("points"))
+        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull") && !args.has("points") && !args.has("merge"))
             throw std::runtime_error("--save_lod needs --lod, --lod_pixels or --cull");
         const float cull_thresh = args.f("cull", 0.f);
         if (args.has("cull") && (!std::isfinite(cull_thresh) || cull_thresh < 0.f)) throw std::runtime_error("--cull takes a finite weight threshold, 0 or more");
@@ -757,15 +852,16 @@ int main(int argc, char **argv) {
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
         if (hipSetDevice((int)args.l("gpu", 0)) != hipSuccess) throw std::runtime_error("no usable HIP device");
 
-        viewer::N3Tree tree;
-        if (args.has("points")) {
-            tree_from_points(args, tree);
-            if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull")) {
-                tree.save_npz(args.get("save_lod", ""));
-                std::printf("save_lod: %d chunks -> %s\n", tree.capacity, args.get("save_lod", "").c_str());
-            }
-        } else {
-            tree.open(args.file);  // main.cpp:528
+        std::unique_ptr<viewer::N3Tree> tree_owner = std::make_unique<viewer::N3Tree>();
+        if (args.has("points"))
+            tree_from_points(args, *tree_owner);
+        else
+            tree_owner->open(args.file);  // main.cpp:528
+        if (!merges.empty()) merge_trees(merges, tree_owner);
+        viewer::N3Tree &tree = *tree_owner;
+        if ((args.has("points") || args.has("merge")) && args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull")) {
+            tree.save_npz(args.get("save_lod", ""));
+            std::printf("save_lod: %d chunks -> %s\n", tree.capacity, args.get("save_lod", "").c_str());
         }
         if (args.has("bounds_only") && tree.N > 0) {  // main.cpp:529-538: keep one empty root chunk
             tree.capacity = 1;

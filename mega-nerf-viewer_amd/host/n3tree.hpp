@@ -153,6 +153,15 @@ struct N3Tree {
     static void from_points_into(N3Tree &out, const mnv_points_params &params, const std::vector<float> &xyz, const std::vector<uint8_t> &rgb,
                                  void *hip_stream = nullptr, mnv_points_stats *stats = nullptr);
 
+    // This tree with `other` placed into its depth-params.level voxel with corner params.corner (include/mnv.h, "merging two trees":
+    // mnv_tree_merge_plan / write): the union of the two structures in canonical breadth-first order, rows by params.mode.  The result is
+    // what make_lod's is: a new tree on the device with this tree's offset / scale / format, its accel / parent / sample counts where it
+    // has them, host arrays downloaded.  Neither tree is changed; both need move_to_device.  stats: or null.  Waits for the stream.
+    std::unique_ptr<N3Tree> merge(const N3Tree &other, const mnv_merge_params &params, void *hip_stream = nullptr, mnv_merge_stats *stats = nullptr) const;
+    void merge_into(N3Tree &out, const N3Tree &other, const mnv_merge_params &params, void *hip_stream = nullptr, mnv_merge_stats *stats = nullptr) const;
+    // The offset and scale a tile must be built with so that it merges into this tree at level : corner (mnv_tree_voxel_cube).
+    void voxel_cube(int level, const std::array<int32_t, 3> &corner, std::array<float, 3> &offset_out, std::array<float, 3> &scale_out) const;
+
     // Write the tree in the svox .npz layout the loader reads (plain `data` form).
     void save_npz(const std::string &path) const;
 
