@@ -206,9 +206,21 @@ int mnv_accel_create_reserved(const mnv_tree_view *device_tree, int64_t max_capa
  *   tree           the view with its NEW capacity; chunks [old_capacity, tree->capacity) were appended under existing
  *                  leaves (mnv_add_children_and_generate_samples + mnv_apply_split_results); needs tree->parent then
  *   changed_nodes  device int32 [n_changed][2] (chunk, child) of existing leaves whose data row was rewritten
- *                  (mnv_apply_sample_results), or NULL
+ *                  (mnv_apply_sample_results), or NULL.  An entry may name a voxel that was split in the same step (it is
+ *                  skipped: the voxel is a link now, its new chunk is patched as an appended one), and an entry may
+ *                  appear more than once (every copy writes the same words).  Without tree->parent (allowed when no
+ *                  chunk was appended) the lookup arrays that a changed leaf reaches are derived again whole.
  * Node words, colour rows and chunk depths of the affected voxels are patched, and of the lookup grids exactly the cells
- * those voxels cover.  After mnv_prune_tree, which renumbers chunks, destroy and create instead.  Synchronises hip_stream.
+ * those voxels cover; the inline cell words and the brick records (mnv_accel_brick_levels) are patched in place with
+ * them, and records are allocated and derived here when the tree first reaches two levels below the second grid.  A
+ * tree that an edit takes past depth 23 is refused with MNV_E_UNSUPPORTED: the accel then describes no frame (its
+ * brick levels read 0) until mnv_accel_rebuild accepts a tree again; mnv_render_voxels still renders the arrays.
+ * After mnv_prune_tree, which renumbers chunks, call mnv_accel_rebuild (or prune with mnv_prune_tree_accel, which
+ * renumbers the accel in place).
+ * Ordering: all work is queued on hip_stream.  The call waits for hip_stream only up to the read-back of its flags
+ * (chunk depths, node words and colour rows are then written); the kernels that patch the lookup grids, inline words
+ * and records are queued behind that and are NOT waited for.  Work queued on hip_stream afterwards is ordered behind
+ * them; a frame on another stream needs its own wait on hip_stream.
  */
 int mnv_accel_refresh(mnv_accel *accel, const mnv_tree_view *tree, int32_t old_capacity, const int32_t *changed_nodes,
                       int32_t n_changed, void *hip_stream);

@@ -18,45 +18,25 @@ import sys
 import numpy as np
 import pytest
 
-import cases
-import hooks
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":   # the child process of the word-for-word test: the import paths that tests/conftest.py gives the suite
+    for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+
+import hooks  # noqa: E402
+from accel_edit_model import EditModel, chunk_depths  # noqa: E402, F401  (chunk_depths: tests/test_devmem_gpu.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def chunk_depths(parent, cap):
-    depth = np.zeros(cap, np.int32)
-    depth[0] = 1
-    pc = parent[:cap] >> 3
-    for _ in range(64):   # level by level, whatever order the chunks are numbered in
-        todo = (depth == 0) & (depth[pc] > 0)
-        todo[0] = False
-        if not todo.any():
-            break
-        depth[todo] = depth[pc[todo]] + 1
-    assert (depth > 0).all()
-    return depth
-
-
-class EditedTree:
-    """Host copy of the reference-layout arrays + their device twins at fixed addresses, edited the way the refinement loop edits them."""
+class EditedTree(EditModel):
+    """The host model (tests/accel_edit_model.py) + device twins of its arrays at fixed addresses, edited the way the refinement loop edits them."""
 
     def __init__(self, mnv, torch, spec, reserve):
-        self.mnv, self.torch = mnv, torch
-        tree = cases.make_tree(mnv, spec)
-        self.tree = tree
-        v = tree.host_view()
-        data, child, parent = tree.host_arrays()
-        self.cap, self.dd, self.max_cap = v.capacity, v.data_dim, v.capacity + reserve
-        self.data = np.zeros((self.max_cap, 8, self.dd), np.float16)
-        self.child = np.zeros((self.max_cap, 8), np.int32)
-        self.parent = np.zeros(self.max_cap, np.int32)
-        self.data[:self.cap], self.child[:self.cap], self.parent[:self.cap] = data.view(np.float16).reshape(self.cap, 8, self.dd), child, parent
-        self.depth = np.zeros(self.max_cap, np.int32)
-        self.depth[:self.cap] = chunk_depths(parent, self.cap)
-        self.counts = np.random.default_rng(99).integers(0, 13, (self.max_cap, 8)).astype(np.int16)
+        super().__init__(mnv, spec, reserve)
+        self.torch = torch
+        v = self.tree.host_view()
         self.d = dict(data=torch.from_numpy(self.data.view(np.int16)).cuda(), child=torch.from_numpy(self.child).cuda(), parent=torch.from_numpy(self.parent).cuda(),
                       counts=torch.from_numpy(self.counts).cuda())
         tv = mnv.TreeView()
@@ -70,53 +50,26 @@ class EditedTree:
     def close(self):
         self.mnv.accel_destroy(self.accel)
 
-    def random_row(self, rng, empty_prob):
-        row = (rng.standard_normal(self.dd) * 0.7).astype(np.float16)
-        row[self.dd - 1] = np.float16(0.0) if rng.random() < empty_prob else np.float16(rng.uniform(0.02, 40.0))
-        return row
-
-    def edit(self, rng, n_split, n_change, depths_wanted, empty_prob=0.5):
-        """n_split leaves become inner voxels with eight new leaves each (a third of them under chunks appended in this very round),
-        n_change leaf rows are rewritten; then ONE mnv_accel_refresh, as the loop issues it."""
+    def upload(self):
+        """The device twins take the host arrays (the tree view's capacity with them)."""
         torch = self.torch
-        old_cap = self.cap
-        for k in range(n_split):
-            if self.cap >= self.max_cap:
-                break
-            lo = old_cap if (k % 3 == 2 and self.cap > old_cap) else 0    # chained: a leaf of a chunk that is new in this round
-            cand = np.argwhere(self.child[lo:self.cap] == 0)
-            cand[:, 0] += lo
-            want = depths_wanted[k % len(depths_wanted)]
-            at = cand[self.depth[cand[:, 0]] == want]
-            pick = at if len(at) else cand
-            c, s = pick[rng.integers(len(pick))]
-            if self.depth[c] >= 22:
-                continue
-            nc = self.cap
-            self.child[c, s] = nc - c
-            self.parent[nc] = c * 8 + s
-            self.child[nc] = 0
-            self.depth[nc] = self.depth[c] + 1
-            for j in range(8):
-                self.data[nc, j] = self.random_row(rng, empty_prob)
-            self.cap += 1
-        changed = []
-        leaves = np.argwhere(self.child[:old_cap] == 0)
-        for k in range(n_change):
-            want = depths_wanted[k % len(depths_wanted)]
-            at = leaves[self.depth[leaves[:, 0]] == want]
-            pick = at if len(at) else leaves
-            c, s = pick[rng.integers(len(pick))]
-            if self.child[c, s] != 0:
-                continue   # split in this round
-            self.data[c, s] = self.random_row(rng, empty_prob)
-            changed.append((c, s))
         self.d["data"].copy_(torch.from_numpy(self.data.view(np.int16)))
         self.d["child"].copy_(torch.from_numpy(self.child))
         self.d["parent"].copy_(torch.from_numpy(self.parent))
         self.tv.capacity = self.cap
-        ch = torch.from_numpy(np.asarray(changed, np.int32).reshape(-1, 2)).cuda() if changed else None
+
+    def refresh(self, old_cap, changed):
+        """ONE mnv_accel_refresh for the chunks appended since old_cap and the (chunk, slot) rows in `changed`, as the loop issues it."""
+        ch = self.torch.from_numpy(np.asarray(changed, np.int32).reshape(-1, 2)).cuda() if len(changed) else None
         self.mnv.accel_refresh(self.accel, self.tv, old_cap, changed_nodes=ch)
+        self.refreshed()
+
+    def edit(self, rng, n_split, n_change, depths_wanted, empty_prob=0.5):
+        """n_split leaves become inner voxels with eight new leaves each (a third of them under chunks appended in this very round),
+        n_change leaf rows are rewritten; then ONE mnv_accel_refresh, as the loop issues it."""
+        old_cap, changed = self.edit_host(rng, n_split, n_change, depths_wanted, empty_prob)
+        self.upload()
+        self.refresh(old_cap, changed)
         return self.cap - old_cap, len(changed)
 
 
@@ -251,9 +204,6 @@ def test_patched_lookup_words_equal_a_fresh_derivation_word_for_word(mnv, torch_
 
 
 if __name__ == "__main__":   # the child process of the word-for-word test
-    for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     import torch
 
     import mega_nerf_viewer_amd as m
