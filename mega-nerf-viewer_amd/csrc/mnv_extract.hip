@@ -423,8 +423,6 @@ struct U32ToU64 {
     __host__ __device__ unsigned long long operator()(uint32_t x) const { return (unsigned long long)x; }
 };
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 // row format of the accel as the march sees it: -1 RGBA, 1 / 4 / 9 / 16 / 25 SH, anything else unsupported (-2)
 int row_basis(const mnv::AccelView &A) {
     if (A.format == MNV_FORMAT_SH && A.basis_dim >= 0) {
@@ -450,11 +448,7 @@ TreeRef tree_ref(const mnv_accel *a) {
 
 int require_device() {
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
-    return MNV_OK;
+    return mnv::current_device(&dev);
 }
 
 }  // namespace
@@ -514,12 +508,12 @@ int extract(const mnv_accel *accel, const mnv_extract_params *prm, hipStream_t s
         return rc;
     // (a) candidates, compacted in ascending brick order
     (void)hipEventRecord(W.ev[0].get(), stream);
-    hipLaunchKernelGGL(candidate_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, stream, T, level, prm->iso, all ? 1 : 0, n_bricks, W.flag.get(), W.fault.get());
+    hipLaunchKernelGGL(candidate_kernel, dim3(mnv::blocks_for(n_bricks)), dim3(256), 0, stream, T, level, prm->iso, all ? 1 : 0, n_bricks, W.flag.get(), W.fault.get());
     size_t t = tmp_bytes;
     if ((rc = check_hip(rocprim::exclusive_scan(W.tmp.get(), t, (const uint32_t *)W.flag.get(), W.pos.get(), 0u, (size_t)n_bricks, rocprim::plus<uint32_t>(), stream),
                         "exclusive_scan(candidates)")))
         return rc;
-    hipLaunchKernelGGL(candidate_list_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, stream, W.flag.get(), W.pos.get(), n_bricks, W.list.get(), W.totals.get());
+    hipLaunchKernelGGL(candidate_list_kernel, dim3(mnv::blocks_for(n_bricks)), dim3(256), 0, stream, W.flag.get(), W.pos.get(), n_bricks, W.list.get(), W.totals.get());
     (void)hipEventRecord(W.ev[1].get(), stream);
     unsigned long long totals[3] = {0, 0, 0};
     uint32_t fault = 0;
@@ -566,7 +560,7 @@ int extract(const mnv_accel *accel, const mnv_extract_params *prm, hipStream_t s
     }
     (void)hipEventRecord(W.ev[4].get(), stream);
     if (n_verts > 0 && colour) {
-        const dim3 grid(blocks_for((int64_t)n_verts)), block(256);
+        const dim3 grid(mnv::blocks_for((int64_t)n_verts)), block(256);
         switch (basis) {
             case -1: hipLaunchKernelGGL(colour_kernel<0>, grid, block, 0, stream, T, vert, (int64_t)n_verts); break;
             case 1: hipLaunchKernelGGL(colour_kernel<1>, grid, block, 0, stream, T, vert, (int64_t)n_verts); break;
@@ -605,7 +599,7 @@ int mnv_accel_sample_points(const mnv_accel *accel, const float *points, int64_t
     if (rc) return rc;
     if (accel->view.capacity < 1 || !accel->view.nodes) return set_error(MNV_E_INVALID, "mnv_accel_sample_points: the accel holds no tree");
     if (n == 0 || (!voxel_out && !depth_out && !sigma_out)) return MNV_OK;
-    hipLaunchKernelGGL(sample_points_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)hip_stream, tree_ref(accel), points, n, voxel_out, depth_out,
+    hipLaunchKernelGGL(sample_points_kernel, dim3(mnv::blocks_for(n)), dim3(256), 0, (hipStream_t)hip_stream, tree_ref(accel), points, n, voxel_out, depth_out,
                        sigma_out);
     return check_hip(hipGetLastError(), "sample_points_kernel");
 }

@@ -22,6 +22,31 @@ int alloc_pair(Mirrored<T> &m, size_t count, const char *dev_text, const char *p
     return check_hip(e, pinned ? pinned_text : dev_text);
 }
 
+// the current HIP device of the calling thread
+inline int current_device(int *dev) {
+    if (hipGetDevice(dev) != hipSuccess || *dev < 0) {
+        (void)hipGetLastError();
+        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
+    }
+    return MNV_OK;
+}
+// is p device memory (not host, pinned or managed)
+inline bool on_device(const void *p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uint8_t *x = (const uint8_t *)a, *y = (const uint8_t *)b;
+    return x < y + nb && y < x + na;
+}
+// workgroups of a launch with `per` items each
+inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
 // Fill the camera / option / rodrigues part of the kernel argument block.
 int fill_params(FrameParams &P, const mnv_camera *cam, const mnv_render_options *opt, mnv_rect tile);
 

@@ -11,32 +11,23 @@
 // are the same in every lane), so the eye and the threshold of a view come through scalar loads; a lane stops testing at the first view
 // that passes and the wavefront leaves the loop when no lane is left.
 //
-// Cut: mnv_tree_truncate's three steps with keep[c] != 0 as the survivor predicate: ranks from an exclusive rocPRIM scan, a thread per
-// (chunk, voxel) for links / parents / sample counts, a thread per 16-byte segment for the rows.
+// Cut: the compaction of mnv_tree_walk.h with keep[c] != 0 as the survivor predicate.
 //
 // Build flags as everywhere: -ffp-contract=off, correctly rounded division; binary32 subnormals are kept (the default of the target).
 #include <hip/hip_runtime.h>
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/functional.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <cmath>
 #include <mutex>
 #include <vector>
 
-#include "mnv_internal.h"
+#include "mnv_tree_walk.h"
 
 using mnv::check_hip;
 using mnv::set_error;
 
 namespace {
 
-constexpr int kMaxLodDepth = 23;  // as the packed accel
-constexpr int kMaxDataDim = 1024;  // as mnv_tree_truncate
 constexpr int kMaxViews = 4096;
-
-unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // ---------------------------------------------------------------------------------------------------- selection
 
@@ -92,122 +83,12 @@ __global__ void __launch_bounds__(256) lodv_level_kernel(const int32_t *__restri
             push = true;
         }
     }
-    const unsigned lane = __lane_id();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const unsigned long long m = __ballot(push);
-    if (m) {
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if ((int)lane == leader) base = atomicAdd(&ctr[0], (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (push) {
-            const unsigned long long slot = base + (unsigned long long)__popcll(m & below);
-            if ((int64_t)slot < cap_next)
-                next[slot] = make_int4(nid, ix, iy, iz);
-            else
-                atomicOr(&ctr[1], 2ull);  // more arrivals than chunks left
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------- cut
-
-struct KeptFlag {
-    __host__ __device__ int32_t operator()(uint8_t k) const { return k != 0 ? 1 : 0; }
-};
-
-// thread per (chunk, voxel) of the input: links, parents and sample counts of the survivors
-__global__ void __launch_bounds__(256) lodv_cut_topology_kernel(const int32_t *__restrict__ child, const int16_t *__restrict__ counts, const uint8_t *__restrict__ keep,
-                                                                 const int32_t *__restrict__ rank, int32_t capacity, int32_t new_capacity, int32_t *__restrict__ child_out,
-                                                                 int32_t *__restrict__ parent_out, int16_t *__restrict__ counts_out) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (int64_t)capacity * 8) return;
-    const int32_t c = (int32_t)(t >> 3);
-    const int j = (int)(t & 7);
-    if (keep[c] == 0) return;
-    const int32_t nc = rank[c];
-    if (nc < 0 || nc >= new_capacity) return;
-    const int64_t o = (int64_t)nc * 8 + j;
-    const int32_t ch = child[t];
-    int32_t link = 0;
-    if (ch != 0) {
-        const int64_t k = (int64_t)c + ch;
-        if (k >= 1 && k < capacity && keep[k] != 0) {
-            const int32_t nk = rank[k];
-            if (nk >= 0 && nk < new_capacity) {
-                link = nk - nc;
-                if (parent_out) parent_out[nk] = (int32_t)o;
-            }
-        }
-    }
-    child_out[o] = link;
-    if (counts_out) counts_out[o] = counts[t];
-    if (parent_out && c == 0 && j == 0) parent_out[nc] = -1;
-}
-
-// thread per 16-byte segment of the input rows: the survivors' rows to their new place
-__global__ void __launch_bounds__(256) lodv_cut_rows_kernel(const uint4 *__restrict__ in4, const uint8_t *__restrict__ keep, const int32_t *__restrict__ rank, int64_t n_seg,
-                                                             int32_t dd, int32_t new_capacity, uint4 *__restrict__ out4) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_seg) return;
-    const int64_t c = t / dd;
-    if (keep[c] == 0) return;
-    const int32_t nc = rank[c];
-    if (nc < 0 || nc >= new_capacity) return;
-    out4[(int64_t)nc * dd + (t - c * dd)] = in4[t];
-}
-
-// ---------------------------------------------------------------------------------------------------- host
-
-// scratch of both calls, one per (device, HIP stream): calls on a stream are ordered, so the next call may reuse what the previous one
-// still reads.  Heap objects that live as long as the process (no hipFree after the runtime went).
-struct StreamScratch {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    mnv::Buffer<uint8_t> bytes;  // cut: ranks and the scan's temporary
-    mnv::Buffer<int4> order;     // selection: the level lists, [capacity]
-    mnv::Buffer<int32_t> mark;   // ... a word per chunk: reached
-    mnv::Buffer<float> views;    // ... q [n_views][4], then R2 [n_views][24]
-    mnv::Mirrored<unsigned long long> ctr;
-};
-std::mutex g_scratch_mutex;
-std::vector<StreamScratch *> *const g_scratch = new std::vector<StreamScratch *>();
-
-StreamScratch &scratch_of(int dev, hipStream_t stream) {  // (under g_scratch_mutex)
-    for (StreamScratch *e : *g_scratch)
-        if (e->device == dev && e->stream == stream) return *e;
-    g_scratch->push_back(new StreamScratch());
-    g_scratch->back()->device = dev;
-    g_scratch->back()->stream = stream;
-    return *g_scratch->back();
-}
-
-bool on_device(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
-
-int check_view(const mnv_tree_view *t, const char *who) {
-    if (!t || !t->data || !t->child) return set_error(MNV_E_INVALID, std::string(who) + ": null tree view / arrays");
-    if (t->N != 2) return set_error(MNV_E_UNSUPPORTED, std::string(who) + ": only N == 2 trees");
-    if (t->capacity < 1) return set_error(MNV_E_INVALID, std::string(who) + ": a tree has at least its root chunk");
-    if (t->data_dim < 2) return set_error(MNV_E_INVALID, std::string(who) + ": data_dim must be at least 2");
-    if (t->data_dim > kMaxDataDim) return set_error(MNV_E_UNSUPPORTED, std::string(who) + ": data_dim above 1024");
-    if (((uintptr_t)t->data & 15u) != 0) return set_error(MNV_E_INVALID, std::string(who) + ": the data array must be 16-byte aligned");
-    if (!on_device(t->child) || !on_device(t->data)) return set_error(MNV_E_INVALID, std::string(who) + ": the tree view must hold device arrays");
-    return MNV_OK;
-}
-
-int current_device(int *dev) {
-    if (hipGetDevice(dev) != hipSuccess || *dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
-    return MNV_OK;
+    mnv::wave_append(push, &ctr[0], [=](unsigned long long slot) {
+        if ((int64_t)slot < cap_next)
+            next[slot] = make_int4(nid, ix, iy, iz);
+        else
+            atomicOr(&ctr[1], 2ull);  // more arrivals than chunks left
+    });
 }
 
 }  // namespace
@@ -220,7 +101,7 @@ int mnv_tree_select_cut(const mnv_tree_view *tree, const mnv_lod_view *views, in
     int rc;
     if (!views || !keep_out || !kept_at_depth) return set_error(MNV_E_INVALID, std::string(who) + ": null views / output");
     for (int d = 0; d < 24; ++d) kept_at_depth[d] = 0;
-    if ((rc = check_view(tree, who))) return rc;
+    if ((rc = mnv::check_view(tree, who))) return rc;
     if (n_views < 1 || n_views > kMaxViews) return set_error(MNV_E_INVALID, std::string(who) + ": n_views outside [1, 4096]");
     if (!std::isfinite(pixels) || pixels < 0.f) return set_error(MNV_E_INVALID, std::string(who) + ": pixels must be finite and not negative");
     if (min_depth < 1 || max_depth < min_depth) return set_error(MNV_E_INVALID, std::string(who) + ": need 1 <= min_depth <= max_depth");
@@ -260,11 +141,11 @@ int mnv_tree_select_cut(const mnv_tree_view *tree, const mnv_lod_view *views, in
     hipStream_t stream = (hipStream_t)hip_stream;
     const int32_t cap = tree->capacity;
     int dev = -1;
-    if ((rc = current_device(&dev))) return rc;
+    if ((rc = mnv::current_device(&dev))) return rc;
 
     // the scratch is kept between calls (grow-only): the call holds the lock until it has waited for the stream
-    std::lock_guard<std::mutex> lock(g_scratch_mutex);
-    StreamScratch &S = scratch_of(dev, stream);
+    std::lock_guard<std::mutex> lock(mnv::stream_scratch_mutex());
+    mnv::StreamScratch &S = mnv::stream_scratch(dev, stream);
     struct Drain {  // ... also when an error leaves this function early: queued work may still use the scratch and `table`
         hipStream_t s;
         ~Drain() { (void)hipStreamSynchronize(s); }
@@ -287,27 +168,14 @@ int mnv_tree_select_cut(const mnv_tree_view *tree, const mnv_lod_view *views, in
         (rc = check_hip(hipMemcpyAsync(S.views.get(), table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, stream), "view tables")) ||
         (rc = check_hip(hipMemsetAsync(S.ctr.dev.get(), 0, 16, stream), "level counters")))
         return rc;
-    int64_t offset[26] = {0};  // level d's entries: order[offset[d] .. offset[d + 1])
-    offset[2] = 1;
-    kept_at_depth[1] = 1;
-    for (int d = 1; d < max_depth; ++d) {
-        const int64_t n_front = offset[d + 1] - offset[d], cap_next = (int64_t)cap - offset[d + 1];
+    mnv::LevelLists L;
+    rc = mnv::walk_loop(L, cap, max_depth, S.ctr, who, "lodv_level_kernel", stream, [&](int d, int64_t front, int64_t n_front, int64_t next, int64_t cap_next) {
         const LevelArgs A = {cap, d, d < min_depth ? 1 : 0, n_views, std::ldexp(1.f, -d), tree->scale[0], tree->scale[1], tree->scale[2]};
-        hipLaunchKernelGGL(lodv_level_kernel, dim3(blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, order + offset[d], n_front, A, q_dev, r2_dev,
-                           order + offset[d + 1], cap_next, S.mark.get(), keep_out, S.ctr.dev.get());
-        if ((rc = check_hip(hipGetLastError(), "lodv_level_kernel")) ||
-            (rc = check_hip(hipMemcpyAsync(S.ctr.host.get(), S.ctr.dev.get(), 16, hipMemcpyDeviceToHost, stream), "level counters")) ||
-            (rc = check_hip(hipMemsetAsync(S.ctr.dev.get(), 0, 8, stream), "level counters")) || (rc = check_hip(hipStreamSynchronize(stream), "lodv_level_kernel")))
-            return rc;
-        const unsigned long long fault = S.ctr.host.get()[1];
-        if (fault & 1ull) return set_error(MNV_E_INVALID, std::string(who) + ": a child link leaves the tree (outside [1, capacity))");
-        if (fault & 2ull) return set_error(MNV_E_INVALID, std::string(who) + ": a chunk is reached twice (not a tree)");
-        const int64_t n_next = (int64_t)S.ctr.host.get()[0];
-        if (n_next == 0) break;
-        if (d + 1 > kMaxLodDepth) return set_error(MNV_E_UNSUPPORTED, std::string(who) + ": tree deeper than 23 levels");
-        offset[d + 2] = offset[d + 1] + n_next;
-        kept_at_depth[d + 1] = n_next;
-    }
+        hipLaunchKernelGGL(lodv_level_kernel, dim3(mnv::blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, order + front, n_front, A, q_dev, r2_dev, order + next,
+                           cap_next, S.mark.get(), keep_out, S.ctr.dev.get());
+    });
+    for (int d = 1; d <= L.levels; ++d) kept_at_depth[d] = L.size(d);
+    if (rc) return rc;
     return check_hip(hipStreamSynchronize(stream), who);
 }
 
@@ -316,21 +184,16 @@ int mnv_tree_cut(const mnv_tree_view *tree, const uint8_t *keep, int32_t new_cap
     const char *who = "mnv_tree_cut";
     int rc;
     if (!keep || !child_out || !data_out) return set_error(MNV_E_INVALID, std::string(who) + ": null keep / output");
-    if ((rc = check_view(tree, who))) return rc;
+    if ((rc = mnv::check_view(tree, who))) return rc;
     if (new_capacity < 1 || new_capacity > tree->capacity) return set_error(MNV_E_INVALID, std::string(who) + ": new_capacity outside [1, capacity]");
     if (((uintptr_t)data_out & 15u) != 0) return set_error(MNV_E_INVALID, std::string(who) + ": data_out must be 16-byte aligned");
-    if (!on_device(keep)) return set_error(MNV_E_INVALID, std::string(who) + ": keep must be a device array");
+    if (!mnv::on_device(keep)) return set_error(MNV_E_INVALID, std::string(who) + ": keep must be a device array");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int32_t cap = tree->capacity, dd = tree->data_dim;
     int dev = -1;
-    if ((rc = current_device(&dev))) return rc;
-    auto flags = rocprim::make_transform_iterator(keep, KeptFlag{});
-    size_t tmp_bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, tmp_bytes, flags, (int32_t *)nullptr, 0, (size_t)cap, rocprim::plus<int32_t>(), stream);
-    const size_t rank_bytes = ((size_t)cap * 4 + 255) & ~(size_t)255, need = rank_bytes + tmp_bytes + 256;
+    if ((rc = mnv::current_device(&dev))) return rc;
 
-    std::lock_guard<std::mutex> lock(g_scratch_mutex);
-    StreamScratch &S = scratch_of(dev, stream);
+    std::lock_guard<std::mutex> lock(mnv::stream_scratch_mutex());
+    mnv::StreamScratch &S = mnv::stream_scratch(dev, stream);
     if (!S.ctr && (rc = mnv::alloc_pair(S.ctr, 2, "hipMalloc(level counters)", "hipHostMalloc(level counters)"))) return rc;
     // the root's byte decides whether there is a tree to cut: read it behind what the stream holds (the one wait of this call)
     uint8_t *root_keep = reinterpret_cast<uint8_t *>(S.ctr.host.get());
@@ -338,19 +201,7 @@ int mnv_tree_cut(const mnv_tree_view *tree, const uint8_t *keep, int32_t new_cap
         (rc = check_hip(hipStreamSynchronize(stream), "read keep[0]")))
         return rc;
     if (*root_keep == 0) return set_error(MNV_E_INVALID, std::string(who) + ": the root chunk is not kept (keep[0] == 0)");
-    if ((rc = check_hip(mnv::grow(S.bytes, need, need + need / 4, stream, true), "hipMalloc(cut scratch)"))) return rc;
-    int32_t *rank = reinterpret_cast<int32_t *>(S.bytes.get());
-    if ((rc = check_hip(rocprim::exclusive_scan(S.bytes.get() + rank_bytes, tmp_bytes, flags, rank, 0, (size_t)cap, rocprim::plus<int32_t>(), stream), "exclusive_scan")))
-        return rc;
-    if (parent_out && (rc = check_hip(hipMemsetAsync(parent_out, 0xff, (size_t)new_capacity * 4, stream), "clear parents"))) return rc;
-    const int16_t *counts = sample_counts_out ? tree->sample_counts : nullptr;
-    hipLaunchKernelGGL(lodv_cut_topology_kernel, dim3(blocks_for((int64_t)cap * 8)), dim3(256), 0, stream, tree->child, counts, keep, rank, cap, new_capacity, child_out,
-                       parent_out, counts ? sample_counts_out : nullptr);
-    if ((rc = check_hip(hipGetLastError(), "lodv_cut_topology_kernel"))) return rc;
-    const int64_t n_seg = (int64_t)cap * dd;
-    hipLaunchKernelGGL(lodv_cut_rows_kernel, dim3(blocks_for(n_seg)), dim3(256), 0, stream, reinterpret_cast<const uint4 *>(tree->data), keep, rank, n_seg, dd, new_capacity,
-                       reinterpret_cast<uint4 *>(data_out));
-    return check_hip(hipGetLastError(), "lodv_cut_rows_kernel");
+    return mnv::compact_tree(tree, mnv::ByteKeep{keep}, new_capacity, child_out, data_out, parent_out, sample_counts_out, "cut", S, stream);
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@
 #include <cstring>
 #include <memory>
 
-#include "mnv_internal.h"
+#include "mnv_tree_walk.h"
 
 using mnv::check_hip;
 using mnv::set_error;
@@ -42,8 +42,6 @@ constexpr int kMaxMergeLevel = 22;      // B's root chunk then has depth 23
 constexpr int kMaxDataDim = 1024;       // as mnv_tree_truncate
 constexpr int32_t kMaxChunks = 1 << 27;  // of an input: a voxel id (chunk * 8 + j) is an int32, and eight times a level's size a uint32
 constexpr int32_t kNone = INT32_MIN, kPath = INT32_MIN + 1;  // b_ref: outside B's cube / the chunk holds a voxel above B's cube
-
-unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // ---------------------------------------------------------------------------------------------------- the walk
 
@@ -186,29 +184,6 @@ __global__ void __launch_bounds__(256) merge_emit_kernel(Inputs I, LevelArgs L, 
 
 // ---------------------------------------------------------------------------------------------------- rows
 
-// h(bits): the binary16 value as binary32; bits that are not finite read as +0
-__device__ __forceinline__ float merge_h(uint32_t b) {
-    const uint32_t e = (b >> 10) & 31u, m = b & 0x3ffu, s = (b & 0x8000u) << 16;
-    if (e == 31u) return 0.f;
-    if (e == 0u) return __uint_as_float(s | __float_as_uint((float)m * 0x1p-24f));  // (a subnormal half is a normal float)
-    return __uint_as_float(s | ((e + 112u) << 23) | (m << 13));
-}
-
-// sat_half(): binary32 -> binary16 bits, round to nearest even, once; subnormal results kept, a result that would be infinite is 65504
-__device__ __forceinline__ uint16_t merge_sat_half(float f) {
-    uint32_t x = __float_as_uint(f);
-    const uint32_t s = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x47800000u) return (uint16_t)(s | 0x7bffu);  // 65536 and more (no NaN arrives here)
-    if (x < 0x38800000u) {  // below 2^-14: the sum with 0.5 has the spacing of binary16 subnormals (2^-24) and is rounded by the add
-        const float r = __uint_as_float(x) + 0.5f;
-        return (uint16_t)(s | (__float_as_uint(r) - 0x3f000000u));
-    }
-    x += 0xfffu + ((x >> 13) & 1u);
-    x = (x - 0x38000000u) >> 13;
-    return (uint16_t)(s | (x >= 0x7c00u ? 0x7bffu : x));
-}
-
 struct WriteArgs {
     const int32_t *a_ref, *b_ref, *first_child, *parent;
     const uint8_t *mask;
@@ -219,11 +194,6 @@ struct WriteArgs {
     int32_t *parent_out;
     int16_t *counts_out;
     int32_t *src_a_out, *src_b_out;
-};
-
-union Seg16 {
-    uint4 v;
-    uint16_t h[8];
 };
 
 __global__ void __launch_bounds__(256) merge_write_kernel(Inputs I, WriteArgs P) {
@@ -267,7 +237,7 @@ __global__ void __launch_bounds__(256) merge_write_kernel(Inputs I, WriteArgs P)
         return;
     }
     for (int s = gl; s < dd; s += G) {
-        Seg16 o;
+        mnv::Seg16 o;
         for (int i = 0; i < 8; ++i) {
             const int at = 8 * s + i, j = at / dd, col = at - j * dd;
             const int4 vi = voxel_info[grp][j];
@@ -276,12 +246,12 @@ __global__ void __launch_bounds__(256) merge_write_kernel(Inputs I, WriteArgs P)
             } else if (vi.z == 1) {
                 o.h[i] = I.b_data[(int64_t)vi.y * dd + col];
             } else {
-                const float wa = merge_h((uint32_t)vi.w & 0xffffu), wb = merge_h((uint32_t)vi.w >> 16), W = wa + wb;
+                const float wa = mnv::h((uint32_t)vi.w & 0xffffu), wb = mnv::h((uint32_t)vi.w >> 16), W = wa + wb;
                 if (col == dd - 1) {
-                    o.h[i] = merge_sat_half(W);
+                    o.h[i] = mnv::sat_half(W);
                 } else {
-                    const float ta = wa * merge_h(I.a_data[(int64_t)vi.x * dd + col]), tb = wb * merge_h(I.b_data[(int64_t)vi.y * dd + col]);
-                    o.h[i] = merge_sat_half((ta + tb) / W);
+                    const float ta = wa * mnv::h(I.a_data[(int64_t)vi.x * dd + col]), tb = wb * mnv::h(I.b_data[(int64_t)vi.y * dd + col]);
+                    o.h[i] = mnv::sat_half((ta + tb) / W);
                 }
             }
         }
@@ -290,15 +260,6 @@ __global__ void __launch_bounds__(256) merge_write_kernel(Inputs I, WriteArgs P)
 }
 
 // ---------------------------------------------------------------------------------------------------- host
-
-bool on_device(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
 
 // what can be said about a view before a device is touched
 int check_view_host(const mnv_tree_view *t, const char *who, const char *which) {
@@ -339,13 +300,10 @@ int mnv_tree_merge_plan(const mnv_tree_view *a, const mnv_tree_view *b, const mn
             return set_error(MNV_E_INVALID, std::string(who) + ": a corner outside [0, 2^level)");
     if (p->mode != MNV_MERGE_OVER && p->mode != MNV_MERGE_ADD) return set_error(MNV_E_INVALID, std::string(who) + ": mode must be over (0) or add (1)");
     for (const mnv_tree_view *t : {a, b})
-        if (!on_device(t->child) || !on_device(t->data) || (t->sample_counts && !on_device(t->sample_counts)))
+        if (!mnv::on_device(t->child) || !mnv::on_device(t->data) || (t->sample_counts && !mnv::on_device(t->sample_counts)))
             return set_error(MNV_E_INVALID, std::string(who) + ": the tree views must hold device arrays");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
+    if ((rc = mnv::current_device(&dev))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     // every merged chunk but the root lies under an interior voxel of A, an interior voxel of B or a path voxel
     const int64_t bound = (int64_t)a->capacity + b->capacity + p->level;
@@ -387,7 +345,7 @@ int mnv_tree_merge_plan(const mnv_tree_view *a, const mnv_tree_view *b, const mn
         L.mask = m->mask.get() + first, L.count = count.get(), L.first_child = m->first_child.get() + first;
         L.a_next = m->a_ref.get() + first + n, L.b_next = m->b_ref.get() + first + n, L.parent_next = m->parent.get() + first + n;
         L.ctr = ctr.dev.get();
-        hipLaunchKernelGGL(merge_level_kernel, dim3(std::min(blocks_for(n * 8), (unsigned)kLevelGrid)), dim3(256), 0, stream, m->in, L);
+        hipLaunchKernelGGL(merge_level_kernel, dim3(std::min(mnv::blocks_for(n * 8), (unsigned)kLevelGrid)), dim3(256), 0, stream, m->in, L);
         if ((rc = check_hip(hipGetLastError(), "merge_level_kernel"))) return rc;
         size_t tb = tmp_bytes;
         if ((rc = check_hip(rocprim::exclusive_scan(tmp.get(), tb, count.get(), scanned.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream), "exclusive_scan")) ||
@@ -400,7 +358,7 @@ int mnv_tree_merge_plan(const mnv_tree_view *a, const mnv_tree_view *b, const mn
         const int64_t n_next = (int64_t)tail[0] + tail[1];
         if (n_next == 0) {
             L.count = scanned.get();  // (first_child of the deepest level: never followed, but defined)
-            hipLaunchKernelGGL(merge_emit_kernel, dim3(blocks_for(n * 8)), dim3(256), 0, stream, m->in, L, n_next);
+            hipLaunchKernelGGL(merge_emit_kernel, dim3(mnv::blocks_for(n * 8)), dim3(256), 0, stream, m->in, L, n_next);
             if ((rc = check_hip(hipGetLastError(), "merge_emit_kernel"))) return rc;
             first += n;
             break;
@@ -410,7 +368,7 @@ int mnv_tree_merge_plan(const mnv_tree_view *a, const mnv_tree_view *b, const mn
         if (first + n + n_next > bound)
             return set_error(MNV_E_INVALID, std::string(who) + ": more merged chunks than the inputs hold (a chunk of an input is reached twice)");
         L.count = scanned.get();
-        hipLaunchKernelGGL(merge_emit_kernel, dim3(blocks_for(n * 8)), dim3(256), 0, stream, m->in, L, n_next);
+        hipLaunchKernelGGL(merge_emit_kernel, dim3(mnv::blocks_for(n * 8)), dim3(256), 0, stream, m->in, L, n_next);
         if ((rc = check_hip(hipGetLastError(), "merge_emit_kernel"))) return rc;
         stats->chunks_at_depth[d + 1] = n_next;
         first += n;
@@ -431,8 +389,8 @@ int mnv_tree_merge_write(const mnv_tree_merge *m, int32_t *child_out, uint16_t *
     const char *who = "mnv_tree_merge_write";
     if (!m || !child_out || !data_out) return set_error(MNV_E_INVALID, std::string(who) + ": null argument");
     if (((uintptr_t)data_out & 15u) != 0) return set_error(MNV_E_INVALID, std::string(who) + ": data_out must be 16-byte aligned");
-    if (!on_device(child_out) || !on_device(data_out) || (parent_out && !on_device(parent_out)) || (sample_counts_out && !on_device(sample_counts_out)) ||
-        (src_a_out && !on_device(src_a_out)) || (src_b_out && !on_device(src_b_out)))
+    if (!mnv::on_device(child_out) || !mnv::on_device(data_out) || (parent_out && !mnv::on_device(parent_out)) || (sample_counts_out && !mnv::on_device(sample_counts_out)) ||
+        (src_a_out && !mnv::on_device(src_a_out)) || (src_b_out && !mnv::on_device(src_b_out)))
         return set_error(MNV_E_INVALID, std::string(who) + ": the outputs must be device arrays");
     WriteArgs P;
     P.a_ref = m->a_ref.get(), P.b_ref = m->b_ref.get(), P.first_child = m->first_child.get(), P.parent = m->parent.get(), P.mask = m->mask.get();
@@ -440,7 +398,7 @@ int mnv_tree_merge_write(const mnv_tree_merge *m, int32_t *child_out, uint16_t *
     P.log2_g = 3;  // lanes per chunk: 8, 16, 32 or 64, at least data_dim where that is below 64
     while ((1 << P.log2_g) < m->in.dd && P.log2_g < 6) ++P.log2_g;
     P.child_out = child_out, P.data_out = data_out, P.parent_out = parent_out, P.counts_out = sample_counts_out, P.src_a_out = src_a_out, P.src_b_out = src_b_out;
-    hipLaunchKernelGGL(merge_write_kernel, dim3(blocks_for(m->capacity, 256 >> P.log2_g)), dim3(256), 0, (hipStream_t)hip_stream, m->in, P);
+    hipLaunchKernelGGL(merge_write_kernel, dim3(mnv::blocks_for(m->capacity, 256 >> P.log2_g)), dim3(256), 0, (hipStream_t)hip_stream, m->in, P);
     return check_hip(hipGetLastError(), "merge_write_kernel");
 }
 

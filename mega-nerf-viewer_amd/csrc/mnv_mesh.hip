@@ -370,8 +370,6 @@ __global__ void __launch_bounds__(256) mesh_tile_kernel(DrawParams P, const Prim
     }
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 // scratch of the pass, one set per (device, HIP stream), left reset by every call (tile counts zero).  mnv_render_meshes holds `mu` from its
 // first launch to its last, so calls from several host threads do not interleave their passes.
 struct Scratch {
@@ -426,10 +424,7 @@ static int upload_mesh(mnv_mesh *m, const float *vert, int64_t n_verts, const ui
     int rc = validate_mesh_arrays(vert, n_verts, faces, face_size >= 1 && face_size <= 3 ? n_indices / face_size : 0, face_size);
     if (rc) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
+    if ((rc = mnv::current_device(&dev))) return rc;
     mnv::Buffer<float> dv;
     mnv::Buffer<uint32_t> df;
     if ((rc = check_hip(dv.alloc((size_t)n_verts * 9), "hipMalloc(mesh vertices)")) ||
@@ -499,10 +494,7 @@ int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv
         return set_error(MNV_E_INVALID, "rgba8 images must be 4-byte aligned");
     if (n_meshes > (1 << 28)) return set_error(MNV_E_INVALID, "too many meshes");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
+    if (const int no_device = mnv::current_device(&dev)) return no_device;
     if (!tmax_px_out && !rgba8_out) return MNV_OK;
     const int64_t n_px = (int64_t)tile.w * tile.h;
     if (n_px == 0) return MNV_OK;
@@ -562,8 +554,8 @@ int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv
     P.descs = S->descs.get();
     TileBins &B = S->bins;
     if ((rc = B.ensure(n_tiles, stream, "mesh scratch"))) return rc;
-    hipLaunchKernelGGL(mesh_setup_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, P, S->recs.get());
-    hipLaunchKernelGGL(mesh_bin_count_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, S->recs.get(), n_prims, P.V, G, B.count.get());
+    hipLaunchKernelGGL(mesh_setup_kernel, dim3(mnv::blocks_for(n_prims)), dim3(256), 0, stream, P, S->recs.get());
+    hipLaunchKernelGGL(mesh_bin_count_kernel, dim3(mnv::blocks_for(n_prims)), dim3(256), 0, stream, S->recs.get(), n_prims, P.V, G, B.count.get());
     hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, B.count.get(), (int)n_tiles, B.offset.get(), B.cursor.get(), B.total.dev.get());
     if ((rc = check_hip(hipGetLastError(), "mesh setup / count / scan")) ||
         (rc = check_hip(hipMemcpyAsync(B.total.host.get(), B.total.dev.get(), 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
@@ -572,7 +564,7 @@ int mnv_render_meshes(const mnv_mesh *const *meshes, int32_t n_meshes, const mnv
     const int64_t pairs = (int64_t)*B.total.host.get(), list_need = std::max<int64_t>(pairs, 1);
     if ((rc = B.grow_list(list_need, (int64_t)with_slack(list_need), "pair list"))) return rc;
     if (pairs > 0) {
-        hipLaunchKernelGGL(mesh_bin_fill_kernel, dim3(blocks_for(n_prims)), dim3(256), 0, stream, S->recs.get(), n_prims, P.V, G, B.offset.get(), B.cursor.get(), B.list.get());
+        hipLaunchKernelGGL(mesh_bin_fill_kernel, dim3(mnv::blocks_for(n_prims)), dim3(256), 0, stream, S->recs.get(), n_prims, P.V, G, B.offset.get(), B.cursor.get(), B.list.get());
         if ((rc = check_hip(hipGetLastError(), "mesh_bin_fill_kernel"))) return rc;
     }
     hipLaunchKernelGGL(mesh_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, (const PrimRec *)S->recs.get(), G, B.count.get(),

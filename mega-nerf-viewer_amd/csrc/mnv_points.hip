@@ -36,7 +36,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "mnv_internal.h"
+#include "mnv_tree_walk.h"
 
 using mnv::check_hip;
 using mnv::set_error;
@@ -57,8 +57,6 @@ struct Rec {  // one distinct voxel: 40 bytes
 struct Acc {
     uint64_t n, r, g, b;
 };
-
-unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // ---------------------------------------------------------------------------------------------------- keys
 
@@ -309,11 +307,6 @@ struct WriteParams {
     uint32_t *counts;
 };
 
-union Seg16 {
-    uint4 v;
-    uint16_t h[8];
-};
-
 // index of `v` in a sorted list read through `at`, or -1
 template <typename At>
 __device__ __forceinline__ int64_t find_code(At at, int64_t n, uint64_t v) {
@@ -369,7 +362,7 @@ __global__ void __launch_bounds__(256) points_write_kernel(WriteParams P) {
     if (!active) return;
     uint4 *out4 = reinterpret_cast<uint4 *>(P.data) + c * P.dd;
     for (int s = gl; s < P.dd; s += G) {
-        Seg16 a;
+        mnv::Seg16 a;
         a.v = make_uint4(0u, 0u, 0u, 0u);
         if (P.leaf_level) {
             for (int i = 0; i < 8; ++i) {
@@ -392,26 +385,6 @@ __global__ void __launch_bounds__(256) points_write_kernel(WriteParams P) {
 
 // ---------------------------------------------------------------------------------------------------- host
 
-// binary32 -> binary16 bits, round to nearest even, once; subnormal results kept, overflow to infinity
-uint16_t half_bits(float f) {
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    const uint32_t s = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u) return (uint16_t)(s | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));
-    if (x < 0x38800000u) {  // below 2^-14: the sum with 0.5 has the spacing of binary16 subnormals and is rounded by the add
-        float a;
-        std::memcpy(&a, &x, 4);
-        const float r = a + 0.5f;
-        uint32_t y;
-        std::memcpy(&y, &r, 4);
-        return (uint16_t)(s | (y - 0x3f000000u));
-    }
-    x += 0xfffu + ((x >> 13) & 1u);
-    x = (x - 0x38000000u) >> 13;
-    return (uint16_t)(s | (x > 0x7c00u ? 0x7c00u : x));
-}
-
 int check_format(int32_t format, int32_t basis_dim, const char *who) {
     if (format == MNV_FORMAT_RGBA) return MNV_OK;
     if (format == MNV_FORMAT_SH && (basis_dim == 1 || basis_dim == 4 || basis_dim == 9 || basis_dim == 16 || basis_dim == 25)) return MNV_OK;
@@ -421,22 +394,13 @@ int check_format(int32_t format, int32_t basis_dim, const char *who) {
 void colour_table(int32_t format, uint16_t out[256]) {
     for (int v = 0; v < 256; ++v) {
         if (format == MNV_FORMAT_RGBA) {
-            out[v] = half_bits((float)v / 255.f);
+            out[v] = mnv::half((float)v / 255.f);
         } else {
             double x = (double)v / 255.0;
             x = x < 1.0 / 512.0 ? 1.0 / 512.0 : x > 511.0 / 512.0 ? 511.0 / 512.0 : x;
-            out[v] = half_bits((float)(std::log(x / (1.0 - x)) / 0.28209479177387814));
+            out[v] = mnv::half((float)(std::log(x / (1.0 - x)) / 0.28209479177387814));
         }
     }
-}
-
-bool on_device(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
 }
 
 struct Carver {
@@ -498,10 +462,10 @@ int add_batch(mnv_point_tree *t, const float *xyz, const uint8_t *rgb, int64_t n
     for (int k = 0; k < 3; ++k) K.offset[k] = t->p.offset[k], K.scale[k] = t->p.scale[k];
     K.cells = (float)((int64_t)1 << t->p.depth);
     if ((rc = check_hip(hipMemsetAsync(t->ctr.dev.get(), 0, 8, stream), "clear the drop counter"))) return rc;
-    hipLaunchKernelGGL(points_key_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, xyz, rgb, n, K, keys, vals, t->ctr.dev.get());
+    hipLaunchKernelGGL(points_key_kernel, dim3(mnv::blocks_for(n)), dim3(256), 0, stream, xyz, rgb, n, K, keys, vals, t->ctr.dev.get());
     if ((rc = check_hip(hipGetLastError(), "points_key_kernel"))) return rc;
     if (n_old > 0) {
-        hipLaunchKernelGGL(points_record_keys_kernel, dim3(blocks_for(n_old)), dim3(256), 0, stream, t->recs.get(), n_old, keys + n, vals + n);
+        hipLaunchKernelGGL(points_record_keys_kernel, dim3(mnv::blocks_for(n_old)), dim3(256), 0, stream, t->recs.get(), n_old, keys + n, vals + n);
         if ((rc = check_hip(hipGetLastError(), "points_record_keys_kernel"))) return rc;
     }
     size_t tmp = tmp_sort;
@@ -510,7 +474,7 @@ int add_batch(mnv_point_tree *t, const float *xyz, const uint8_t *rgb, int64_t n
     if ((rc = check_hip(rocprim::radix_sort_pairs(ws + o_tmp, tmp, key_pair, val_pair, (size_t)n_elem, 0, key_bits, stream), "radix_sort_pairs"))) return rc;
     const uint64_t *sorted = key_pair.current();  // (whichever half the last pass wrote)
     const uint32_t *svals = val_pair.current();
-    hipLaunchKernelGGL(points_count_kernel, dim3(blocks_for(n_tiles, kWaves)), dim3(64 * kWaves), 0, stream, sorted, n_elem, t->mask, heads);
+    hipLaunchKernelGGL(points_count_kernel, dim3(mnv::blocks_for(n_tiles, kWaves)), dim3(64 * kWaves), 0, stream, sorted, n_elem, t->mask, heads);
     if ((rc = check_hip(hipGetLastError(), "points_count_kernel"))) return rc;
     tmp = tmp_scan;
     if ((rc = check_hip(rocprim::exclusive_scan(ws + o_tmp, tmp, heads, base, 0u, (size_t)n_tiles, rocprim::plus<uint32_t>(), stream), "exclusive_scan"))) return rc;
@@ -524,11 +488,11 @@ int add_batch(mnv_point_tree *t, const float *xyz, const uint8_t *rgb, int64_t n
     if (t->accepted + (n - n_dropped) > 0xffffffffll) return set_error(MNV_E_UNSUPPORTED, "mnv_point_tree_add: more than 2^32 - 1 accepted points");
     mnv::Buffer<Rec> recs;
     if ((rc = check_hip(recs.alloc((size_t)n_new), "hipMalloc(point records)"))) return rc;
-    hipLaunchKernelGGL(points_reduce_kernel, dim3(blocks_for(n_tiles, kWaves)), dim3(64 * kWaves), 0, stream, sorted, svals, n_elem, t->mask, t->recs.get(), base,
+    hipLaunchKernelGGL(points_reduce_kernel, dim3(mnv::blocks_for(n_tiles, kWaves)), dim3(64 * kWaves), 0, stream, sorted, svals, n_elem, t->mask, t->recs.get(), base,
                        recs.get(), pre, info);
     if ((rc = check_hip(hipGetLastError(), "points_reduce_kernel"))) return rc;
     if (n_tiles > 1) {
-        hipLaunchKernelGGL(points_fixup_kernel, dim3(blocks_for(n_tiles)), dim3(256), 0, stream, pre, info, n_tiles, recs.get());
+        hipLaunchKernelGGL(points_fixup_kernel, dim3(mnv::blocks_for(n_tiles)), dim3(256), 0, stream, pre, info, n_tiles, recs.get());
         if ((rc = check_hip(hipGetLastError(), "points_fixup_kernel"))) return rc;
     }
     if ((rc = check_hip(hipStreamSynchronize(stream), "mnv_point_tree_add"))) return rc;  // the old records go
@@ -554,7 +518,7 @@ int compact(const void *in, int64_t n, uint32_t *flag, uint32_t *pos, void *tmp,
     *n_out = total;
     if (total == 0) return MNV_OK;
     if ((rc = check_hip(out.alloc(total), "hipMalloc(chunk list)"))) return rc;
-    hipLaunchKernelGGL(points_scatter_kernel<FROM_RECORDS>, dim3(blocks_for(n)), dim3(256), 0, stream, in, flag, pos, n, out.get());
+    hipLaunchKernelGGL(points_scatter_kernel<FROM_RECORDS>, dim3(mnv::blocks_for(n)), dim3(256), 0, stream, in, flag, pos, n, out.get());
     return check_hip(hipGetLastError(), "points_scatter_kernel");
 }
 
@@ -583,16 +547,13 @@ int mnv_point_tree_create(const mnv_points_params *p, mnv_point_tree **out) {
     int rc;
     if ((rc = check_format(p->format, p->basis_dim, "mnv_point_tree_create"))) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
+    if ((rc = mnv::current_device(&dev))) return rc;
     auto *t = new mnv_point_tree();
     t->p = *p;
     t->dd = p->format == MNV_FORMAT_RGBA ? 4 : 3 * p->basis_dim + 1;
     t->colour_stride = p->format == MNV_FORMAT_RGBA ? 1 : p->basis_dim;
     t->mask = (1ull << (3 * p->depth)) - 1ull;
-    t->sigma_half = half_bits(p->sigma);
+    t->sigma_half = mnv::half(p->sigma);
     std::memset(&t->stats, 0, sizeof(t->stats));
     uint16_t table[256];
     colour_table(p->format, table);
@@ -613,7 +574,7 @@ int mnv_point_tree_add(mnv_point_tree *t, const float *xyz, const uint8_t *rgb, 
     if (n < 0) return set_error(MNV_E_INVALID, "mnv_point_tree_add: n < 0");
     if (n == 0) return MNV_OK;
     if (!xyz || !rgb) return set_error(MNV_E_INVALID, "mnv_point_tree_add: null points / colours");
-    if (!on_device(xyz) || !on_device(rgb)) return set_error(MNV_E_INVALID, "mnv_point_tree_add: the points and colours must be device arrays");
+    if (!mnv::on_device(xyz) || !mnv::on_device(rgb)) return set_error(MNV_E_INVALID, "mnv_point_tree_add: the points and colours must be device arrays");
     t->finished = false;
     for (int64_t at = 0; at < n; at += kMaxBatch) {
         const int rc = add_batch(t, xyz + at * 3, rgb + at * 3, std::min(kMaxBatch, n - at), (hipStream_t)hip_stream);
@@ -645,7 +606,7 @@ int mnv_point_tree_finish(mnv_point_tree *t, mnv_points_stats *stats, void *hip_
             (rc = check_hip(tmp.alloc(tmp_bytes + 256), "hipMalloc(scan scratch)")) ||
             (rc = check_hip(hipMemsetAsync(t->ctr.dev.get() + 1, 0, 8, stream), "clear the voxel counter")))
             return rc;
-        hipLaunchKernelGGL(points_occupied_kernel, dim3(std::min(blocks_for(n), (unsigned)kOccupiedGrid)), dim3(256), 0, stream, t->recs.get(), n, (uint64_t)t->p.min_points, flag.get(),
+        hipLaunchKernelGGL(points_occupied_kernel, dim3(std::min(mnv::blocks_for(n), (unsigned)kOccupiedGrid)), dim3(256), 0, stream, t->recs.get(), n, (uint64_t)t->p.min_points, flag.get(),
                            t->ctr.dev.get() + 1);
         if ((rc = check_hip(hipGetLastError(), "points_occupied_kernel")) ||
             (rc = check_hip(hipMemcpyAsync(t->ctr.host.get() + 1, t->ctr.dev.get() + 1, 8, hipMemcpyDeviceToHost, stream), "copy the voxel counter")))
@@ -656,7 +617,7 @@ int mnv_point_tree_finish(mnv_point_tree *t, mnv_points_stats *stats, void *hip_
         S.occupied_voxels = m;
         const uint64_t *below = occupied.get();
         for (int d = D; d >= 2 && m > 0; --d) {
-            hipLaunchKernelGGL(points_parent_flags_kernel, dim3(blocks_for(m)), dim3(256), 0, stream, below, m, flag.get());
+            hipLaunchKernelGGL(points_parent_flags_kernel, dim3(mnv::blocks_for(m)), dim3(256), 0, stream, below, m, flag.get());
             if ((rc = check_hip(hipGetLastError(), "points_parent_flags_kernel"))) return rc;
             int64_t m_up = 0;
             if ((rc = compact<false>(below, m, flag.get(), pos.get(), tmp.get(), tmp_bytes, t->level[d], &m_up, stream))) return rc;
@@ -680,8 +641,8 @@ int mnv_point_tree_write(const mnv_point_tree *t, int32_t *child_out, uint16_t *
     if (!t || !child_out || !data_out) return set_error(MNV_E_INVALID, "mnv_point_tree_write: null argument");
     if (!t->finished) return set_error(MNV_E_INVALID, "mnv_point_tree_write: call mnv_point_tree_finish first (also after a later add)");
     if (((uintptr_t)data_out & 15u) != 0) return set_error(MNV_E_INVALID, "mnv_point_tree_write: data_out must be 16-byte aligned");
-    if (!on_device(child_out) || !on_device(data_out) || (parent_out && !on_device(parent_out)) || (sample_counts_out && !on_device(sample_counts_out)) ||
-        (counts_out && !on_device(counts_out)))
+    if (!mnv::on_device(child_out) || !mnv::on_device(data_out) || (parent_out && !mnv::on_device(parent_out)) || (sample_counts_out && !mnv::on_device(sample_counts_out)) ||
+        (counts_out && !mnv::on_device(counts_out)))
         return set_error(MNV_E_INVALID, "mnv_point_tree_write: the outputs must be device arrays");
     hipStream_t stream = (hipStream_t)hip_stream;
     const int D = t->p.depth;
@@ -712,7 +673,7 @@ int mnv_point_tree_write(const mnv_point_tree *t, int32_t *child_out, uint16_t *
         P.parent = parent_out;
         P.sample_counts = sample_counts_out;
         P.counts = counts_out;
-        hipLaunchKernelGGL(points_write_kernel, dim3(blocks_for(n_chunks, 256 >> log2_g)), dim3(256), 0, stream, P);
+        hipLaunchKernelGGL(points_write_kernel, dim3(mnv::blocks_for(n_chunks, 256 >> log2_g)), dim3(256), 0, stream, P);
         const int rc = check_hip(hipGetLastError(), "points_write_kernel");
         if (rc) return rc;
         first += n_chunks;

@@ -9,7 +9,7 @@
 // there: the first finds out whether the ray is skipped (a skipped ray must add nothing) and how many dense samples it has, the second
 // repeats the same steps and writes.  The words are maxima of non-negative binary32 bit patterns, so they depend on no order.
 //
-// mnv_tree_cull: the level walk of mnv_lod.hip (restated: a list of (chunk, voxel above) per depth), then one launch per depth, deepest
+// mnv_tree_cull: the level walk of mnv_tree_walk.h (a list of (chunk, voxel above) per depth), then one launch per depth, deepest
 // first, a group of 8 .. 64 lanes per chunk as the mip pass has them.  The group's first eight lanes decide the chunk's eight voxels -- a
 // leaf by its word of wmax, an interior voxel by the keep byte the launch of the level below wrote for its child chunk -- a ballot hands
 // the eight bits to the whole group, which then moves the chunk's rows in 16-byte segments and zeroes the halves of dead voxels on the way.
@@ -18,9 +18,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 
-#include "mnv_internal.h"
+#include "mnv_tree_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -33,12 +32,9 @@ constexpr int kMaxDescent = 23;     // levels, as mnv_rays_grad
 constexpr int kMaxSteps = 1 << 20;  // march steps of one ray; a ray that needs more is skipped
 constexpr int kVisGrid = 4096;      // workgroups of one wavefront: 16 per CU
 constexpr int64_t kMaxRays = (int64_t)1 << 22;
-constexpr int kMaxCullDepth = 23;   // as the mip pass
 constexpr int kMaxDataDim = 1024;
 constexpr int kWavesPerBlock = 4;
 constexpr int kCullGrid = 8192;     // workgroups of four wavefronts: 32 per CU
-
-unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // ---------------------------------------------------------------------------------------------------- visibility
 
@@ -210,55 +206,8 @@ __global__ __launch_bounds__(64) void rays_visibility_kernel(const VisArgs K) {
 
 // ---------------------------------------------------------------------------------------------------- cull
 
-enum { kCtrNext = 0, kCtrFault = 1, kCtrSeen = 2, kCtrCulled = 3, kCtrDead = 4, kCtrKept = 5, kCtrWords = kCtrKept + 24 };
-
-// The level walk of mnv_lod.hip (lod_level_kernel): thread t is child (t & 7) of list entry t >> 3.  ctr[kCtrNext]: size of the next level,
-// ctr[kCtrFault]: 1 a link outside the tree, 2 a chunk reached twice
-__global__ void __launch_bounds__(256) cull_level_kernel(const int32_t *__restrict__ child, int32_t capacity, const int2 *__restrict__ front, int64_t n_front,
-                                                          int32_t depth, int2 *__restrict__ next, int64_t cap_next, int32_t *__restrict__ chunk_depth,
-                                                          unsigned long long *__restrict__ ctr) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool push = false;
-    int32_t nid = 0, above = 0;
-    if (t < n_front * 8) {
-        const int32_t c = front[t >> 3].x;
-        const int j = (int)(t & 7);
-        const int32_t ch = child[(int64_t)c * 8 + j];
-        if (ch != 0) {
-            const int64_t n = (int64_t)c + ch;
-            if (n < 1 || n >= capacity) {
-                atomicOr(&ctr[kCtrFault], 1ull);
-            } else if (atomicCAS(&chunk_depth[n], 0, depth + 1) != 0) {
-                atomicOr(&ctr[kCtrFault], 2ull);
-            } else {
-                nid = (int32_t)n;
-                above = c * 8 + j;
-                push = true;
-            }
-        }
-    }
-    const unsigned lane = __lane_id();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const unsigned long long m = __ballot(push);
-    if (m) {
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if ((int)lane == leader) base = atomicAdd(&ctr[kCtrNext], (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (push) {
-            const unsigned long long slot = base + (unsigned long long)__popcll(m & below);
-            if ((int64_t)slot < cap_next)
-                next[slot] = make_int2(nid, above);
-            else
-                atomicOr(&ctr[kCtrFault], 2ull);  // more arrivals than chunks left
-        }
-    }
-}
-
-union Seg16 {
-    uint4 v;
-    uint16_t h[8];
-};
+// the counters of cull_rows_kernel (words 0 and 1 are not used: the walk's counters were there once, and the kernel's offsets stay)
+enum { kCtrSeen = 2, kCtrCulled = 3, kCtrDead = 4, kCtrKept = 5, kCtrWords = kCtrKept + 24 };
 
 // A group of G lanes (a power of two, 8 .. 64) per list entry of one depth, 64 / G entries per wavefront.  thresh_bits: the pattern of the
 // (finite, non-negative) threshold.  A word of wmax is seen iff it is a non-negative, non-NaN pattern above thresh_bits: such patterns order
@@ -300,7 +249,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) cull_rows_kernel(const ui
             const uint4 *in4 = reinterpret_cast<const uint4 *>(data_in) + k * dd;
             uint4 *out4 = reinterpret_cast<uint4 *>(data_out) + k * dd;
             for (int s = gl; s < dd; s += G) {
-                Seg16 a;
+                mnv::Seg16 a;
                 a.v = in4[s];
                 if (mask != 0xffu) {
 #pragma unroll
@@ -325,38 +274,8 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) cull_rows_kernel(const ui
     }
 }
 
-// rows of the chunks the walk did not reach, bit for bit; thread per 16-byte segment
-__global__ void __launch_bounds__(256) cull_copy_unreached_kernel(const uint4 *__restrict__ in4, uint4 *__restrict__ out4, const int32_t *__restrict__ chunk_depth,
-                                                                   int64_t n_seg, int32_t dd) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_seg) return;
-    if (chunk_depth[t / dd] == 0) out4[t] = in4[t];
-}
-
-// scratch of the level walk (mnv_tree_cull waits for its stream: one call at a time per process uses it), per device; heap objects that
-// live as long as the process (no hipFree after the runtime went)
-constexpr int kMaxDevices = 16;
-struct CullScratch {
-    mnv::Buffer<int2> order;     // the level lists, [capacity]
-    mnv::Buffer<int32_t> depth;  // a word per chunk: its depth, 0 = not reached
-    mnv::Mirrored<unsigned long long> ctr;
-};
-std::mutex g_cull_mutex;
-CullScratch *const g_cull = new CullScratch[kMaxDevices];
-
-bool on_device(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uint8_t *x = (const uint8_t *)a, *y = (const uint8_t *)b;
-    return x < y + nb && y < x + na;
-}
+// the counters of mnv_tree_cull, per device; used under the walk's guard and kept as long as the process (no hipFree after the runtime went)
+mnv::Mirrored<unsigned long long> *const g_cull_ctr = new mnv::Mirrored<unsigned long long>[mnv::kMaxWalkDevices];
 
 }  // namespace
 
@@ -423,81 +342,37 @@ int mnv_tree_cull(const mnv_tree_view *tree, const uint32_t *wmax, float weight_
     const size_t data_bytes = (size_t)cap * 16 * dd;
     if ((((uintptr_t)tree->data | (uintptr_t)data_out) & 15u) != 0) return set_error(MNV_E_INVALID, std::string(who) + ": the data arrays must be 16-byte aligned");
     if (((uintptr_t)wmax & 3u) != 0) return set_error(MNV_E_INVALID, std::string(who) + ": wmax must be 4-byte aligned");
-    if (!on_device(tree->child) || !on_device(tree->data) || !on_device(wmax) || !on_device(data_out) || !on_device(keep_out))
+    if (!mnv::on_device(tree->child) || !mnv::on_device(tree->data) || !mnv::on_device(wmax) || !mnv::on_device(data_out) || !mnv::on_device(keep_out))
         return set_error(MNV_E_INVALID, std::string(who) + ": the tree view, wmax, data_out and keep_out must be device arrays");
-    if (overlap(data_out, data_bytes, tree->data, data_bytes) || overlap(data_out, data_bytes, tree->child, (size_t)cap * 32) ||
-        overlap(data_out, data_bytes, wmax, (size_t)cap * 32) || overlap(data_out, data_bytes, keep_out, (size_t)cap) ||
-        overlap(keep_out, (size_t)cap, tree->data, data_bytes) || overlap(keep_out, (size_t)cap, tree->child, (size_t)cap * 32) ||
-        overlap(keep_out, (size_t)cap, wmax, (size_t)cap * 32))
+    if (mnv::overlap(data_out, data_bytes, tree->data, data_bytes) || mnv::overlap(data_out, data_bytes, tree->child, (size_t)cap * 32) ||
+        mnv::overlap(data_out, data_bytes, wmax, (size_t)cap * 32) || mnv::overlap(data_out, data_bytes, keep_out, (size_t)cap) ||
+        mnv::overlap(keep_out, (size_t)cap, tree->data, data_bytes) || mnv::overlap(keep_out, (size_t)cap, tree->child, (size_t)cap * 32) ||
+        mnv::overlap(keep_out, (size_t)cap, wmax, (size_t)cap * 32))
         return set_error(MNV_E_INVALID, std::string(who) + ": the outputs must overlap neither each other nor the inputs (the input tree is never modified)");
     hipStream_t stream = (hipStream_t)hip_stream;
     const float thresh = weight_thresh + 0.f;  // (-0 becomes +0)
     uint32_t thresh_bits;
     std::memcpy(&thresh_bits, &thresh, 4);
 
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
-    // the walk's scratch is kept between calls (grow-only, per device), as mnv_tree_mip_rows keeps its own: the call holds the lock until it
-    // has waited for the stream
-    std::lock_guard<std::mutex> lock(g_cull_mutex);
-    CullScratch &S = g_cull[dev];
-    struct Drain {  // ... also when an error leaves this function early: queued work may still use the scratch
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{stream};
-    mnv::Mirrored<unsigned long long> &ctr = S.ctr;
-    if ((rc = check_hip(mnv::grow(S.order, (size_t)cap, (size_t)cap + cap / 4, stream, false), "hipMalloc(level lists)")) ||
-        (rc = check_hip(mnv::grow(S.depth, (size_t)cap, (size_t)cap + cap / 4, stream, false), "hipMalloc(chunk depths)")))
-        return rc;
+    // the call holds the walk's scratch, and with it its own counters, until it has waited for the stream
+    mnv::WalkGuard guard;
+    mnv::LevelLists L;
+    if ((rc = guard.begin(stream))) return rc;
+    mnv::Mirrored<unsigned long long> &ctr = g_cull_ctr[guard.device()];
     if (!ctr && (rc = mnv::alloc_pair(ctr, kCtrWords, "hipMalloc(level counters)", "hipHostMalloc(level counters)"))) return rc;
-    int2 *order = S.order.get();
-    int32_t *depth = S.depth.get();
-    const int2 root = make_int2(0, -1);
-    const int32_t one = 1;
-    if ((rc = check_hip(hipMemsetAsync(depth, 0, (size_t)cap * 4, stream), "clear chunk depths")) ||
-        (rc = check_hip(hipMemcpyAsync(depth, &one, 4, hipMemcpyHostToDevice, stream), "root depth")) ||
-        (rc = check_hip(hipMemcpyAsync(order, &root, sizeof(root), hipMemcpyHostToDevice, stream), "root entry")) ||
-        (rc = check_hip(hipMemsetAsync(ctr.dev.get(), 0, kCtrWords * 8, stream), "level counters")) ||
-        (rc = check_hip(hipMemsetAsync(keep_out, 0, (size_t)cap, stream), "clear keep")))
+    if ((rc = check_hip(hipMemsetAsync(ctr.dev.get(), 0, kCtrWords * 8, stream), "level counters")) ||
+        (rc = check_hip(hipMemsetAsync(keep_out, 0, (size_t)cap, stream), "clear keep")) ||
+        (rc = mnv::walk_levels(tree->child, cap, nullptr, who, guard, L)))
         return rc;
-    int64_t offset[26] = {0};  // level d's entries: order[offset[d] .. offset[d + 1])
-    offset[2] = 1;
-    int levels = 1;
-    for (int d = 1;; ++d) {
-        const int64_t n_front = offset[d + 1] - offset[d], cap_next = (int64_t)cap - offset[d + 1];
-        hipLaunchKernelGGL(cull_level_kernel, dim3(blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, cap, order + offset[d], n_front, d,
-                           order + offset[d + 1], cap_next, depth, ctr.dev.get());
-        if ((rc = check_hip(hipGetLastError(), "cull_level_kernel")) ||
-            (rc = check_hip(hipMemcpyAsync(ctr.host.get(), ctr.dev.get(), 16, hipMemcpyDeviceToHost, stream), "level counters")) ||
-            (rc = check_hip(hipMemsetAsync(ctr.dev.get(), 0, 8, stream), "level counters")) || (rc = check_hip(hipStreamSynchronize(stream), "cull_level_kernel")))
-            return rc;
-        const unsigned long long fault = ctr.host.get()[kCtrFault];
-        if (fault & 1ull) return set_error(MNV_E_INVALID, std::string(who) + ": a child link leaves the tree (outside [1, capacity))");
-        if (fault & 2ull) return set_error(MNV_E_INVALID, std::string(who) + ": a chunk is reached twice (not a tree)");
-        const int64_t n_next = (int64_t)ctr.host.get()[kCtrNext];
-        if (n_next == 0) break;
-        if (d + 1 > kMaxCullDepth) return set_error(MNV_E_UNSUPPORTED, std::string(who) + ": tree deeper than 23 levels");
-        offset[d + 2] = offset[d + 1] + n_next;
-        levels = d + 1;
-    }
     int log2_g = 3;  // lanes per chunk: 8, 16, 32 or 64, at least data_dim where that is below 64
     while ((1 << log2_g) < dd && log2_g < 6) ++log2_g;
     const int per_block = kWavesPerBlock * (64 >> log2_g);
-    for (int d = levels; d >= 1; --d) {
-        const int64_t n = offset[d + 1] - offset[d];
-        hipLaunchKernelGGL(cull_rows_kernel, dim3(std::min(blocks_for(n, per_block), (unsigned)kCullGrid)), dim3(64 * kWavesPerBlock), 0, stream, tree->data, data_out, tree->child, wmax,
-                           thresh_bits, order + offset[d], n, dd, log2_g, d, keep_out, ctr.dev.get());
+    for (int d = L.levels; d >= 1; --d) {
+        hipLaunchKernelGGL(cull_rows_kernel, dim3(std::min(mnv::blocks_for(L.size(d), per_block), (unsigned)kCullGrid)), dim3(64 * kWavesPerBlock), 0, stream, tree->data, data_out,
+                           tree->child, wmax, thresh_bits, L.order + L.offset[d], L.size(d), dd, log2_g, d, keep_out, ctr.dev.get());
         if ((rc = check_hip(hipGetLastError(), "cull_rows_kernel"))) return rc;
     }
-    if (offset[levels + 1] < cap) {
-        const int64_t n_seg = (int64_t)cap * dd;
-        hipLaunchKernelGGL(cull_copy_unreached_kernel, dim3(blocks_for(n_seg)), dim3(256), 0, stream, reinterpret_cast<const uint4 *>(tree->data),
-                           reinterpret_cast<uint4 *>(data_out), depth, n_seg, dd);
-        if ((rc = check_hip(hipGetLastError(), "cull_copy_unreached_kernel"))) return rc;
-    }
+    if (L.offset[L.levels + 1] < cap && (rc = mnv::copy_unreached(tree->data, data_out, L.depth, cap, dd, stream))) return rc;
     if ((rc = check_hip(hipMemcpyAsync(ctr.host.get(), ctr.dev.get(), kCtrWords * 8, hipMemcpyDeviceToHost, stream), "cull counters")) ||
         (rc = check_hip(hipStreamSynchronize(stream), who)))
         return rc;

@@ -21,8 +21,8 @@
 #include <mutex>
 #include <vector>
 
-#include "mnv_internal.h"
 #include "mnv_raster.h"
+#include "mnv_tree_walk.h"
 
 using mnv::check_hip;
 using mnv::set_error;
@@ -64,42 +64,18 @@ __global__ void __launch_bounds__(256) wire_level_kernel(const int32_t *__restri
             }
         }
     }
-    const unsigned lane = __lane_id();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    // cubes
-    {
-        const unsigned long long m = __ballot(emit);
-        if (m) {
-            const int leader = __ffsll((long long)m) - 1;
-            unsigned long long base = 0;
-            if ((int)lane == leader) base = atomicAdd(&ctr[1], (unsigned long long)__popcll(m));
-            base = __shfl(base, leader);
-            if (emit) {
-                const unsigned long long slot = base + (unsigned long long)__popcll(m & below);
-                if ((int64_t)slot < cap_cubes)
-                    cubes[slot] = make_uint4(gi, gj, gk, (unsigned)depth);
-                else
-                    atomicOr(&ctr[2], 2ull);
-            }
-        }
-    }
-    // next frontier
-    {
-        const unsigned long long m = __ballot(push);
-        if (m) {
-            const int leader = __ffsll((long long)m) - 1;
-            unsigned long long base = 0;
-            if ((int)lane == leader) base = atomicAdd(&ctr[0], (unsigned long long)__popcll(m));
-            base = __shfl(base, leader);
-            if (push) {
-                const unsigned long long slot = base + (unsigned long long)__popcll(m & below);
-                if ((int64_t)slot < cap_next)
-                    next[slot] = make_int4(nid, (int)gi, (int)gj, (int)gk);
-                else
-                    atomicOr(&ctr[2], 2ull);  // more frontier entries than chunks: not a tree
-            }
-        }
-    }
+    mnv::wave_append(emit, &ctr[1], [=](unsigned long long slot) {
+        if ((int64_t)slot < cap_cubes)
+            cubes[slot] = make_uint4(gi, gj, gk, (unsigned)depth);
+        else
+            atomicOr(&ctr[2], 2ull);
+    });
+    mnv::wave_append(push, &ctr[0], [=](unsigned long long slot) {
+        if ((int64_t)slot < cap_next)
+            next[slot] = make_int4(nid, (int)gi, (int)gj, (int)gk);
+        else
+            atomicOr(&ctr[2], 2ull);  // more frontier entries than chunks: not a tree
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- edges
@@ -259,8 +235,6 @@ __global__ void __launch_bounds__(256) wire_tile_kernel(const uint4 *__restrict_
     }
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 struct mnv_wireframe {
@@ -292,11 +266,7 @@ int generate(mnv_wireframe *w, const mnv_tree_view *tree, int32_t max_depth, hip
     if (!tree || (tree->capacity > 0 && !tree->child)) return set_error(MNV_E_INVALID, "mnv_wireframe: null tree view / child array");
     if (tree->capacity > 0 && tree->N != 2) return set_error(MNV_E_UNSUPPORTED, "mnv_wireframe: only N == 2 trees");
     if (tree->capacity < 0) return set_error(MNV_E_INVALID, "mnv_wireframe: negative capacity");
-    hipPointerAttribute_t attr;
-    if (tree->capacity > 0 && (hipPointerGetAttributes(&attr, tree->child) != hipSuccess || attr.type != hipMemoryTypeDevice)) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_INVALID, "mnv_wireframe: the tree view must hold device arrays");
-    }
+    if (tree->capacity > 0 && !mnv::on_device(tree->child)) return set_error(MNV_E_INVALID, "mnv_wireframe: the tree view must hold device arrays");
     w->max_depth = max_depth;
     for (int a = 0; a < 3; ++a) {
         w->T.offset[a] = tree->offset[a];
@@ -322,7 +292,7 @@ int generate(mnv_wireframe *w, const mnv_tree_view *tree, int32_t max_depth, hip
         const int64_t cap_next = std::min<int64_t>(8 * n_front, tree->capacity);
         if ((rc = check_hip(mnv::grow(w->front[cur ^ 1], (size_t)cap_next, with_slack(cap_next), stream, false), "hipMalloc(wireframe)"))) return rc;
         if ((rc = check_hip(hipMemsetAsync(ctr, 0, sizeof(unsigned long long), stream), "wireframe counters"))) return rc;
-        hipLaunchKernelGGL(wire_level_kernel, dim3(blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, tree->capacity, w->front[cur].get(), n_front,
+        hipLaunchKernelGGL(wire_level_kernel, dim3(mnv::blocks_for(n_front * 8)), dim3(256), 0, stream, tree->child, tree->capacity, w->front[cur].get(), n_front,
                            depth, max_depth, w->front[cur ^ 1].get(), cap_next, w->cubes.get(), (int64_t)w->cubes.count(), ctr);
         if ((rc = check_hip(hipGetLastError(), "wire_level_kernel"))) return rc;
         if ((rc = check_hip(hipMemcpyAsync(ctr_host, ctr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "wireframe counters")) ||
@@ -346,13 +316,10 @@ extern "C" {
 int mnv_wireframe_create(const mnv_tree_view *device_tree, int32_t max_depth, void *hip_stream, mnv_wireframe **out) {
     if (!out) return set_error(MNV_E_INVALID, "null output");
     *out = nullptr;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-        (void)hipGetLastError();
-        return set_error(MNV_E_NO_DEVICE, "no current HIP device");
-    }
+    int dev = -1, rc;
+    if ((rc = mnv::current_device(&dev))) return rc;
     mnv_wireframe *w = new mnv_wireframe();
-    const int rc = generate(w, device_tree, max_depth, (hipStream_t)hip_stream);
+    rc = generate(w, device_tree, max_depth, (hipStream_t)hip_stream);
     if (rc) {
         delete w;
         return rc;
@@ -375,7 +342,7 @@ int mnv_wireframe_segments(const mnv_wireframe *w, float *segments_out, int64_t 
     if (!segments_out) return cap_segments == 0 ? MNV_OK : set_error(MNV_E_INVALID, "null segment buffer");
     if (cap_segments < n) return set_error(MNV_E_INVALID, "segment buffer too small (n_segments holds the count)");
     if (n == 0) return MNV_OK;
-    hipLaunchKernelGGL(wire_segments_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)hip_stream, w->cubes.get(), n, w->T, segments_out);
+    hipLaunchKernelGGL(wire_segments_kernel, dim3(mnv::blocks_for(n)), dim3(256), 0, (hipStream_t)hip_stream, w->cubes.get(), n, w->T, segments_out);
     return check_hip(hipGetLastError(), "wire_segments_kernel");
 }
 
@@ -422,10 +389,10 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
             }
         }
         if (n_edges > 0) {
-            hipLaunchKernelGGL(wire_raster_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, S->keys.get());
+            hipLaunchKernelGGL(wire_raster_kernel, dim3(mnv::blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, S->keys.get());
             if ((rc = check_hip(hipGetLastError(), "wire_raster_kernel"))) return rc;
         }
-        hipLaunchKernelGGL(wire_resolve_kernel, dim3(blocks_for(n_px)), dim3(256), 0, stream, S->keys.get(), n_px, bg, tmax_px_out, (uint32_t *)rgba8_out);
+        hipLaunchKernelGGL(wire_resolve_kernel, dim3(mnv::blocks_for(n_px)), dim3(256), 0, stream, S->keys.get(), n_px, bg, tmax_px_out, (uint32_t *)rgba8_out);
         return check_hip(hipGetLastError(), "wire_resolve_kernel");
     }
     const TileGrid G = {(tile.w + kTile - 1) / kTile, (tile.h + kTile - 1) / kTile};
@@ -433,7 +400,7 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
     TileBins &B = S->bins;
     if ((rc = B.ensure(n_tiles, stream, "wireframe scratch"))) return rc;
     if (n_edges > 0) {
-        hipLaunchKernelGGL(wire_bin_count_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, G, B.count.get());
+        hipLaunchKernelGGL(wire_bin_count_kernel, dim3(mnv::blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, G, B.count.get());
         hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, stream, B.count.get(), (int)n_tiles, B.offset.get(), B.cursor.get(), B.total.dev.get());
         if ((rc = check_hip(hipGetLastError(), "wire_bin_count / scan")) ||
             (rc = check_hip(hipMemcpyAsync(B.total.host.get(), B.total.dev.get(), 8, hipMemcpyDeviceToHost, stream), "read pair total")) ||
@@ -442,7 +409,7 @@ int mnv_render_wireframe(const mnv_wireframe *w, const mnv_camera *cam, const mn
         const int64_t pairs = (int64_t)*B.total.host.get();
         if ((rc = B.grow_list(pairs, pairs + pairs / 4 + 1024, "hipMalloc(pair list)"))) return rc;
         if (pairs > 0) {
-            hipLaunchKernelGGL(wire_bin_fill_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, G, B.offset.get(), B.cursor.get(), B.list.get());
+            hipLaunchKernelGGL(wire_bin_fill_kernel, dim3(mnv::blocks_for(n_edges)), dim3(256), 0, stream, w->cubes.get(), n_edges, P, G, B.offset.get(), B.cursor.get(), B.list.get());
             if ((rc = check_hip(hipGetLastError(), "wire_bin_fill_kernel"))) return rc;
         }
     }
