@@ -1256,6 +1256,63 @@ int mnv_rows_master_init(const uint16_t *data /* device [n] */, int64_t n, float
 int mnv_rows_sgd_step(uint16_t *data, float *master, int64_t *acc /* device [n_rows][data_dim] each */, int64_t n_rows, int32_t data_dim,
                       float lr_colour, float lr_sigma, void *hip_stream);
 
+/* ------------------------------------------------ fitting on a photo set: a normalised row step and ray mini-batches, on the device
+ * mnv_rows_sgd_step takes one rate for every row, while a row's gradient grows with the rays through it; mnv_n3tree_fit is full batch and
+ * stops at 2^24 pixels.  These entry points lift both limits: mnv_rows_adam_step is the row update with Adam's step (Kingma & Ba 2015), which
+ * does not depend on the gradient's scale, and mnv_ray_batcher_* draws batches of rays and targets across a whole set of cameras and images,
+ * so that mnv_rays_grad + one row step run per batch and the accumulators are cleared every step.
+ *
+ * mnv_rows_adam_step (elementwise; m1 / m2: the float32 first and second moments, zero before the first step).  The host computes
+ *     omb1 = 1.f - beta1;  omb2 = 1.f - beta2                                   (binary32)
+ *     c1 = (float)(1 / (1 - (double)beta1^step));  c2 likewise with beta2       (binary64 pow, rounded once)
+ *   and for every row r < n_rows with a non-zero word in acc[r][0 .. data_dim) -- mnv_rows_sgd_step's rule -- per column c, in binary32, one
+ *   operation at a time in this order, no contraction, division and square root correctly rounded:
+ *     g   = (float)((double)acc[r][c] * 2^-32)
+ *     a   = (m1 * beta1) + (g * omb1);           v = (m2 * beta2) + ((g * g) * omb2)
+ *     den = sqrtf(v * c2) + eps;                 upd = (lr * (a * c1)) / den          lr = c == data_dim - 1 ? lr_sigma : lr_colour
+ *     m   = master - upd;   the sigma column: m = m < 0 ? 0 : m
+ *     m1 = a;  m2 = v;  master = m;  data = binary16(m) exactly as mnv_rows_sgd_step writes it (a NaN m writes +0);  acc[r][.] = 0
+ *   Rows whose words are all zero keep master, moments and bytes: a lazy, sparse Adam.  Two known approximations, those of every sparse
+ *   Adam: untouched rows do not decay their moments, and the bias correction uses the global step for rows first touched late.
+ *   Traffic: a touched word moves 42 bytes (acc 8, master 4, m1 4, m2 4 read, the same 20 written back, 2 of data) against the SGD step's
+ *   26; an untouched word reads 8 in both.  State: 22 bytes per word with Adam (2 + 4 + 4 + 4 + 8) -- about 35 GB for a tree of 1.6 G words.
+ *   MNV_E_INVALID, before any launch: null arrays or parameters, n_rows < 0, data_dim < 1, step < 1, a rate that is not finite, a beta outside
+ *   [0, 1), eps not finite or <= 0, misaligned arrays.
+ *
+ * mnv_ray_batcher_*: cameras may differ in size.  A unit is a pixel (tile 1) or an 8 x 8 pixel tile (tile 8: a camera has ceil(w/8) *
+ * ceil(h/8) of them, row-major; pixels are row-major for tile 1); units are numbered camera after camera, U is their total (< 2^31).
+ * create copies the cameras and a prefix table of their first units to the device; `targets` is a HOST array of n_cams DEVICE images float
+ * [h][w][4] (16-byte aligned) that must outlive the handle's draws.  draw writes, for j < count, the unit perm(epoch, first + j) to rays
+ * j * tile^2 .. (j + 1) * tile^2 - 1 of the outputs.  It changes nothing in the handle: any stream, any number of draws at once.
+ *   The permutation is integer arithmetic only (uint32, wrapping), a 4-round Feistel network on 2k bits with cycle walking:
+ *     mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     k = max(1, ceil(bitlen(U - 1) / 2));  mask = 2^k - 1;  seed_lo / seed_hi: the halves of `seed`
+ *     key_r = mix32(mix32(seed_lo ^ mix32(seed_hi ^ (uint32)epoch)) + r),  r = 0 .. 3
+ *     x = i;  do { L = x >> k; R = x & mask;  for r in 0 .. 3: (L, R) = (R, L ^ (mix32(R ^ key_r) & mask));  x = (L << k) | R; } while (x >= U)
+ *   The Feistel map is a bijection of [0, 2^2k), so perm(epoch, .) is a bijection of [0, U), and the loop is bounded: the walk follows the
+ *   orbit of i, which returns to i, and i < U -- at most 2^2k <= 4U rounds, under four on average.
+ *   Rays.  Within a tile, lane l is pixel (tx * 8 + (l & 7), ty * 8 + (l >> 3)): a wavefront of mnv_rays_grad on the flat list (64 x 1 ray
+ *   tiles) marches one image tile.  A pixel inside the image gets the origin and direction mnv_generate_rays(MNV_PROJ_PINHOLE) gives that
+ *   pixel of that camera, bit for bit, and the 16 bytes of targets[cam][iy][ix].  A lane outside the image (edge tiles) gets the origin
+ *   c2w[9 .. 11], the direction (0, 0, 0) -- a degenerate ray, a miss -- and the target (0, 0, 0, 0): alpha 0 excludes it.
+ *   MNV_E_INVALID, before any launch: null arguments, n_cams outside 1 .. 4096, a tile other than 1 or 8, a camera with width or height
+ *   < 1, a null or misaligned target image, U >= 2^31; draw: epoch < 0, first < 0, count < 1, first + count > U, count * tile^2 > 2^22
+ *   (mnv_rays_grad's limit), origins_out / dirs_out not 4-byte aligned, target_out not 16-byte aligned.
+ */
+typedef struct mnv_adam_params {
+    float lr_colour, lr_sigma, beta1, beta2, eps;
+    int32_t reserved[3];
+} mnv_adam_params;
+int mnv_rows_adam_step(uint16_t *data, float *master, float *m1, float *m2, int64_t *acc /* device [n_rows][data_dim] each */, int64_t n_rows,
+                       int32_t data_dim, const mnv_adam_params *p, int64_t step /* >= 1 */, void *hip_stream);
+typedef struct mnv_ray_batcher mnv_ray_batcher;
+int mnv_ray_batcher_create(const mnv_camera *cams /* HOST */, const float *const *targets /* HOST array of device [h][w][4] */, int32_t n_cams,
+                           int32_t tile /* 1 or 8 */, uint64_t seed, mnv_ray_batcher **out);
+int mnv_ray_batcher_units(const mnv_ray_batcher *b, int64_t *units, int32_t *rays_per_unit);
+int mnv_ray_batcher_draw(const mnv_ray_batcher *b, int64_t epoch, int64_t first, int64_t count, float *origins_out,
+                         float *dirs_out /* device [count * tile * tile][3] */, float *target_out /* device [count * tile * tile][4] */, void *hip_stream);
+void mnv_ray_batcher_destroy(mnv_ray_batcher *b);
+
 /* ------------------------------------------------ culling a tree to a pose set: the largest weight per leaf, then a bottom-up cull
  * A batch renderer knows its poses in advance.  Leaves no listed ray weights above zero -- occluded ones, those behind an early stop, the
  * inside of a thick shell -- still cost rows and accel.  The octree family's step for this (PlenOctree extraction / compression): record per
@@ -1529,6 +1586,37 @@ int mnv_n3tree_fit(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const 
  * (mnv_n3tree_make_lod of the teacher) fitted this way is the use. */
 int mnv_n3tree_fit_to_tree(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt,
                            const mnv_fit_params *params, int64_t *se_q32_out);
+/* N3Tree::fit_ex: mnv_n3tree_fit with a choice of optimizer and of batching ("fitting on a photo set" above).
+ *   batch_rays == 0: full batch, mnv_n3tree_fit's loop with its 2^24 bound and the chosen row step.  optimizer == MNV_FIT_SGD with
+ *     batch_rays == 0 IS mnv_n3tree_fit (steps = iterations), byte for byte: both run the same loop.
+ *   batch_rays > 0: a multiple of tile^2, at most 2^22.  A mnv_ray_batcher over the cameras and targets (tile, seed) has U units;
+ *     B = batch_rays / tile^2 units per step, nb = ceil(U / B) batches per epoch.  Step s = 0 .. steps - 1 draws the units
+ *     [b * B, min((b + 1) * B, U)) of epoch s / nb, b = s % nb, runs ONE mnv_rays_grad on that flat list and one row step.  The accumulators
+ *     are cleared by every step, so the 2^24 bound does not apply: any number of images of any size (U < 2^31, 4096 cameras).
+ *   MNV_FIT_ADAM: mnv_rows_adam_step with step = s + 1; the moments are allocated (zeroed) only then.  beta1 / beta2 / eps are not read
+ *     for MNV_FIT_SGD.  Adam's rates chosen on the fit scene of tests/fit_cases.py: lr_colour 0.03, lr_sigma 1, beta 0.9 / 0.999, eps 1e-8
+ *     (the sweep stands in tests/fit_adam_ref.py); they do not depend on the gradient's scale, hence not on the image size.
+ *   se_q32_out / n_rays_out: HOST int64 [steps] or NULL: the se_q32 and the n_rays of each step's rays BEFORE its step; their ratio
+ *     (/ 2^32) is that batch's mean squared error.
+ *   After the loop the accel is rebuilt and the host arrays are refreshed, as mnv_n3tree_fit does.  Runs on the null stream and waits.
+ *   MNV_E_INVALID: what mnv_n3tree_fit refuses (the 2^24 bound only for batch_rays == 0), an unknown optimizer, a tile other than 1 or 8,
+ *     batch_rays < 0, not a multiple of tile^2 or above 2^22, for Adam a beta outside [0, 1) or eps not finite or <= 0; otherwise the
+ *     codes of the calls. */
+#define MNV_FIT_SGD 0
+#define MNV_FIT_ADAM 1
+typedef struct mnv_fit_params_ex {
+    int32_t steps, optimizer /* MNV_FIT_SGD 0, MNV_FIT_ADAM 1 */;
+    float lr_colour, lr_sigma, beta1, beta2, eps;
+    int32_t batch_rays /* 0: full batch */, tile /* 1 | 8 */;
+    uint64_t seed;
+    int32_t reserved[4];
+} mnv_fit_params_ex;
+int mnv_n3tree_fit_ex(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets /* HOST array of n_cams device pointers */,
+                      const mnv_render_options *opt, const mnv_fit_params_ex *p, int64_t *se_q32_out /* HOST [steps] or NULL */,
+                      int64_t *n_rays_out /* HOST [steps] or NULL */);
+/* N3Tree::fit_to_ex: the teacher's frames first, as mnv_n3tree_fit_to_tree renders them, then mnv_n3tree_fit_ex. */
+int mnv_n3tree_fit_to_tree_ex(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt,
+                              const mnv_fit_params_ex *p, int64_t *se_q32_out, int64_t *n_rays_out);
 /* N3Tree::from_points: mnv_point_tree_create, one add of the n device points, finish and write into a NEW tree on the device -- data, child,
  * parent, sample counts and the packed accel -- with the params' offset / scale / row format (basis_dim -1 for RGBA); its host arrays are
  * downloaded, so mnv_n3tree_save_npz, mnv_n3tree_make_lod, mnv_n3tree_fit and mnv_extract_surface work on it at once.  stats: HOST or NULL.
@@ -1684,6 +1772,10 @@ int mnv_renderer_set_cull(mnv_renderer *r, const mnv_camera *cams, int32_t n_cam
  * cameras are copied.  Refused wherever a level of detail is (mnv_renderer_render says so).  MNV_E_INVALID here: a null argument, a negative
  * count, negative iterations, learning rates that are not finite or negative; the fit's own refusals surface at the frame that builds the tree. */
 int mnv_renderer_set_lod_fit(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, const mnv_fit_params *params);
+/* The same with mnv_fit_params_ex (mnv_n3tree_fit_to_tree_ex with `params`; n_cams == 0 or params->steps == 0 = off):
+ * mnv_renderer_set_lod_fit is this call with MNV_FIT_SGD and batch_rays 0.  The optimizer's and the batching's refusals surface at the
+ * frame that builds the tree. */
+int mnv_renderer_set_lod_fit_ex(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, const mnv_fit_params_ex *params);
 
 /* ------------------------------------------------ deterministic synthetic trees */
 /* Integer-hash PRNG, IEEE-only arithmetic: bit-identical on every host. */

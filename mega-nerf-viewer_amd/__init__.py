@@ -152,6 +152,21 @@ class FitParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("lr_colour", C.c_float), ("lr_sigma", C.c_float), ("reserved", C.c_int32)]
 
 
+class AdamParams(C.Structure):
+    """mnv_adam_params"""
+    _fields_ = [("lr_colour", C.c_float), ("lr_sigma", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class FitParamsEx(C.Structure):
+    """mnv_fit_params_ex"""
+    _fields_ = [("steps", C.c_int32), ("optimizer", C.c_int32), ("lr_colour", C.c_float), ("lr_sigma", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("batch_rays", C.c_int32), ("tile", C.c_int32), ("seed", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+FIT_SGD, FIT_ADAM = 0, 1
+# Adam's rates for fitting rows (include/mnv.h, mnv_n3tree_fit_ex; the sweep behind them stands in tests/fit_adam_ref.py)
+ADAM_DEFAULTS = dict(lr_colour=0.03, lr_sigma=1.0, betas=(0.9, 0.999), eps=1e-8)
+
 FIT_SUMS = ("n_rays", "n_stopped", "n_samples", "n_skipped", "se_q32")   # the first five int64 words of mnv_fit_sums (8 in all)
 
 
@@ -472,6 +487,7 @@ _SIGNATURES = {
     "mnv_n3tree_make_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
     "mnv_renderer_set_view_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32]),
     "mnv_renderer_set_lod_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FitParams)]),
+    "mnv_renderer_set_lod_fit_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FitParamsEx)]),
     "mnv_renderer_set_cull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]),
     "mnv_rays_grad": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RenderOptions), C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -479,6 +495,13 @@ _SIGNATURES = {
     "mnv_rows_sgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
     "mnv_n3tree_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(FitParams), C.c_void_p]),
     "mnv_n3tree_fit_to_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RenderOptions), C.POINTER(FitParams), C.c_void_p]),
+    "mnv_rows_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(AdamParams), C.c_int64, C.c_void_p]),
+    "mnv_ray_batcher_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "mnv_ray_batcher_units": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "mnv_ray_batcher_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mnv_ray_batcher_destroy": (None, [C.c_void_p]),
+    "mnv_n3tree_fit_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(FitParamsEx), C.c_void_p, C.c_void_p]),
+    "mnv_n3tree_fit_to_tree_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RenderOptions), C.POINTER(FitParamsEx), C.c_void_p, C.c_void_p]),
     "mnv_rays_visibility": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RenderOptions), C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "mnv_tree_cull": (C.c_int, [C.POINTER(TreeView), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(CullCounts), C.c_void_p]),
@@ -903,10 +926,28 @@ class N3Tree:
                                             C.byref(h)))
         return N3Tree(h.value), kept, counts.as_dict()
 
-    def fit(self, cams, targets, opt: RenderOptions, iterations: int, lr_colour: float, lr_sigma: float) -> np.ndarray:
-        """N3Tree::fit: `iterations` full-batch gradient steps on this tree's rows (on the device) against `targets`, one float32 device
-        tensor [height, width, 4] per camera of `cams` (alpha 0 excludes a pixel).  The accel is rebuilt and the host arrays are refreshed.
-        -> int64 [iterations]: se_q32 of each iteration's rays before its step."""
+    @staticmethod
+    def _fit_params_ex(iterations, lr_colour, lr_sigma, optimizer, batch_rays, tile, seed, betas, eps) -> "FitParamsEx":
+        """mnv_fit_params_ex of fit's / fit_to's arguments; with optimizer "adam", rates given as None are ADAM_DEFAULTS'"""
+        opts = {"sgd": FIT_SGD, "adam": FIT_ADAM}
+        if optimizer not in opts:
+            raise MnvError(MNV_E_INVALID, "optimizer is 'sgd' or 'adam'")
+        if optimizer == "adam":
+            lr_colour = ADAM_DEFAULTS["lr_colour"] if lr_colour is None else lr_colour
+            lr_sigma = ADAM_DEFAULTS["lr_sigma"] if lr_sigma is None else lr_sigma
+        if lr_colour is None or lr_sigma is None:
+            raise MnvError(MNV_E_INVALID, "the SGD step needs lr_colour and lr_sigma")
+        return FitParamsEx(int(iterations), opts[optimizer], float(lr_colour), float(lr_sigma), float(betas[0]), float(betas[1]), float(eps), int(batch_rays),
+                           int(tile), int(seed))
+
+    def fit(self, cams, targets, opt: RenderOptions, iterations: int, lr_colour: Optional[float] = None, lr_sigma: Optional[float] = None, *,
+            optimizer: str = "sgd", batch_rays: int = 0, tile: int = 8, seed: int = 0, betas=ADAM_DEFAULTS["betas"], eps: float = ADAM_DEFAULTS["eps"],
+            return_counts: bool = False):
+        """N3Tree::fit / fit_ex: `iterations` gradient steps on this tree's rows (on the device) against `targets`, one float32 device
+        tensor [height, width, 4] per camera of `cams` (alpha 0 excludes a pixel).  optimizer "sgd" (mnv_rows_sgd_step) or "adam"
+        (mnv_rows_adam_step with betas / eps; rates left None are ADAM_DEFAULTS').  batch_rays 0: full batch; otherwise every step takes
+        batch_rays rays drawn across all cameras in units of tile x tile pixels (RayBatcher with `seed`).  The accel is rebuilt and the host
+        arrays are refreshed.  -> int64 [iterations]: se_q32 of each step's rays before its step; with return_counts (se_q32, n_rays)."""
         import torch
 
         n = len(cams)
@@ -918,20 +959,32 @@ class N3Tree:
         arr = (CameraStruct * n)(*[c.c for c in cams])
         ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in targets])
         se = np.zeros(max(int(iterations), 0), np.int64)
-        p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
-        _check(lib().mnv_n3tree_fit(self._h, arr, n, ptrs, C.byref(opt), C.byref(p), se.ctypes.data))
-        return se
+        if optimizer == "sgd" and batch_rays == 0 and not return_counts and lr_colour is not None and lr_sigma is not None:
+            p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
+            _check(lib().mnv_n3tree_fit(self._h, arr, n, ptrs, C.byref(opt), C.byref(p), se.ctypes.data))
+            return se
+        px = self._fit_params_ex(iterations, lr_colour, lr_sigma, optimizer, batch_rays, tile, seed, betas, eps)
+        n_rays = np.zeros_like(se)
+        _check(lib().mnv_n3tree_fit_ex(self._h, arr, n, ptrs, C.byref(opt), C.byref(px), se.ctypes.data, n_rays.ctypes.data))
+        return (se, n_rays) if return_counts else se
 
-    def fit_to(self, teacher: "N3Tree", cams, opt: RenderOptions, iterations: int, lr_colour: float, lr_sigma: float) -> np.ndarray:
-        """N3Tree::fit_to: fit against the frames the accel march renders of `teacher` (on the device) at `cams`; as fit otherwise."""
+    def fit_to(self, teacher: "N3Tree", cams, opt: RenderOptions, iterations: int, lr_colour: Optional[float] = None, lr_sigma: Optional[float] = None, *,
+               optimizer: str = "sgd", batch_rays: int = 0, tile: int = 8, seed: int = 0, betas=ADAM_DEFAULTS["betas"], eps: float = ADAM_DEFAULTS["eps"],
+               return_counts: bool = False):
+        """N3Tree::fit_to / fit_to_ex: fit against the frames the accel march renders of `teacher` (on the device) at `cams`; as fit otherwise."""
         n = len(cams)
         if n < 1:
             raise MnvError(MNV_E_INVALID, "at least one camera")
         arr = (CameraStruct * n)(*[c.c for c in cams])
         se = np.zeros(max(int(iterations), 0), np.int64)
-        p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
-        _check(lib().mnv_n3tree_fit_to_tree(self._h, teacher._h, arr, n, C.byref(opt), C.byref(p), se.ctypes.data))
-        return se
+        if optimizer == "sgd" and batch_rays == 0 and not return_counts and lr_colour is not None and lr_sigma is not None:
+            p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
+            _check(lib().mnv_n3tree_fit_to_tree(self._h, teacher._h, arr, n, C.byref(opt), C.byref(p), se.ctypes.data))
+            return se
+        px = self._fit_params_ex(iterations, lr_colour, lr_sigma, optimizer, batch_rays, tile, seed, betas, eps)
+        n_rays = np.zeros_like(se)
+        _check(lib().mnv_n3tree_fit_to_tree_ex(self._h, teacher._h, arr, n, C.byref(opt), C.byref(px), se.ctypes.data, n_rays.ctypes.data))
+        return (se, n_rays) if return_counts else se
 
     def gen_wireframe(self, max_depth: int = 100000) -> np.ndarray:
         """N3Tree::gen_wireframe (n3tree.cpp:249-329) on the host arrays: float32 [n_vertices, 9] (position, colour, normal), 24 vertices
@@ -1517,13 +1570,18 @@ class Renderer:
         arr = (CameraStruct * max(len(cams), 1))(*[c.c for c in cams])
         _check(lib().mnv_renderer_set_cull(self._h, arr if cams else None, len(cams), float(weight_thresh)))
 
-    def set_lod_fit(self, cams=(), iterations: int = 0, lr_colour: float = 0.0, lr_sigma: float = 0.0) -> None:
+    def set_lod_fit(self, cams=(), iterations: int = 0, lr_colour: Optional[float] = 0.0, lr_sigma: Optional[float] = 0.0, *, optimizer: str = "sgd",
+                    batch_rays: int = 0, tile: int = 8, seed: int = 0, betas=ADAM_DEFAULTS["betas"], eps: float = ADAM_DEFAULTS["eps"]) -> None:
         """VolumeRenderer::set_lod_fit: every tree set_lod / set_view_lod builds from now on is fitted to the full tree at `cams`
-        (N3Tree.fit_to) right after it is built; no camera or no iteration (the default) switches it off."""
+        (N3Tree.fit_to, with its keywords) right after it is built; no camera or no iteration (the default) switches it off."""
         cams = list(cams)
         arr = (CameraStruct * max(len(cams), 1))(*[c.c for c in cams])
-        p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
-        _check(lib().mnv_renderer_set_lod_fit(self._h, arr if cams else None, len(cams), C.byref(p)))
+        if optimizer == "sgd" and batch_rays == 0:
+            p = FitParams(int(iterations), float(lr_colour), float(lr_sigma), 0)
+            _check(lib().mnv_renderer_set_lod_fit(self._h, arr if cams else None, len(cams), C.byref(p)))
+            return
+        px = N3Tree._fit_params_ex(iterations, lr_colour, lr_sigma, optimizer, batch_rays, tile, seed, betas, eps)
+        _check(lib().mnv_renderer_set_lod_fit_ex(self._h, arr if cams else None, len(cams), C.byref(px)))
 
     def set_target(self, target=None, flags: int = 0) -> None:
         """VolumeRenderer::set_target: score every frame against `target`, a contiguous uint8 device tensor [height, width, 4], on the
@@ -2236,6 +2294,81 @@ def rows_sgd_step(data, master, acc, data_dim: int, lr_colour: float, lr_sigma: 
         raise MnvError(MNV_E_INVALID, f"data must be a contiguous 16-bit device tensor with at least {n} elements")
     _check(lib().mnv_rows_sgd_step(_ptr(data), master.data_ptr(), acc.data_ptr(), int(n_rows), int(data_dim), float(lr_colour), float(lr_sigma),
                                    C.c_void_p(stream)))
+
+
+def rows_adam_step(data, master, m1, m2, acc, data_dim: int, step: int, lr_colour: float = ADAM_DEFAULTS["lr_colour"], lr_sigma: float = ADAM_DEFAULTS["lr_sigma"],
+                   betas=ADAM_DEFAULTS["betas"], eps: float = ADAM_DEFAULTS["eps"], n_rows: Optional[int] = None, stream: int = 0) -> None:
+    """mnv_rows_adam_step: step number `step` (from 1) of the lazy Adam on the rows whose accumulators are not all zero (master, m1, m2
+    float32, data binary16 and acc int64 device tensors of n_rows * data_dim elements each; data may be a raw device pointer); clears the
+    accumulators it consumed."""
+    import torch
+
+    if n_rows is None:
+        n_rows = master.numel() // int(data_dim)
+    n = int(n_rows) * int(data_dim)
+    for name, t in (("master", master), ("m1", m1), ("m2", m2)):
+        _check_dev(name, t, torch.float32, n)
+    _check_dev("acc", acc, torch.int64, n)
+    if not isinstance(data, int) and (not data.is_cuda or not data.is_contiguous() or data.element_size() != 2 or data.numel() < n):
+        raise MnvError(MNV_E_INVALID, f"data must be a contiguous 16-bit device tensor with at least {n} elements")
+    p = AdamParams(float(lr_colour), float(lr_sigma), float(betas[0]), float(betas[1]), float(eps))
+    _check(lib().mnv_rows_adam_step(_ptr(data), master.data_ptr(), m1.data_ptr(), m2.data_ptr(), acc.data_ptr(), int(n_rows), int(data_dim), C.byref(p), int(step),
+                                    C.c_void_p(stream)))
+
+
+class RayBatcher:
+    """mnv_ray_batcher: batches of rays and targets drawn across a set of cameras and their target images (float32 device tensors
+    [height, width, 4], kept alive by this object) in a seeded order that changes with the epoch.  A unit is a pixel (tile 1) or an 8 x 8
+    pixel tile (tile 8); `units` is their total, `rays_per_unit` tile * tile."""
+
+    def __init__(self, cams, targets, tile: int = 8, seed: int = 0):
+        import torch
+
+        n = len(cams)
+        if n < 1 or len(targets) != n:
+            raise MnvError(MNV_E_INVALID, "one target image per camera, at least one camera")
+        for c, t in zip(cams, targets):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != c.width * c.height * 4:
+                raise MnvError(MNV_E_INVALID, "a target must be a contiguous float32 device tensor [height, width, 4] of its camera's size")
+        self._targets = list(targets)
+        arr = (CameraStruct * n)(*[c.c for c in cams])
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in targets])
+        h = C.c_void_p()
+        _check(lib().mnv_ray_batcher_create(arr, ptrs, n, int(tile), int(seed), C.byref(h)))
+        self._h = h
+        units, per = C.c_int64(), C.c_int32()
+        _check(lib().mnv_ray_batcher_units(self._h, C.byref(units), C.byref(per)))
+        self.units, self.rays_per_unit = int(units.value), int(per.value)
+
+    def draw(self, epoch: int, first: int, count: int, origins=None, dirs=None, target=None, stream: int = 0):
+        """mnv_ray_batcher_draw (asynchronous on `stream`): the units at places first .. first + count - 1 of the epoch's order, as float32
+        device tensors origins, dirs [count * rays_per_unit, 3] and target [count * rays_per_unit, 4] (allocated when not given): what
+        rays_grad takes as a flat list.  -> (origins, dirs, target)"""
+        import torch
+
+        n = max(int(count), 0) * self.rays_per_unit
+        if origins is None:
+            origins = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        if dirs is None:
+            dirs = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        if target is None:
+            target = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+        _check_dev("origins", origins, torch.float32, n * 3)
+        _check_dev("dirs", dirs, torch.float32, n * 3)
+        _check_dev("target", target, torch.float32, n * 4)
+        _check(lib().mnv_ray_batcher_draw(self._h, int(epoch), int(first), int(count), origins.data_ptr(), dirs.data_ptr(), target.data_ptr(), C.c_void_p(stream)))
+        return origins, dirs, target
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().mnv_ray_batcher_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def render_voxels_accel_batch(accel: int, cams, opt: RenderOptions, tile=None, part=None, rgba=None, rgba8=None,

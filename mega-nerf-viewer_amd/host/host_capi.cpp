@@ -284,6 +284,36 @@ int mnv_n3tree_fit_to_tree(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_c
     });
 }
 
+namespace {
+void copy_fit_sums(const std::vector<mnv_fit_sums> &sums, int64_t *se_q32_out, int64_t *n_rays_out) {
+    for (size_t i = 0; i < sums.size(); ++i) {
+        if (se_q32_out) se_q32_out[i] = sums[i].se_q32;
+        if (n_rays_out) n_rays_out[i] = sums[i].n_rays;
+    }
+}
+}  // namespace
+
+int mnv_n3tree_fit_ex(mnv_n3tree *t, const mnv_camera *cams, int32_t n_cams, const float *const *targets, const mnv_render_options *opt,
+                      const mnv_fit_params_ex *p, int64_t *se_q32_out, int64_t *n_rays_out) {
+    if (!t || !cams || !targets || !opt || !p) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit_ex: null argument");
+    if (n_cams < 1) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit_ex: no camera");
+    return guarded([&] {
+        copy_fit_sums(t->tree.fit_ex(std::vector<mnv_camera>(cams, cams + n_cams), std::vector<const float *>(targets, targets + n_cams), *opt, *p), se_q32_out,
+                      n_rays_out);
+        return MNV_OK;
+    });
+}
+
+int mnv_n3tree_fit_to_tree_ex(mnv_n3tree *t, const mnv_n3tree *teacher, const mnv_camera *cams, int32_t n_cams, const mnv_render_options *opt,
+                              const mnv_fit_params_ex *p, int64_t *se_q32_out, int64_t *n_rays_out) {
+    if (!t || !teacher || !cams || !opt || !p) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit_to_tree_ex: null argument");
+    if (n_cams < 1) return mnv::set_error(MNV_E_INVALID, "mnv_n3tree_fit_to_tree_ex: no camera");
+    return guarded([&] {
+        copy_fit_sums(t->tree.fit_to_ex(teacher->tree, std::vector<mnv_camera>(cams, cams + n_cams), *opt, *p), se_q32_out, n_rays_out);
+        return MNV_OK;
+    });
+}
+
 void mnv_data_format_parse(const char *str, int32_t *format, int32_t *basis_dim) {
     viewer::DataFormat f;
     f.parse(str ? str : "");
@@ -606,6 +636,15 @@ int mnv_renderer_set_cull(mnv_renderer *r, const mnv_camera *cams, int32_t n_cam
 int mnv_renderer_set_lod_fit(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, const mnv_fit_params *params) {
     if (!r || !params || (n_cams > 0 && !cams)) return mnv::set_error(MNV_E_INVALID, "null argument");
     if (n_cams < 0) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_lod_fit: negative camera count");
+    return guarded([&] {
+        r->rend.set_lod_fit(n_cams ? std::vector<mnv_camera>(cams, cams + n_cams) : std::vector<mnv_camera>(), *params);
+        return MNV_OK;
+    });
+}
+
+int mnv_renderer_set_lod_fit_ex(mnv_renderer *r, const mnv_camera *cams, int32_t n_cams, const mnv_fit_params_ex *params) {
+    if (!r || !params || (n_cams > 0 && !cams)) return mnv::set_error(MNV_E_INVALID, "null argument");
+    if (n_cams < 0) return mnv::set_error(MNV_E_INVALID, "mnv_renderer_set_lod_fit_ex: negative camera count");
     return guarded([&] {
         r->rend.set_lod_fit(n_cams ? std::vector<mnv_camera>(cams, cams + n_cams) : std::vector<mnv_camera>(), *params);
         return MNV_OK;

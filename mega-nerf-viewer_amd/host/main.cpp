@@ -67,6 +67,18 @@
 //                    1 and 20: the rates at which the numpy restatement's loss falls at every step on the test suite's fit scene, where
 //                    a leaf of the cut covers a few pixels of a frame; the gradient of a row is a SUM over the rays through its voxel,
 //                    so larger frames want smaller rates).  At most 2^24 pixels over the poses.
+//                    --fit_optimizer sgd|adam: the row step (mnv_rows_sgd_step; mnv_rows_adam_step, whose step does not depend on the
+//                    gradient's scale: rates 0.03 and 1 unless given, beta 0.9 / 0.999, eps 1e-8).  --fit_batch RAYS: every step takes
+//                    RAYS rays drawn across all poses (mnv_ray_batcher, N3Tree::fit_to_ex) in units of --fit_tile 1|8 pixels squared, in
+//                    the order --fit_seed S gives; the 2^24 bound does not apply then.  Defaults sgd / 0 (full batch) / 8 / 0.
+//                    --fit_seed takes all 64 bits (decimal, or hexadecimal with 0x).
+//   --fit_images PREFIX --fit_steps N [--fit_holdout K]   fit the tree this run is about to march -- the input tree (.npz, --points, --merge)
+//                    or its --lod / --lod_pixels cut -- to photographs: frame f of the --frames / --orbit loop has the target
+//                    PREFIX_%04d.ppm (the P6 files --out writes; channel = byte / 255, alpha 1), N steps of N3Tree::fit_ex with the
+//                    --fit_* flags above (sgd, full batch unless given).  Poses with f % K == K - 1 are held out.  Prints the mean PSNR
+//                    (mnv_frame_metrics, quantised) of the fitted and of the held-out poses before and after; --save_lod OUT.npz writes
+//                    the fitted tree; the frames then show it.  Refused with --lod_fit, --cull, --gpus, --use_splitting,
+//                    --use_guided_sampling.
 //   --merge B.npz    place the tree of B.npz into the input tree before anything else is done with it (N3Tree::merge: mnv_tree_merge_plan /
 //                    write): the union of the two structures in canonical breadth-first order.  --merge_at k:x,y,z after it names the
 //                    voxel of the base tree that is B's cube (depth k, integer corner); without it k and the corner are derived from the
@@ -187,6 +199,11 @@ void usage() {
               "                  [--cull W [--save_lod OUT.npz]]   march (and write) the tree without what this run's poses cannot see (weights <= W)\n"
               "                  [--lod_fit ITERS [--fit_lr_colour X] [--fit_lr_sigma Y]]   with --lod / --lod_pixels: fit that tree's rows to the full\n"
               "                   tree's frames at the poses of this run first (ITERS gradient steps)\n"
+              "                  [--fit_optimizer sgd|adam] [--fit_batch RAYS] [--fit_tile 1|8] [--fit_seed S]   with --lod_fit: the row step (adam: rates\n"
+              "                                     0.03 / 1 unless given) and ray batches drawn over all poses in pixel or 8 x 8 tile units (0: full batch)\n"
+              "                  [--fit_images PREFIX --fit_steps N [--fit_holdout K] [--save_lod OUT.npz]]   fit the tree this run marches (the input, --points,\n"
+              "                                     --merge, --lod or --lod_pixels tree) to PREFIX_%04d.ppm of this run's poses (the files --out writes) in N steps\n"
+              "                                     with the --fit_* flags above; poses f % K == K - 1 are held out; prints the PSNR before and after\n"
               "                  [--merge B.npz [--merge_at k:x,y,z] [--merge_mode over|add]]... [--save_lod OUT.npz]   place B's tree into a voxel of the\n"
               "                   input tree (default: the voxel its offset and scale name exactly); repeatable, folds left to right\n"
               "                  [--points FILE.npz|FILE.obj [--points_depth D] [--points_sigma S] [--points_min N] [--points_format RGBA|SH9...]\n"
@@ -829,7 +846,7 @@ int main(int argc, char **argv) {
         if ((args.has("target_mask") || args.has("ssim")) && !args.has("target")) throw std::runtime_error("--target_mask and --ssim need --target");
         const long lod = args.l("lod", 0);
         if (args.has("lod") && lod < 1) throw std::runtime_error("--lod takes a depth of at least 1");
-        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull") && !args.has("points") && !args.has("merge"))
+        if (args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull") && !args.has("points") && !args.has("merge") && !args.has("fit_images"))
             throw std::runtime_error("--save_lod needs --lod, --lod_pixels or --cull");
         const float cull_thresh = args.f("cull", 0.f);
         if (args.has("cull") && (!std::isfinite(cull_thresh) || cull_thresh < 0.f)) throw std::runtime_error("--cull takes a finite weight threshold, 0 or more");
@@ -843,10 +860,43 @@ int main(int argc, char **argv) {
         if (args.has("lod_pixels") && (args.has("lod") || args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
             throw std::runtime_error("--lod_pixels renders a cut copy of the tree on one GPU: it cannot be combined with --lod, --gpus, --use_splitting or --use_guided_sampling");
         const long lod_fit = args.l("lod_fit", 0);
-        const float fit_lr_colour = args.f("fit_lr_colour", 1.f), fit_lr_sigma = args.f("fit_lr_sigma", 20.f);
+        const std::string fit_optimizer = args.get("fit_optimizer", "sgd");
+        if (fit_optimizer != "sgd" && fit_optimizer != "adam") throw std::runtime_error("--fit_optimizer takes sgd or adam");
+        const bool fit_adam = fit_optimizer == "adam";
+        // the rates: SGD's were chosen on the test suite's fit scene (tests/fit_cases.py), Adam's likewise (tests/fit_adam_ref.py)
+        const float fit_lr_colour = args.f("fit_lr_colour", fit_adam ? 0.03f : 1.f), fit_lr_sigma = args.f("fit_lr_sigma", fit_adam ? 1.f : 20.f);
+        const long fit_batch = args.l("fit_batch", 0), fit_tile = args.l("fit_tile", 8);
+        uint64_t fit_seed = 0;  // all 64 bits: decimal, or hexadecimal with 0x
+        if (args.has("fit_seed")) {
+            const std::string text = args.get("fit_seed", "");
+            size_t used = 0;
+            try {
+                if (text.empty() || text[0] == '-') throw std::invalid_argument(text);
+                fit_seed = std::stoull(text, &used, 0);
+            } catch (const std::exception &) {
+                used = 0;
+            }
+            if (used == 0 || used != text.size()) throw std::runtime_error("--fit_seed takes an unsigned 64-bit seed");
+        }
         if (args.has("lod_fit") && lod_fit < 1) throw std::runtime_error("--lod_fit takes an iteration count of at least 1");
-        if ((args.has("lod_fit") || args.has("fit_lr_colour") || args.has("fit_lr_sigma")) && !((args.has("lod") || args.has("lod_pixels")) && args.has("lod_fit")))
-            throw std::runtime_error("--lod_fit needs --lod or --lod_pixels; --fit_lr_colour and --fit_lr_sigma need --lod_fit");
+        const bool fit_flag = args.has("fit_lr_colour") || args.has("fit_lr_sigma") || args.has("fit_optimizer") || args.has("fit_batch") || args.has("fit_tile") ||
+                              args.has("fit_seed");
+        const std::string fit_images = args.get("fit_images", "");
+        const long fit_steps = args.l("fit_steps", 0), fit_holdout = args.l("fit_holdout", 0);
+        if (args.has("fit_images")) {
+            if (fit_images.empty()) throw std::runtime_error("--fit_images takes the prefix of the target files (PREFIX_%04d.ppm)");
+            if (!args.has("fit_steps") || fit_steps < 1) throw std::runtime_error("--fit_images needs --fit_steps N with N of at least 1");
+            if (args.has("fit_holdout") && fit_holdout < 2) throw std::runtime_error("--fit_holdout takes K of at least 2 (every K-th pose is held out)");
+            if (args.has("lod_fit") || args.has("cull") || args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling"))
+                throw std::runtime_error("--fit_images fits the tree this run marches on one GPU: it cannot be combined with --lod_fit, --cull, --gpus, --use_splitting or --use_guided_sampling");
+        } else if (args.has("fit_steps") || args.has("fit_holdout")) {
+            throw std::runtime_error("--fit_steps and --fit_holdout need --fit_images");
+        }
+        if (!args.has("fit_images") && (args.has("lod_fit") || fit_flag) && !((args.has("lod") || args.has("lod_pixels")) && args.has("lod_fit")))
+            throw std::runtime_error("--lod_fit needs --lod or --lod_pixels; --fit_lr_colour, --fit_lr_sigma, --fit_optimizer, --fit_batch, --fit_tile and --fit_seed need --lod_fit or --fit_images");
+        if (fit_tile != 1 && fit_tile != 8) throw std::runtime_error("--fit_tile takes 1 or 8");
+        if (fit_batch < 0 || fit_batch > (1L << 22) || fit_batch % (fit_tile * fit_tile) != 0)
+            throw std::runtime_error("--fit_batch takes a ray count that is a multiple of the tile's pixels, at most 4194304 (0: full batch)");
         if (args.has("lod") && (args.has("gpus") || args.has("use_splitting") || args.has("use_guided_sampling")))
             throw std::runtime_error("--lod renders a truncated copy of the tree on one GPU: it cannot be combined with --gpus, --use_splitting or --use_guided_sampling");
         if (args.has("gpus")) return run_distributed(args, (int)args.l("gpus", 1));  // before any HIP call in this process
@@ -859,7 +909,8 @@ int main(int argc, char **argv) {
             tree_owner->open(args.file);  // main.cpp:528
         if (!merges.empty()) merge_trees(merges, tree_owner);
         viewer::N3Tree &tree = *tree_owner;
-        if ((args.has("points") || args.has("merge")) && args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull")) {
+        if ((args.has("points") || args.has("merge")) && args.has("save_lod") && !args.has("lod") && !args.has("lod_pixels") && !args.has("cull") &&
+            !args.has("fit_images")) {  // (--fit_images writes the tree after its fit)
             tree.save_npz(args.get("save_lod", ""));
             std::printf("save_lod: %d chunks -> %s\n", tree.capacity, args.get("save_lod", "").c_str());
         }
@@ -913,7 +964,13 @@ int main(int argc, char **argv) {
         rend.projection = projection == "ortho" ? MNV_PROJ_ORTHO : projection == "equirect" ? MNV_PROJ_EQUIRECT : MNV_PROJ_PINHOLE;
         // --lod_fit: the camera of every pose this run renders (the frame loop below, stepped on a copy of the camera), and the fit of a cut
         std::vector<mnv_camera> fit_cams;
-        const mnv_fit_params fit_params{(int32_t)lod_fit, fit_lr_colour, fit_lr_sigma, 0};
+        mnv_fit_params_ex fit_params = {};  // (sgd, no batch: what --lod_fit was before it had these flags, N3Tree::fit_to)
+        fit_params.steps = (int32_t)lod_fit;
+        fit_params.optimizer = fit_adam ? MNV_FIT_ADAM : MNV_FIT_SGD;
+        fit_params.lr_colour = fit_lr_colour, fit_params.lr_sigma = fit_lr_sigma;
+        fit_params.beta1 = 0.9f, fit_params.beta2 = 0.999f, fit_params.eps = 1e-8f;
+        fit_params.batch_rays = (int32_t)fit_batch, fit_params.tile = (int32_t)fit_tile;
+        fit_params.seed = fit_seed;
         if (lod_fit > 0) {
             viewer::Camera walk = rend.camera;
             for (long f = 0; f < std::max<long>(frames, 1) && fit_cams.size() < 4096; ++f) {
@@ -926,13 +983,111 @@ int main(int argc, char **argv) {
         }
         auto fit_cut = [&](viewer::N3Tree &cut) {
             if (lod_fit < 1) return;
-            const std::vector<int64_t> se = cut.fit_to(tree, fit_cams, *rend.options.c_abi(), fit_params);
+            const std::vector<mnv_fit_sums> sums = cut.fit_to_ex(tree, fit_cams, *rend.options.c_abi(), fit_params);
             std::printf("lod_fit: %zu pose(s), lr_colour %g, lr_sigma %g; mean squared error of the fitted rays before each step (x 1e6):", fit_cams.size(),
                         (double)fit_lr_colour, (double)fit_lr_sigma);
-            for (int64_t q : se) std::printf(" %.3f", (double)q / 4294967296.0 / (3.0 * (double)width * height * (double)fit_cams.size()) * 1e6);
+            // full batch: over every pixel of the poses, as before; a batch: over the rays of that batch that count
+            for (const mnv_fit_sums &q : sums)
+                std::printf(" %.3f", (double)q.se_q32 / 4294967296.0 /
+                                         (3.0 * (fit_batch > 0 ? (double)std::max<int64_t>(q.n_rays, 1) : (double)width * height * (double)fit_cams.size())) * 1e6);
             std::printf("\n");
         };
-        if (lod > 0) {
+        // --fit_images: the tree this run marches -- the input tree, or its --lod / --lod_pixels cut -- is fitted to photographs of this run's
+        // poses (PREFIX_%04d.ppm, the files --out writes: byte / 255, alpha 1) with N3Tree::fit_ex, then marched by the frames below
+        std::unique_ptr<viewer::N3Tree> fit_owner;  // the cut, where there is one: the renderer marches it in place of its own
+        if (args.has("fit_images")) {
+            if (tree.N <= 0) throw std::runtime_error("--fit_images needs a tree (N > 0)");
+            if (frames < 1 || frames > 4096) throw std::runtime_error("--fit_images serves 1 to 4096 poses (--frames)");
+            std::vector<mnv_camera> cams;
+            std::vector<mnv_lod_view> views;
+            viewer::Camera walk = rend.camera;
+            for (long f = 0; f < frames; ++f) {
+                walk._update();
+                cams.push_back(walk.c_abi());
+                views.push_back({{walk.center.x, walk.center.y, walk.center.z}, std::max(walk.fx, walk.fy)});
+                if (orbit != 0.0) orbit_step(walk, orbit);
+            }
+            if (lod > 0)
+                fit_owner = tree.make_lod((int)lod);
+            else if (args.has("lod_pixels"))
+                fit_owner = tree.make_view_lod(views, lod_pixels, (int)lod_min, (int)lod_max);
+            viewer::N3Tree &subject = fit_owner ? *fit_owner : tree;
+            const size_t px = (size_t)width * height;
+            std::vector<mnv::Buffer<float>> image((size_t)frames);
+            std::vector<mnv::Buffer<uint8_t>> image8((size_t)frames);
+            std::vector<uint8_t> rgb(px * 3), rgba8_host(px * 4);
+            std::vector<float> rgba_host(px * 4);
+            for (long f = 0; f < frames; ++f) {
+                char name[4096];
+                int32_t w = 0, h = 0, ch = 0;
+                std::snprintf(name, sizeof(name), "%s_%04ld.ppm", fit_images.c_str(), f);
+                mnv_ok(mnv_pnm_read(name, width, height, rgb.data(), (int64_t)rgb.size(), &w, &h, &ch), "--fit_images");
+                if (ch != 3) throw std::runtime_error(std::string("--fit_images: ") + name + " is not a P6 file");
+                for (size_t p = 0; p < px; ++p) {
+                    for (int k = 0; k < 3; ++k) {
+                        rgba8_host[p * 4 + k] = rgb[p * 3 + k];
+                        rgba_host[p * 4 + k] = (float)rgb[p * 3 + k] / 255.f;
+                    }
+                    rgba8_host[p * 4 + 3] = 255;
+                    rgba_host[p * 4 + 3] = 1.f;
+                }
+                hip_ok(image[(size_t)f].alloc(px * 4), "hipMalloc(fit image)");
+                hip_ok(image8[(size_t)f].alloc(px * 4), "hipMalloc(fit image, bytes)");
+                hip_ok(hipMemcpy(image[(size_t)f].get(), rgba_host.data(), px * 16, hipMemcpyHostToDevice), "upload fit image");
+                hip_ok(hipMemcpy(image8[(size_t)f].get(), rgba8_host.data(), px * 4, hipMemcpyHostToDevice), "upload fit image, bytes");
+            }
+            std::vector<mnv_camera> train_cams;
+            std::vector<const float *> train_images;
+            std::vector<long> train, held;
+            for (long f = 0; f < frames; ++f) {
+                if (fit_holdout > 0 && f % fit_holdout == fit_holdout - 1) {
+                    held.push_back(f);
+                } else {
+                    train.push_back(f);
+                    train_cams.push_back(cams[(size_t)f]);
+                    train_images.push_back(image[(size_t)f].get());
+                }
+            }
+            if (train.empty()) throw std::runtime_error("--fit_images: every pose is held out");
+            mnv_render_options march = *rend.options.c_abi();
+            march.render_depth = false;
+            mnv::Buffer<float> frame;
+            mnv::Buffer<mnv_metric_sums> sums_dev;
+            hip_ok(frame.alloc(px * 4), "hipMalloc(fit frame)");
+            hip_ok(sums_dev.alloc(1), "hipMalloc(metric sums)");
+            auto mean_psnr = [&](const std::vector<long> &poses) {  // mnv_frame_metrics of the tree's frames against the files, quantised
+                double sum = 0.0;
+                for (long f : poses) {
+                    mnv_ok(mnv_render_voxels_accel(subject.device.accel, &cams[(size_t)f], &march, mnv_rect{0, 0, width, height}, frame.get(), nullptr, nullptr),
+                           "mnv_render_voxels_accel (--fit_images)");
+                    hip_ok(hipMemset(sums_dev.get(), 0, sizeof(mnv_metric_sums)), "clear metric sums");
+                    mnv_ok(mnv_frame_metrics(frame.get(), image8[(size_t)f].get(), width, height, MNV_METRIC_QUANTISED, nullptr, sums_dev.get(), nullptr, nullptr, nullptr),
+                           "mnv_frame_metrics");
+                    mnv_metric_sums host{};
+                    hip_ok(hipMemcpy(&host, sums_dev.get(), sizeof(host), hipMemcpyDeviceToHost), "download metric sums");
+                    mnv_frame_metric_values m{};
+                    mnv_ok(mnv_metrics_finish(&host, &m), "mnv_metrics_finish");
+                    sum += m.psnr;
+                }
+                return poses.empty() ? 0.0 : sum / (double)poses.size();
+            };
+            if (!subject.device.accel) throw std::runtime_error("--fit_images: the tree has no packed accel to march");
+            const double train_before = mean_psnr(train), held_before = mean_psnr(held);
+            mnv_fit_params_ex p = fit_params;
+            p.steps = (int32_t)fit_steps;
+            subject.fit_ex(train_cams, train_images, march, p);
+            const double train_after = mean_psnr(train), held_after = mean_psnr(held);
+            std::printf("fit_images: %zu pose(s) fitted, %zu held out, %ld %s step(s), lr_colour %g, lr_sigma %g, batch %ld; PSNR of the fitted poses %.4f -> %.4f dB",
+                        train.size(), held.size(), fit_steps, fit_adam ? "adam" : "sgd", (double)fit_lr_colour, (double)fit_lr_sigma, fit_batch, train_before, train_after);
+            if (!held.empty()) std::printf(", of the held-out poses %.4f -> %.4f dB", held_before, held_after);
+            std::printf("\n");
+            if (args.has("save_lod")) {
+                subject.save_npz(args.get("save_lod", ""));
+                std::printf("save_lod: %d of %d chunks -> %s\n", subject.capacity, tree.capacity, args.get("save_lod", "").c_str());
+            }
+            rend.set(subject, fit_owner ? (long)subject.capacity : max_capacity);  // the frames below show the fitted tree
+        }
+        if (lod > 0 && !args.has("fit_images")) {
             if (tree.N <= 0) throw std::runtime_error("--lod needs a tree (N > 0)");
             rend.set_lod((int)lod);
             if (args.has("save_lod")) {
@@ -942,7 +1097,7 @@ int main(int argc, char **argv) {
                 std::printf("save_lod: depth %ld, %d of %d chunks -> %s\n", lod, cut->capacity, tree.capacity, args.get("save_lod", "").c_str());
             }
         }
-        if (args.has("lod_pixels")) {
+        if (args.has("lod_pixels") && !args.has("fit_images")) {
             if (tree.N <= 0) throw std::runtime_error("--lod_pixels needs a tree (N > 0)");
             // the eye of every pose this run renders: the frame loop below, stepped on a copy of the camera
             std::vector<mnv_lod_view> views;

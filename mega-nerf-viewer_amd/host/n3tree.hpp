@@ -138,6 +138,13 @@ struct N3Tree {
     // fit against the frames of `teacher` (on the device with its accel) at the cameras: a level of detail fitted to its full tree.
     std::vector<int64_t> fit_to(const N3Tree &teacher, const std::vector<mnv_camera> &cams, const mnv_render_options &opt, const mnv_fit_params &params,
                                 void *hip_stream = nullptr);
+    // The same with a choice of row step (SGD, Adam) and of batching (full batch, or ray batches drawn across all cameras by a
+    // mnv_ray_batcher; include/mnv.h, mnv_n3tree_fit_ex).  fit / fit_to are these with SGD and full batch.  Returns every step's sums
+    // (se_q32 and n_rays among them) before its step.
+    std::vector<mnv_fit_sums> fit_ex(const std::vector<mnv_camera> &cams, const std::vector<const float *> &targets, const mnv_render_options &opt,
+                                     const mnv_fit_params_ex &params, void *hip_stream = nullptr);
+    std::vector<mnv_fit_sums> fit_to_ex(const N3Tree &teacher, const std::vector<mnv_camera> &cams, const mnv_render_options &opt,
+                                        const mnv_fit_params_ex &params, void *hip_stream = nullptr);
 
     // A tree from a coloured point cloud (include/mnv.h, "a tree from a coloured point cloud": mnv_point_tree_create / add / finish /
     // write): occupancy at depth params.depth, the chunks above it, mean colours and one density, as a new tree on the device with parent,

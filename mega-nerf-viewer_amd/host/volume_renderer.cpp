@@ -212,9 +212,9 @@ struct VolumeRenderer::Impl {
     }
     // set_lod_fit: the cameras and parameters every level of detail is fitted with when it is built (no iterations: off)
     std::vector<mnv_camera> lod_fit_cams;
-    mnv_fit_params lod_fit{};
+    mnv_fit_params_ex lod_fit{};
     void fit_lod(N3Tree &cut, const RenderOptions &o) {
-        if (lod_fit.iterations > 0 && !lod_fit_cams.empty()) cut.fit_to(*tree, lod_fit_cams, *o.c_abi(), lod_fit, stream);
+        if (lod_fit.steps > 0 && !lod_fit_cams.empty()) cut.fit_to_ex(*tree, lod_fit_cams, *o.c_abi(), lod_fit, stream);
     }
     N3Tree &march_tree() const { return lod_tree ? *lod_tree : *tree; }
     void drop_lod_trees() {  // (frames in flight may march them)
@@ -660,7 +660,17 @@ void VolumeRenderer::set_cull(const std::vector<mnv_camera> &cams, float weight_
 bool VolumeRenderer::cull() const { return !impl_->cull_cams.empty(); }
 
 void VolumeRenderer::set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params &params) {
-    if (params.iterations < 0) throw StatusError(MNV_E_INVALID, "set_lod_fit: negative iteration count");
+    mnv_fit_params_ex ex = {};  // SGD, full batch: N3Tree::fit_to_ex with these is N3Tree::fit_to
+    ex.steps = params.iterations;
+    ex.optimizer = MNV_FIT_SGD;
+    ex.lr_colour = params.lr_colour;
+    ex.lr_sigma = params.lr_sigma;
+    ex.tile = 8;
+    set_lod_fit(cams, ex);
+}
+
+void VolumeRenderer::set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params_ex &params) {
+    if (params.steps < 0) throw StatusError(MNV_E_INVALID, "set_lod_fit: negative iteration count");
     if (!std::isfinite(params.lr_colour) || !std::isfinite(params.lr_sigma) || params.lr_colour < 0.f || params.lr_sigma < 0.f)
         throw StatusError(MNV_E_INVALID, "set_lod_fit: the learning rates must be finite and not negative");
     Impl &I = *impl_;

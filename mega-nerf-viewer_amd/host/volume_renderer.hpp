@@ -184,6 +184,9 @@ struct VolumeRenderer {
     // frames of the tree that was set at the listed cameras; trees built before are dropped, so the next frame builds and fits anew.
     // Refused wherever set_lod is (render() says so).  Refused here: negative iterations, learning rates that are not finite or negative.
     void set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params &params);
+    // The same with a choice of row step and batching (N3Tree::fit_to_ex; mnv_n3tree_fit_to_tree_ex); the overload above is this one with
+    // SGD and full batch.  The optimizer's and the batching's own refusals surface at the frame that builds the tree.
+    void set_lod_fit(const std::vector<mnv_camera> &cams, const mnv_fit_params_ex &params);
 
     // What the last render() did (the reference prints these to stdout).
     struct FrameStats {
